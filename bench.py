@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path: the fused pseudo-transient pressure-Poisson iteration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up (build check, fields, plan phase), W warm-up iterations, the K timed
+ones, the outputs (--dump-outputs DIR) and the line.  --full adds everything else described below — the untimed self-check
+(config.verified), the `strong` measurement, `config_b`, the CPU baseline and the live roofline.traffic — each of which the
+matching --no-* option still leaves out.
 
 Metric (BASELINE.json): Mcells·PT-iter/s (+ achieved HBM GB/s) on the 512³ lid-driven-cavity Poisson-only
 configuration (BASELINE.json configs[2]; synthetic, SURVEY.md §8d Config 3).  One "step" = one PT iteration
 {update_dPrdτ!; update_Pr!; set_bc_Pr!} (multi.jl:459-463) over the whole grid; the K timed steps are issued as passes
 of the planned depth (two, three or four iterations per launch of k_pt_sweep2 / k_pt_sweepN; single sweeps for a
 remainder).  Fields are resident in HBM before the timed region; an untimed plan phase before the warm-up lets the
-library time its tile shapes once.  After the timed region every line CERTIFIES ITSELF (config.verified, untimed): one
+library time its tile shapes once.  With --full, after the timed region the line CERTIFIES ITSELF (config.verified, untimed): one
 more pass of exactly the timed kernel instance — same depth, same tile variant, same arithmetic build — from the state
 the run left behind is compared on the device, bit for bit in STRICT mode (FAST: relative L2 ≤ 1e-6), with as many one-thread-per-cell single sweeps
 (N>1: one pass of the slab schedule against {single sweep; update_halo!(Pr)} per iteration, multi.jl:459-463); a mismatch
@@ -18,7 +23,7 @@ prints verified: false and exits with status 3.
 For N>1 every rank owns one 512×512×512 z-slab of an implicit global grid 512×512×(N·510+2) (weak scaling, the
 reference's own model: local size fixed, multi.jl:325,338); per pass the `depth` outermost own planes of Pr and depth−1
 of dPrdτ travel to each z neighbour behind the interior sweep — by RCCL send/recv over xGMI inside libns3d.so
-(ns3d_mgpu_create_rank, ns3d_slab_iterate).  The same line carries a `strong` object: the same GLOBAL grid (BASELINE:
+(ns3d_mgpu_create_rank, ns3d_slab_iterate).  With --full the same line carries a `strong` object: the same GLOBAL grid (BASELINE:
 "512³ grid, 1/2/4/8 MI355X") split into N z-slabs, measured right after the weak run with the same K and W.  `python bench.py --gpus N` without a launcher starts its N ranks itself (torch.distributed.run as a
 child process, before this process touches the GPU).  The ranks agree COLLECTIVELY on the transport: a gloo group comes up
 first (control plane: unique id, barriers, timing), RCCL is brought up and probed with a verified plane exchange, and only
@@ -49,6 +54,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E nominal, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_SAMPLE = 2500000   # --dump-outputs: values per array beyond which a seeded sample is written (2 x 20 MB in fp64)
 
 
 def algorithmic_bytes(nx, ny, nz, itemsize):
@@ -230,7 +236,15 @@ def main():
     ap.add_argument("--transport", default=os.environ.get("NS3D_BENCH_TRANSPORT", "auto"), choices=["auto", "rccl", "host"],
                     help="N>1: rccl = libns3d's RCCL communicator (fails loudly if it cannot come up), host = host-staged "
                          "over gloo, auto = rccl with a collective fall-back to host")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the self-check, `strong`, `config_b`, the CPU baseline and the live roofline.traffic "
+                         "(each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps, write Pr and dPrdtau as the timed path left them to DIR/<name>.npy; "
+                         "arrays of more than %d values as a seeded sample (dump_outputs)" % DUMP_SAMPLE)
     a = ap.parse_args()
+    if a.dump_outputs is not None and a.gpus > 1:
+        ap.error("--dump-outputs writes the fields of a one-GPU run")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))
@@ -257,16 +271,16 @@ def main():
     p = cavity_params(a.n, a.nz)
     if a.scaling == "strong" and world > 1:
         p = strong_params(a.n, p.nz, world)
-    head = run_case(a, world, rank, device, ndev, shared_gpu, p, a.scaling)
+    head = run_case(a, world, rank, device, ndev, shared_gpu, p, a.scaling, dump=a.dump_outputs)
     strong = None
-    if not a.no_strong and a.scaling == "weak":
+    if a.full and not a.no_strong and a.scaling == "weak":
         # BASELINE.json's metric reads "512³ grid, 1/2/4/8 MI355X": the same GLOBAL grid split in z, next to the weak headline
         if world == 1:
             strong = strong_object(head, world)
         else:
             strong = strong_object(run_case(a, world, rank, device, ndev, shared_gpu, strong_params(a.n, p.nz, world), "strong"), world)
     config_b = None
-    if world == 1 and not a.no_config_b:
+    if world == 1 and a.full and not a.no_config_b:
         config_b = config_b_object(a, device, ndev, shared_gpu)
     ok = True
     if rank == 0:
@@ -275,7 +289,7 @@ def main():
             out["strong"] = strong
         if world == 1 and config_b is not None:
             out["config_b"] = config_b
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(a.n, 128, a.cpu_iters, a.dtype)
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
@@ -342,9 +356,28 @@ def strong_object(r, world):
             "finite": r["finite"]}
 
 
-def run_case(a, world, rank, device, ndev, shared_gpu, p, scaling):
+def dump_outputs(out_dir, fields):
+    """--dump-outputs: each field as out_dir/<name>.npy in the run's element type — the whole array in column-major (Fortran)
+    order up to DUMP_SAMPLE values, beyond that the values at DUMP_SAMPLE column-major positions drawn without replacement from a
+    generator seeded by the array's size, in increasing order, so that two runs (or two builds) with the same arguments write
+    the same positions."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in fields.items():
+        n = t.numel()
+        if n <= DUMP_SAMPLE:
+            v = np.asfortranarray(t.permute(2, 1, 0).cpu().numpy().transpose(2, 1, 0))
+        else:
+            idx = np.sort(np.random.Generator(np.random.MT19937(n)).choice(n, DUMP_SAMPLE, replace=False))
+            flat = t.permute(2, 1, 0).reshape(-1)             # (nx,ny,nz) with strides (1,nx,nx*ny): a view, column-major
+            v = flat[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def run_case(a, world, rank, device, ndev, shared_gpu, p, scaling, dump=None):
     """One timed measurement: plan (untimed), W warm-up iterations, EXACTLY K timed iterations between barriers + device
-    synchronisation, then the untimed self-check.  Returns a dict on every rank (timings are the maximum over ranks)."""
+    synchronisation, the outputs to `dump` if given, then (--full) the untimed self-check.  Returns a dict on every rank
+    (timings are the maximum over ranks)."""
     from navierstokes3d_amd import kernels as K
     from navierstokes3d_amd import lib as L
     from navierstokes3d_amd.halo import ZSlabGrid
@@ -513,6 +546,8 @@ def run_case(a, world, rank, device, ndev, shared_gpu, p, scaling):
         t = torch.tensor([wall, dev_ms], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, dev_ms = t[0].item(), t[1].item()
+    if dump is not None:
+        dump_outputs(dump, {"Pr": st["Pr"], "dPrdtau": st["D"]})
     if mg is not None:
         err = mg.slab_residual()
     elif slab is not None:
@@ -529,7 +564,7 @@ def run_case(a, world, rank, device, ndev, shared_gpu, p, scaling):
     # update_halo!(Pr)} — the reference's own per-iteration sequence, multi.jl:459-463.  STRICT: bit for bit on the device.
     verify = {"against": None, "iterations": 0, "bitwise": None, "rel_l2": None}
     verified = None
-    if not a.no_verify:
+    if a.full and not a.no_verify:
         vd = max(passes) if passes else 0
         if vd >= 1:
             vctx = ctx
@@ -672,8 +707,12 @@ def json_line(a, world, r):
     must_move = algorithmic_bytes(nx, ny, nz, itemsize)          # bytes ONE pass has to move, per launch
     physical = must_move / (kern_ms * 1e-3) / 1e9
     effective = r["effective"]                       # 40 B per cell and iteration
-    traffic, traffic_source = None, "--no-traffic" if a.no_traffic else "N > 1"
-    if world == 1 and not a.no_traffic:
+    traffic, traffic_source = None, "N > 1"
+    if not a.full:
+        traffic_source = "without --full"
+    elif a.no_traffic:
+        traffic_source = "--no-traffic"
+    if world == 1 and a.full and not a.no_traffic:
         traffic, traffic_source = measure_traffic(a, r)
         if traffic is None:
             sys.stderr.write("bench.py: roofline.traffic not measured live (%s); falling back to profiles/\n" % traffic_source)

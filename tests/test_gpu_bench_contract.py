@@ -1,5 +1,5 @@
-"""bench.py keeps its contract: one JSON line on stdout with the driver's keys plus `roofline` and `cpu_baseline`
-(small grid, a handful of steps; the numbers themselves are not judged here)."""
+"""bench.py keeps its contract: one JSON line on stdout with the driver's keys plus `roofline`, and with --full the self-check,
+`strong`, `config_b` and `cpu_baseline` (small grid, a handful of steps; the numbers themselves are not judged here)."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("extra", [[], ["--mode", "fast", "--dtype", "f32", "--no-cpu-baseline", "--no-traffic"],
                                    ["--steps", "5", "--no-cpu-baseline", "--no-traffic"]])
 def test_bench_prints_one_json_line(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "96", "--steps", "6", "--warmup", "2", "--cpu-iters", "2"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--grid", "96", "--steps", "6", "--warmup", "2", "--cpu-iters", "2"] + extra
     out = subprocess.run(cmd, cwd=ROOT, check=True, capture_output=True, text=True, timeout=600).stdout
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1, out
@@ -62,7 +62,7 @@ def test_bench_gpus_2_as_typed_starts_its_own_ranks():
     before any GPU call) and relays rank 0's line.  On this one-GPU box the two ranks share the device, so the collective
     transport choice is the host-staged one over gloo — and the line says so; the RCCL data plane needs the multi-GPU node."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "96", "--steps", "6", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--grid", "96", "--steps", "6", "--warmup", "2"]
     out = subprocess.run(cmd, cwd=ROOT, check=True, capture_output=True, text=True, timeout=900, env=env).stdout
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1, out
@@ -88,9 +88,49 @@ def test_bench_exits_nonzero_when_the_self_check_fails():
     """config.verified is load-bearing: with NS3D_BENCH_SABOTAGE=1 the checker perturbs one value of the reference side and the
     run must print verified: false and exit with a non-zero status."""
     env = dict(os.environ, NS3D_BENCH_SABOTAGE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "96", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--grid", "96", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
            "--no-traffic"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode != 0
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["config"]["verified"] is False and d["config"]["verify"]["bitwise"] is False
+
+
+def test_plain_run_times_the_headline_only_and_dumps_what_it_computed(hip, oracle, tmp_path):
+    """A plain run (no --full) sets up, warms up, times the K steps and prints the line — no self-check, `strong`, `config_b`,
+    CPU baseline or live traffic measurement.  --dump-outputs writes Pr and dPrdτ as the timed path left them: W + K PT
+    iterations from Pr = dPrdτ = 0 on bench.py's seeded ∇V, which the oracle's unfused loop reproduces bit for bit (STRICT).
+    160×160×100: Pr (2.56 M values) is written as the seeded sample, dPrdτ (2.45 M) whole."""
+    import numpy as np
+    import torch
+    import bench
+    from navierstokes3d_amd.params import cavity_params
+    assert 2 * bench.DUMP_SAMPLE * 8 < 64 << 20                   # two fp64 samples stay under 64 MB whatever the grid
+    n, nz, steps, warmup = 160, 100, 5, 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--grid", str(n), "--grid-nz", str(nz), "--steps", str(steps),
+           "--warmup", str(warmup), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=ROOT, check=True, capture_output=True, text=True, timeout=600).stdout
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1, out
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mcells*iter/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and "metric" in d
+    assert not {"strong", "config_b", "cpu_baseline"} & set(d) and d["config"]["verified"] is None
+    assert not d["roofline"]["traffic_source"].startswith("measured")
+    assert sorted(os.listdir(tmp_path)) == ["Pr.npy", "dPrdtau.npy"]
+
+    p = cavity_params(n, nz)
+    gen = torch.Generator(device="cuda"); gen.manual_seed(12345)           # bench.py run_case, rank 0
+    rhs = hip.zeros((n, n, nz), torch.float64)
+    rhs.permute(2, 1, 0).uniform_(-1e-3, 1e-3, generator=gen)
+    rhs = hip.to_numpy(rhs)
+    Pr, D = oracle.zeros((n, n, nz)), oracle.zeros((n - 2, n - 2, nz - 2))
+    for _ in range(warmup + steps):
+        oracle.update_dPrdtau(Pr, D, rhs, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz)
+        oracle.update_Pr(Pr, D, p.dtau)
+        oracle.set_bc_Pr(Pr, 0, False, 0.0, p.dz, nz, 0.0, p.rho)
+    got_P, got_D = np.load(tmp_path / "Pr.npy"), np.load(tmp_path / "dPrdtau.npy")
+    assert got_P.dtype == np.float64 and got_D.dtype == np.float64
+    idx = np.sort(np.random.Generator(np.random.MT19937(Pr.size)).choice(Pr.size, bench.DUMP_SAMPLE, replace=False))
+    assert np.array_equal(got_P, Pr.ravel(order="F")[idx])
+    assert got_D.shape == D.shape and np.array_equal(got_D, D)

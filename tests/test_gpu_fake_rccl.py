@@ -299,7 +299,7 @@ def test_bench_gpus_n_over_the_rccl_arm(hip, gpus):
     build_fake()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NS3D_RCCL_LIB=FAKE_SO, FAKE_RCCL_ARENA_MB="16", NS3D_BENCH_RCCL_TIMEOUT="120")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--grid", "128", "--steps", "8", "--warmup", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--grid", "128", "--steps", "8", "--warmup", "4",
            "--transport", "rccl"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -8,7 +8,7 @@ set -u
 TAG=${1:-r3}
 cd $GRAFT_REPO_ROOT
 O=gpurun_out
-b() { name=$1; shift; python3 bench.py "$@" > $O/${TAG}_bench_$name.json 2> $O/${TAG}_bench_$name.err; echo "$name: $(python3 -c "import json,sys; d=json.loads(open('$O/${TAG}_bench_$name.json').read().strip().splitlines()[-1]); r=d['roofline']; print(round(d['value']), 'Mcells*it/s', 'depth', d['config']['pt_depth'], 'frac', round(r['frac'],3), 'eff', round(r['effective_frac'],3), 'kernel_ms', round(r['kernel_ms'],4))" 2>&1)"; }
+b() { name=$1; shift; python3 bench.py --full "$@" > $O/${TAG}_bench_$name.json 2> $O/${TAG}_bench_$name.err; echo "$name: $(python3 -c "import json,sys; d=json.loads(open('$O/${TAG}_bench_$name.json').read().strip().splitlines()[-1]); r=d['roofline']; print(round(d['value']), 'Mcells*it/s', 'depth', d['config']['pt_depth'], 'frac', round(r['frac'],3), 'eff', round(r['effective_frac'],3), 'kernel_ms', round(r['kernel_ms'],4))" 2>&1)"; }
 NS3D_BENCH_NO_TRAFFIC=0 NS3D_BENCH_NO_CONFIG_B=0 b strict                     # the headline line measures roofline.traffic live
 NS3D_BENCH_NO_TRAFFIC=0 b fast --mode fast --no-cpu-baseline
 NS3D_BENCH_NO_TRAFFIC=0 b f32_strict --dtype f32 --no-cpu-baseline
@@ -43,7 +43,7 @@ python3 tools/direct_rates.py --nx 63 > $O/${TAG}_direct_vs_pt.jsonl 2> $O/${TAG
 # what the z-slab schedule costs in compute (virtual ranks of one GPU against the global solve)
 for nzl in 66 130 258; do python3 tools/ab/slab_overhead.py --nz-local $nzl --ranks $((512/(nzl-2))) --iters 96 --temporal 4; done > $O/${TAG}_slab_overhead.log 2>&1; grep slabs $O/${TAG}_slab_overhead.log
 # the RCCL arm on one GPU (tests/fake_rccl): two ranks, weak + strong, self-verified
-NS3D_RCCL_LIB=$PWD/tests/fake_rccl/libfake_rccl.so FAKE_RCCL_ARENA_MB=64 python3 bench.py --gpus 2 --grid 256 --steps 40 --warmup 4 --transport rccl > $O/${TAG}_bench_2ranks_fake_rccl.json 2> $O/${TAG}_bench_2ranks_fake_rccl.err; cut -c1-400 $O/${TAG}_bench_2ranks_fake_rccl.json
+NS3D_RCCL_LIB=$PWD/tests/fake_rccl/libfake_rccl.so FAKE_RCCL_ARENA_MB=64 python3 bench.py --full --gpus 2 --grid 256 --steps 40 --warmup 4 --transport rccl > $O/${TAG}_bench_2ranks_fake_rccl.json 2> $O/${TAG}_bench_2ranks_fake_rccl.err; cut -c1-400 $O/${TAG}_bench_2ranks_fake_rccl.json
 # SQ counters of the two windowed once-per-step kernels (two --pmc passes each over tools/kernel_rates.py)
 { bash tools/ab/kernel_sq.sh k_advect_win2; bash tools/ab/kernel_sq.sh k_predict_fused; } > $O/${TAG}_window_kernels_sq.log 2>&1; cat $O/${TAG}_window_kernels_sq.log
 # a further time step of the two reference cases (wall, >= 40 steps: 5-step differences scatter), and the kernels of the direct-solve step
