@@ -413,7 +413,18 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out);
     int ns3d_pt_solve_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,         \
                                const ns3d_pt_params *p, double eps, int niter, int nchk, double err_mul,    \
                                double err_div, int *iters_done, double *err_hist, int max_checks,           \
-                               int *n_checks);
+                               int *n_checks);                                                      \
+    /* The direct pressure solve (ns3d_poisson_direct) of the GLOBAL grid on z-slab ranks (dims = (1,1,P)): the interior of the \
+     * nx × ny × nz_g grid becomes the solution of ∇²_h Pr = ρ/dt·∇V with set_bc_Pr!'s rule (NS3D_BC_MULTI; all-Neumann: the     \
+     * zero-mean solution), every local plane — seam halo planes and boundary cells included — what the single-rank solve of \
+     * the global grid leaves there (to rounding; P = 1: bit for bit), dPrdtau = 0, divV untouched: multi.jl:175-182 on the   \
+     * solution.  p describes the local grid of every rank, p->owns_outlet / p->outlet_val the global x-hi rule, the z halo   \
+     * flags of p are ignored.  x and y are transformed on each rank's planes, z on a y chunk of every plane between two      \
+     * all-to-all transposes; eigenbases and scratch stay with the ranks while the grid, P, the spacings and \
+     * the x rule stay the same.  fp32 fields are solved in fp64.  NS3D_ERR_ARG: NS3D_BC_GPU, x/y-decomposed topologies, null \
+     * pointers, local grids below 4×4×3. */                                                                \
+    int ns3d_poisson_direct_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,   \
+                                     const ns3d_pt_params *p);
 NS3D_MGPU_DECL(double, f64)
 NS3D_MGPU_DECL(float, f32)
 #undef NS3D_MGPU_DECL

@@ -326,6 +326,25 @@ void eig1d(int m, double d, int kind, std::vector<double> &V, std::vector<double
 
 struct Eig1d { int m, kind; double d; std::vector<double> V, lam; };
 
+// the eigenbases depend on (extent, spacing, boundary kind) only: computed once per process (contexts come and go, one per driver
+// call; z-slab ranks ask for the same global z basis), uploaded per context / rank
+void eig1d_cached(int m, double d, int kind, std::vector<double> &V, std::vector<double> &lam)
+{
+    static std::vector<Eig1d> cache;
+    static std::mutex mtx;
+    std::lock_guard<std::mutex> lock(mtx);
+    const Eig1d *hit = nullptr;
+    for (const Eig1d &e : cache)
+        if (e.m == m && e.d == d && e.kind == kind) hit = &e;
+    if (!hit) {
+        if (cache.size() >= 32) cache.clear();
+        cache.push_back({m, kind, d, {}, {}});
+        eig1d(m, d, kind, cache.back().V, cache.back().lam);
+        hit = &cache.back();
+    }
+    V = hit->V; lam = hit->lam;
+}
+
 struct DirectPlan {
     int nx = 0, ny = 0, nz = 0, xkind = -1;
     double dx = 0, dy = 0, dz = 0;
@@ -360,33 +379,27 @@ int ensure_plan(ns3d_ctx *c, const ns3d_pt_params *p, int xkind, DirectPlan **ou
     const double d[3] = {p->dx, p->dy, p->dz};
     const int kind[3] = {xkind, 0, 0};
     for (int q = 0; q < 3; ++q) {
-        // the eigenbases depend on (extent, spacing, boundary kind) only: computed once per process (contexts come and go, one
-        // per driver call), uploaded per context
-        static std::vector<Eig1d> cache;
-        static std::mutex mtx;
-        std::vector<double> V, lam;
-        {
-            std::lock_guard<std::mutex> lock(mtx);
-            const Eig1d *hit = nullptr;
-            for (const Eig1d &e : cache)
-                if (e.m == m[q] && e.d == d[q] && e.kind == kind[q]) hit = &e;
-            if (!hit) {
-                if (cache.size() >= 32) cache.clear();
-                cache.push_back({m[q], kind[q], d[q], {}, {}});
-                eig1d(m[q], d[q], kind[q], cache.back().V, cache.back().lam);
-                hit = &cache.back();
-            }
-            V = hit->V; lam = hit->lam;
-        }
-        HIPCHK(c, hipMalloc((void **)&pl->V[q], V.size() * sizeof(double)));
-        HIPCHK(c, hipMalloc((void **)&pl->lam[q], lam.size() * sizeof(double)));
-        HIPCHK(c, hipMemcpy(pl->V[q], V.data(), V.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(pl->lam[q], lam.data(), lam.size() * sizeof(double), hipMemcpyHostToDevice));
+        int rc = ns3d_direct_basis(m[q], d[q], kind[q], &pl->V[q], &pl->lam[q]);
+        if (rc) return rc;
     }
     const size_t cells = (size_t)m[0] * m[1] * m[2];
     for (int q = 0; q < 2; ++q) HIPCHK(c, hipMalloc((void **)&pl->W[q], cells * sizeof(double)));
     pl->nx = p->nx; pl->ny = p->ny; pl->nz = p->nz; pl->xkind = xkind; pl->dx = p->dx; pl->dy = p->dy; pl->dz = p->dz;
     return NS3D_OK;
+}
+
+// chunk-major [c][k][i + mx·(ky − ky0_c)] (the y modes in ns3d_direct_ychunk's P chunks, a chunk's planes contiguous) → plane-major
+// [k][i + mx·ky].  One pass, rows of mx contiguous on both sides.
+__global__ __launch_bounds__(256) void k_direct_unpack(const double *__restrict__ src, double *__restrict__ dst, int mx, int my, int mz, int P)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, ky = blockIdx.y * blockDim.y + threadIdx.y, k = blockIdx.z;
+    if (i >= mx || ky >= my) return;
+    const int base = my / P, rem = my % P;
+    const int c = ky < rem * (base + 1) ? ky / (base + 1) : rem + (ky - rem * (base + 1)) / base;
+    int ky0, nky;
+    ns3d_direct_ychunk(my, P, c, &ky0, &nky);
+    const long at = (long)mx * mz * ky0 + (long)mx * nky * k + i + (long)mx * (ky - ky0);
+    dst[(long)i + (long)mx * ((long)ky + (long)my * k)] = src[at];
 }
 
 template <class T>
@@ -397,45 +410,97 @@ int poisson_direct(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_params
     if (p->z_lo_is_halo || p->z_hi_is_halo)
         return fail(NS3D_ERR_ARG, "ns3d_poisson_direct: single-rank grids only (a z-slab rank's planes are not a closed problem)");
     if (p->nx < 4 || p->ny < 4 || p->nz < 4) return fail(NS3D_ERR_ARG, "ns3d_poisson_direct: grid %dx%dx%d too small", p->nx, p->ny, p->nz);
-    const int xkind = p->bc_kind == NS3D_BC_GPU ? 2 : (p->owns_outlet ? 1 : 0);
+    const int xkind = ns3d_direct_xkind(p);
     DirectPlan *pl = nullptr;
     if ((rc = ensure_plan(c, p, xkind, &pl))) return rc;
     hipStream_t s = c->stream;
-    const int nx = p->nx, ny = p->ny, nz = p->nz, mx = nx - 2, my = ny - 2, mz = nz - 2;
-    const long mxy = (long)mx * my;
-    const dim3 blk(64, 4, 1), grd((unsigned)((mx + 63) / 64), (unsigned)((my + 3) / 4), (unsigned)mz);
+    const int mx = p->nx - 2, my = p->ny - 2, mz = p->nz - 2;
     double *W0 = pl->W[0], *W1 = pl->W[1];
-    hipLaunchKernelGGL(k_direct_rhs<T>, grd, blk, 0, s, W0, divV, p->rho / p->dt, nx, ny, nz, p->bc_kind, p->owns_outlet, p->outlet_val,
+    hipError_t e = ns3d_direct_rhs_x<T>(s, divV, p, pl->V[0], W0, W1);
+    if (e == hipSuccess) e = ns3d_direct_fwd_y(s, W1, pl->V[1], W0, mx, my, mz, 0, my);
+    if (e == hipSuccess) e = ns3d_direct_z(s, W0, W1, pl->V[2], pl->lam[0], pl->lam[1], pl->lam[2], mx, my, mz);
+    if (e == hipSuccess) e = ns3d_direct_inv_yx<T>(s, W0, W1, pl->V[0], pl->V[1], Pr, D, p->nx, p->ny, p->nz);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "ns3d_poisson_direct launch: %s", hipGetErrorString(e)); }
+    return NS3D_OK;
+}
+
+} // namespace
+
+// ---- the stages (ns3d_internal.h): ns3d_poisson_direct above runs them on one rank's planes, ns3d_poisson_direct_slab
+// (ns3d_mgpu.cpp) with the z transform on a y chunk of every rank's planes between two all-to-all transposes ----------------
+int ns3d_direct_basis(int m, double d, int kind, double **V, double **lam)
+{
+    std::vector<double> hV, hl;
+    eig1d_cached(m, d, kind, hV, hl);
+    HIPCHK(0, hipMalloc((void **)V, hV.size() * sizeof(double)));
+    HIPCHK(0, hipMalloc((void **)lam, hl.size() * sizeof(double)));
+    HIPCHK(0, hipMemcpy(*V, hV.data(), hV.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(0, hipMemcpy(*lam, hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
+    return NS3D_OK;
+}
+
+template <class T>
+hipError_t ns3d_direct_rhs_x(hipStream_t s, const T *divV, const ns3d_pt_params *p, const double *Vx, double *F, double *U)
+{
+    const int nx = p->nx, ny = p->ny, nz = p->nz, mx = nx - 2, my = ny - 2, mz = nz - 2;
+    const dim3 blk(64, 4, 1), grd((unsigned)((mx + 63) / 64), (unsigned)((my + 3) / 4), (unsigned)mz);
+    hipLaunchKernelGGL(k_direct_rhs<T>, grd, blk, 0, s, F, divV, p->rho / p->dt, nx, ny, nz, p->bc_kind, p->owns_outlet, p->outlet_val,
                        p->rho * p->g, p->dz, 1.0 / (p->dx * p->dx));
     hipError_t e = hipGetLastError();
-    // forward: x (Vxᵀ·U), y (U_k·Vy per plane), z (U·Vz)
-    if (e == hipSuccess) e = gemm(s, pl->V[0], W0, W1, mx, my * mz, mx, /*A(a,i)=Vx[i+a·mx]*/ mx, 1, /*B*/ 1, mx, /*C*/ 1, mx);
-    if (e == hipSuccess) e = gemm(s, W1, pl->V[1], W0, mx, my, my, 1, mx, 1, my, 1, mx, mz, mxy, 0, mxy);
-    // … the division by the eigenvalue sums rides on the store of the z product, the scatter into Pr on the store of the last one
-    // (NS3D_DIRECT_FUSED=0, or extents the LDS-staged kernel does not take: the pointwise kernels as before — same values)
+    // forward x (Vxᵀ·U)
+    if (e == hipSuccess) e = gemm(s, Vx, F, U, mx, my * mz, mx, /*A(a,i)=Vx[i+a·mx]*/ mx, 1, /*B*/ 1, mx, /*C*/ 1, mx);
+    return e;
+}
+template hipError_t ns3d_direct_rhs_x<double>(hipStream_t, const double *, const ns3d_pt_params *, const double *, double *, double *);
+template hipError_t ns3d_direct_rhs_x<float>(hipStream_t, const float *, const ns3d_pt_params *, const double *, double *, double *);
+
+hipError_t ns3d_direct_fwd_y(hipStream_t s, const double *U, const double *Vy, double *out, int mx, int my, int mz, int ky0, int nky)
+{
+    // U_k·Vy per plane, columns ky0 … ky0+nky−1 of Vy only
+    const long mxy = (long)mx * my;
+    return gemm(s, U, Vy + (long)ky0 * my, out, mx, nky, my, 1, mx, 1, my, 1, mx, mz, mxy, 0, (long)mx * nky);
+}
+
+hipError_t ns3d_direct_z(hipStream_t s, double *U, double *tmp, const double *Vz, const double *lx, const double *ly, const double *lz,
+                         int mx, int nky, int mz)
+{
+    const long m = (long)mx * nky;
+    // forward z (U·Vz) — the division by the eigenvalue sums rides on its store (NS3D_DIRECT_FUSED=0, or extents the LDS-staged
+    // kernel does not take: the pointwise kernel as before — same values) — then backward z (Û·Vzᵀ)
     static const bool fused = !(std::getenv("NS3D_DIRECT_FUSED") && *std::getenv("NS3D_DIRECT_FUSED") == '0');
     GemmArgs ep{};
-    ep.epi = 1; ep.l0 = pl->lam[0]; ep.l1 = pl->lam[1]; ep.l2 = pl->lam[2]; ep.e_mx = mx; ep.e_my = my;
+    ep.epi = 1; ep.l0 = lx; ep.l1 = ly; ep.l2 = lz; ep.e_mx = mx; ep.e_my = nky;
+    hipError_t e = hipSuccess;
     bool scaled = false;
-    if (e == hipSuccess && fused) {
-        e = gemm(s, W0, pl->V[2], W1, (int)mxy, mz, mz, 1, mxy, 1, mz, 1, mxy, 1, 0, 0, 0, &ep);
+    if (fused) {
+        e = gemm(s, U, Vz, tmp, (int)m, mz, mz, 1, m, 1, mz, 1, m, 1, 0, 0, 0, &ep);
         if (e == hipErrorInvalidValue) { (void)hipGetLastError(); e = hipSuccess; } else scaled = true;
     }
     if (e == hipSuccess && !scaled) {
-        e = gemm(s, W0, pl->V[2], W1, (int)mxy, mz, mz, 1, mxy, 1, mz, 1, mxy);
+        e = gemm(s, U, Vz, tmp, (int)m, mz, mz, 1, m, 1, mz, 1, m);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_direct_scale, grd, blk, 0, s, W1, pl->lam[0], pl->lam[1], pl->lam[2], mx, my, mz);
+            const dim3 blk(64, 4, 1), grd((unsigned)((mx + 63) / 64), (unsigned)((nky + 3) / 4), (unsigned)mz);
+            hipLaunchKernelGGL(k_direct_scale, grd, blk, 0, s, tmp, lx, ly, lz, mx, nky, mz);
             e = hipGetLastError();
         }
     }
-    // backward: z (Û·Vzᵀ), y (Û_k·Vyᵀ), x (Vx·Û)
-    if (e == hipSuccess) e = gemm(s, W1, pl->V[2], W0, (int)mxy, mz, mz, 1, mxy, /*B(c,k)=Vz[k+c·mz]*/ mz, 1, 1, mxy);
-    if (e == hipSuccess) e = gemm(s, W0, pl->V[1], W1, mx, my, my, 1, mx, my, 1, 1, mx, mz, mxy, 0, mxy);
+    if (e == hipSuccess) e = gemm(s, tmp, Vz, U, (int)m, mz, mz, 1, m, /*B(c,k)=Vz[k+c·mz]*/ mz, 1, 1, m);
+    return e;
+}
+
+template <class T>
+hipError_t ns3d_direct_inv_yx(hipStream_t s, double *U, double *tmp, const double *Vx, const double *Vy, T *Pr, T *D, int nx, int ny, int nz)
+{
+    const int mx = nx - 2, my = ny - 2, mz = nz - 2;
+    const long mxy = (long)mx * my;
+    // backward y (Û_k·Vyᵀ), x (Vx·Û) — the scatter into Pr on the store of the last one
+    static const bool fused = !(std::getenv("NS3D_DIRECT_FUSED") && *std::getenv("NS3D_DIRECT_FUSED") == '0');
+    hipError_t e = gemm(s, U, Vy, tmp, mx, my, my, 1, mx, my, 1, 1, mx, mz, mxy, 0, mxy);
     bool scattered = false;
     if (e == hipSuccess && fused) {
         GemmArgs es{};
         es.epi = sizeof(T) == 8 ? 2 : 3; es.out = (void *)Pr; es.e_mx = mx; es.e_my = my; es.e_nx = nx; es.e_ny = ny;
-        e = gemm(s, pl->V[0], W1, W0, mx, my * mz, mx, 1, mx, 1, mx, 1, mx, 1, 0, 0, 0, &es);
+        e = gemm(s, Vx, tmp, U, mx, my * mz, mx, 1, mx, 1, mx, 1, mx, 1, 0, 0, 0, &es);
         if (e == hipErrorInvalidValue) { (void)hipGetLastError(); e = hipSuccess; }
         else {
             scattered = true;
@@ -443,17 +508,24 @@ int poisson_direct(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_params
         }
     }
     if (e == hipSuccess && !scattered) {
-        e = gemm(s, pl->V[0], W1, W0, mx, my * mz, mx, 1, mx, 1, mx, 1, mx);
+        e = gemm(s, Vx, tmp, U, mx, my * mz, mx, 1, mx, 1, mx, 1, mx);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_direct_scatter<T>, grd, blk, 0, s, Pr, D, W0, nx, ny, nz);
+            const dim3 blk(64, 4, 1), grd((unsigned)((mx + 63) / 64), (unsigned)((my + 3) / 4), (unsigned)mz);
+            hipLaunchKernelGGL(k_direct_scatter<T>, grd, blk, 0, s, Pr, D, U, nx, ny, nz);
             e = hipGetLastError();
         }
     }
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "ns3d_poisson_direct launch: %s", hipGetErrorString(e)); }
-    return NS3D_OK;
+    return e;
 }
+template hipError_t ns3d_direct_inv_yx<double>(hipStream_t, double *, double *, const double *, const double *, double *, double *, int, int, int);
+template hipError_t ns3d_direct_inv_yx<float>(hipStream_t, double *, double *, const double *, const double *, float *, float *, int, int, int);
 
-} // namespace
+hipError_t ns3d_direct_unpack(hipStream_t s, const double *src, double *dst, int mx, int my, int mz, int P)
+{
+    const dim3 blk(64, 4, 1), grd((unsigned)((mx + 63) / 64), (unsigned)((my + 3) / 4), (unsigned)mz);
+    hipLaunchKernelGGL(k_direct_unpack, grd, blk, 0, s, src, dst, mx, my, mz, P);
+    return hipGetLastError();
+}
 
 // set_bc_Pr! (host sequence of ns3d_api.cpp) on the context's stream
 extern "C" int ns3d_set_bc_Pr_f64(ns3d_ctx *, double *, int, int, double, double, int, double, double, int, int, int);

@@ -147,3 +147,33 @@ hipError_t ns3d_enqueue_face_copy(ns3d_ctx *c, hipStream_t s, T *A, T *buf, int 
 // up to NS3D_SUBBOX_MAX blocks between column-major arrays of different pitches in one launch (ns3d_launch.h: ns3d_subbox_batch)
 template <class T>
 hipError_t ns3d_enqueue_subbox_copy(ns3d_ctx *c, hipStream_t s, const ns3d_subbox_batch<T> &batch);
+
+// ---- ns3d_direct.hip: the stages of the direct Poisson solve, shared by ns3d_poisson_direct (one rank) and ns3d_poisson_direct_slab
+// (z-slab ranks, ns3d_mgpu.cpp).  Fields in fp64 scratch, plane-major [k][i + mx·j] over a rank's mz interior planes unless said
+// otherwise; every stage is enqueued on stream s and returns the launch status.
+// x boundary kind of the eigenbasis: 0 Neumann on both ends, 1 Neumann / outlet value (multi.jl:179-180), 2 gpu.jl's given values
+inline int ns3d_direct_xkind(const ns3d_pt_params *p) { return p->bc_kind == NS3D_BC_GPU ? 2 : (p->owns_outlet ? 1 : 0); }
+// y modes of chunk c when my modes are split into P contiguous chunks whose widths differ by at most one (empty when my < P)
+__host__ __device__ inline void ns3d_direct_ychunk(int my, int P, int c, int *ky0, int *nky)
+{
+    const int base = my / P, rem = my % P;
+    *nky = base + (c < rem ? 1 : 0);
+    *ky0 = c * base + (c < rem ? c : rem);
+}
+// eigenbasis (V: m×m, column q = mode q; lam: m eigenvalues) of the 1-D second difference on m cells, uploaded to the current device
+int ns3d_direct_basis(int m, double d, int kind, double **V, double **lam);
+// F ← the right-hand side of the rank's interior cells, U ← Vxᵀ·F
+template <class T>
+hipError_t ns3d_direct_rhs_x(hipStream_t s, const T *divV, const ns3d_pt_params *p, const double *Vx, double *F, double *U);
+// out[k][i + mx·(ky − ky0)] = Σ_j U[k][i + mx·j]·Vy(j, ky) for the y modes ky0 … ky0+nky−1
+hipError_t ns3d_direct_fwd_y(hipStream_t s, const double *U, const double *Vy, double *out, int mx, int my, int mz, int ky0, int nky);
+// mx·nky columns over mz planes ([k][i + mx·(ky − ky0)]): U ← Vz·((Vzᵀ·U) ⊘ (λx + λy + λz)), the null mode set to 0; ly points at the
+// λy of mode ky0; tmp: scratch of U's size
+hipError_t ns3d_direct_z(hipStream_t s, double *U, double *tmp, const double *Vz, const double *lx, const double *ly, const double *lz,
+                         int mx, int nky, int mz);
+// Pr's interior ← Vx·(U_k·Vyᵀ) of the rank's planes, dPrdτ ← 0 (U and tmp are overwritten; Pr's boundary cells are not touched)
+template <class T>
+hipError_t ns3d_direct_inv_yx(hipStream_t s, double *U, double *tmp, const double *Vx, const double *Vy, T *Pr, T *D, int nx, int ny,
+                              int nz);
+// chunk-major [c][k][i + mx·(ky − ky0_c)] (ns3d_direct_ychunk's P chunks, each over the mz planes) → plane-major dst
+hipError_t ns3d_direct_unpack(hipStream_t s, const double *src, double *dst, int mx, int my, int mz, int P);

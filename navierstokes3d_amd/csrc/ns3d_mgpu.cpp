@@ -104,6 +104,13 @@ struct SlabState {                // deep-ghost pseudo-transient state (library-
     int ip = 0, id = 0;           // current Pr / dPrdτ buffer
     int glo = 0, ghi = 0, nze = 0;
 };
+struct DirectSlab {               // ns3d_poisson_direct_slab: what a rank keeps while (grid, P, spacings, x rule) stay the same
+    int nx = 0, ny = 0, nz = 0, P = 0, xkind = -1;
+    double dx = 0, dy = 0, dz = 0;
+    double *V[3] = {nullptr, nullptr, nullptr}, *lam[3] = {nullptr, nullptr, nullptr};   // x, y (local extents) and z (all mz_g planes)
+    double *L[2] = {nullptr, nullptr};    // the rank's planes: mx·my·mz each (plane-major or chunk-major)
+    double *Z[2] = {nullptr, nullptr};    // the rank's y chunk over every global plane: mx·nky·mz_g each
+};
 struct MRank {
     int rank = 0, device = 0;
     int coords[3] = {0, 0, 0};                     // Cartesian coordinates (MPI_Cart_coords order: last dimension fastest)
@@ -125,6 +132,7 @@ struct MRank {
     size_t gbuf_bytes = 0;
     void *wbuf = nullptr;                          // advect_wide: the four old and four new fields, one plane wider per seam
     size_t wbuf_bytes = 0;
+    DirectSlab ds;                                 // ns3d_poisson_direct_slab: eigenbases and transposed scratch
 };
 struct Block {                    // one contiguous piece that travels to both neighbours (pointers on the owning rank)
     void *send_lo, *recv_lo, *send_hi, *recv_hi;
@@ -235,6 +243,55 @@ int exchange_end(ns3d_mgpu *m, int dim = 2)
     }
     return NS3D_OK;
 }
+// All-to-all of one piece per (sender, receiver) pair, including a rank's piece to itself: send[l][c] is what local rank l sends
+// to rank c, recv[l][c] where it receives rank c's piece (same byte count as the matching send; pairs of 0 bytes are skipped on
+// both sides).  Posted on the communication streams behind what the compute streams hold now; when it returns, the compute
+// streams are ordered after every landing — the received pieces are there and no send buffer is still being read.
+struct Piece { void *ptr; size_t bytes; };
+int alltoall(ns3d_mgpu *m, const std::vector<std::vector<Piece>> &send, const std::vector<std::vector<Piece>> &recv)
+{
+    const int n = (int)m->loc.size();
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        HIPCHK(0, hipEventRecord(r.ev_ready, compute(r)));
+    }
+    if (m->rccl) {
+        MRank &r = m->loc[0];
+        const int me = r.rank;
+        ns3d_device_guard g(r.device);
+        HIPCHK(0, hipStreamWaitEvent(r.comm, r.ev_ready, 0));
+        if (recv[0][me].bytes)
+            HIPCHK(0, hipMemcpyAsync(recv[0][me].ptr, send[0][me].ptr, recv[0][me].bytes, hipMemcpyDeviceToDevice, r.comm));
+        NCCLCHK(g_rccl.GroupStart());
+        for (int c = 0; c < m->P; ++c) {
+            if (c == me) continue;
+            if (send[0][c].bytes) NCCLCHK(g_rccl.Send(send[0][c].ptr, send[0][c].bytes, ncclUint8, c, m->comm, r.comm));
+            if (recv[0][c].bytes) NCCLCHK(g_rccl.Recv(recv[0][c].ptr, recv[0][c].bytes, ncclUint8, c, m->comm, r.comm));
+        }
+        NCCLCHK(g_rccl.GroupEnd());
+        HIPCHK(0, hipEventRecord(r.ev_landed, r.comm));
+        HIPCHK(0, hipStreamWaitEvent(compute(r), r.ev_landed, 0));
+        return NS3D_OK;
+    }
+    // one process (local index == rank): every receiver pulls once EVERY sender is ready …
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        for (int c = 0; c < n; ++c) HIPCHK(0, hipStreamWaitEvent(r.comm, m->loc[c].ev_ready, 0));
+        for (int c = 0; c < n; ++c)
+            if (recv[l][c].bytes)
+                HIPCHK(0, hipMemcpyPeerAsync(recv[l][c].ptr, r.device, send[c][l].ptr, m->loc[c].device, recv[l][c].bytes, r.comm));
+        HIPCHK(0, hipEventRecord(r.ev_landed, r.comm));
+    }
+    // … and every compute stream waits for all landings: its own pieces, and the pulls from its send buffers
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        for (int c = 0; c < n; ++c) HIPCHK(0, hipStreamWaitEvent(compute(r), m->loc[c].ev_landed, 0));
+    }
+    return NS3D_OK;
+}
 int sync_all(ns3d_mgpu *m)
 {
     for (MRank &r : m->loc) {
@@ -260,6 +317,19 @@ void free_slab(MRank &r)
     if (r.st.Ra) (void)hipFree(r.st.Ra);
     r.st.R = r.st.Ra = nullptr;
     r.st.bytes_P = r.st.bytes_D = 0;
+}
+
+void free_direct(MRank &r)
+{
+    ns3d_device_guard g(r.device);
+    DirectSlab &d = r.ds;
+    for (int q = 0; q < 3; ++q) { if (d.V[q]) (void)hipFree(d.V[q]); if (d.lam[q]) (void)hipFree(d.lam[q]); d.V[q] = d.lam[q] = nullptr; }
+    for (int q = 0; q < 2; ++q) {
+        if (d.L[q]) (void)hipFree(d.L[q]);
+        if (d.Z[q]) (void)hipFree(d.Z[q]);
+        d.L[q] = d.Z[q] = nullptr;
+    }
+    d.nx = d.ny = d.nz = d.P = 0; d.xkind = -1;
 }
 
 int init_rank(ns3d_mgpu *m, MRank &r, int rank, int device, int flags)
@@ -762,6 +832,129 @@ int update_halo_impl(ns3d_mgpu *m, T *const *fields, const int *extents, int nfi
 {
     const int rc = update_halo_core<T>(m, fields, extents, nfields);
     return rc ? rc : finish_m(m);
+}
+
+// ns3d_poisson_direct_slab: the direct solve of the GLOBAL grid on z-slab ranks.  x and y are transformed on each
+// rank's own planes; for z the y modes are split into P chunks and transposed all-to-all, so that rank c holds chunk c of every
+// plane of the global grid, transforms it against the global z basis (with the eigenvalue division) and back, and the pieces
+// return by a second all-to-all.  Every global z column is then transformed by ONE rank in the same operation order as in the
+// single-rank solve.
+int ensure_direct(ns3d_mgpu *m, MRank &r, const ns3d_pt_params *p, int xkind)
+{
+    DirectSlab &d = r.ds;
+    if (d.nx == p->nx && d.ny == p->ny && d.nz == p->nz && d.P == m->P && d.xkind == xkind && d.dx == p->dx && d.dy == p->dy &&
+        d.dz == p->dz)
+        return NS3D_OK;
+    int rc = sync_all(m);                 // a peer may still be pulling from the old buffers
+    if (rc) return rc;
+    free_direct(r);
+    ns3d_device_guard g(r.device);
+    const int mx = p->nx - 2, my = p->ny - 2, mz = p->nz - 2, mzg = m->P * mz;
+    int ky0, nky;
+    ns3d_direct_ychunk(my, m->P, 0, &ky0, &nky);      // chunk 0 is a widest one
+    const int m3[3] = {mx, my, mzg};
+    const double d3[3] = {p->dx, p->dy, p->dz};
+    const int k3[3] = {xkind, 0, 0};
+    for (int q = 0; q < 3; ++q)
+        if ((rc = ns3d_direct_basis(m3[q], d3[q], k3[q], &d.V[q], &d.lam[q]))) return rc;
+    for (int q = 0; q < 2; ++q) {
+        HIPCHK(0, hipMalloc((void **)&d.L[q], (size_t)mx * my * mz * sizeof(double)));
+        HIPCHK(0, hipMalloc((void **)&d.Z[q], (size_t)mx * nky * mzg * sizeof(double)));
+    }
+    d.nx = p->nx; d.ny = p->ny; d.nz = p->nz; d.P = m->P; d.xkind = xkind; d.dx = p->dx; d.dy = p->dy; d.dz = p->dz;
+    return NS3D_OK;
+}
+
+template <class T>
+int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, const ns3d_pt_params *p)
+{
+    const char *fn = "ns3d_poisson_direct_slab";
+    if (!z_slabs(m))
+        return fail(NS3D_ERR_ARG, "%s: z-slab topologies only (dims = (1,1,P)); this grid is (%d,%d,%d)", fn, m->dims[0], m->dims[1],
+                    m->dims[2]);
+    int rc = ns3d_check_pt_params(p, fn);
+    if (rc) return rc;
+    if (p->bc_kind != NS3D_BC_MULTI)
+        return fail(NS3D_ERR_ARG, "%s: gpu.jl's boundary set (NS3D_BC_GPU) is single-device: use ns3d_poisson_direct", fn);
+    if (p->nx != m->nx || p->ny != m->ny || p->nz != m->nz)
+        return fail(NS3D_ERR_ARG, "%s: params grid %dx%dx%d differs from the grid of ns3d_mgpu_create %dx%dx%d", fn, p->nx, p->ny, p->nz,
+                    m->nx, m->ny, m->nz);
+    if (p->nx < 4 || p->ny < 4 || p->nz < 3) return fail(NS3D_ERR_ARG, "%s: local grid %dx%dx%d too small (need >= 4x4x3)", fn, p->nx, p->ny, p->nz);
+    const int n = (int)m->loc.size();
+    for (int l = 0; l < n; ++l)
+        if (!Pr[l] || !D[l] || !divV[l]) return fail(NS3D_ERR_ARG, "%s: null field pointer (local rank %d)", fn, l);
+    const int P = m->P, mx = p->nx - 2, my = p->ny - 2, mz = p->nz - 2, mzg = P * mz;
+    const int xkind = ns3d_direct_xkind(p);
+    for (MRank &r : m->loc)
+        if ((rc = ensure_direct(m, r, p, xkind))) return rc;
+    std::vector<int> ky0(P), nky(P);
+    for (int c = 0; c < P; ++c) ns3d_direct_ychunk(my, P, c, &ky0[c], &nky[c]);
+    auto launch = [&](hipError_t e, const char *what) -> int {
+        if (e == hipSuccess) return NS3D_OK;
+        (void)hipGetLastError();
+        return fail(NS3D_ERR_HIP, "%s: %s launch: %s", fn, what, hipGetErrorString(e));
+    };
+    // (1) right-hand side, x and y on the rank's planes; y per chunk, chunk-major: the piece for rank c is one block
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        DirectSlab &d = r.ds;
+        hipStream_t s = compute(r);
+        if ((rc = launch(ns3d_direct_rhs_x<T>(s, divV[l], p, d.V[0], d.L[0], d.L[1]), "rhs / x"))) return rc;
+        for (int c = 0; c < P; ++c)
+            if (nky[c] && (rc = launch(ns3d_direct_fwd_y(s, d.L[1], d.V[1], d.L[0] + (size_t)mx * mz * ky0[c], mx, my, mz, ky0[c], nky[c]), "y")))
+                return rc;
+    }
+    // (2) transpose: rank c receives chunk c of every rank's planes, in rank order = [global plane][column]
+    std::vector<std::vector<Piece>> snd(n, std::vector<Piece>(P)), rcv(n, std::vector<Piece>(P));
+    for (int l = 0; l < n; ++l) {
+        DirectSlab &d = m->loc[l].ds;
+        const int me = m->loc[l].rank;
+        for (int c = 0; c < P; ++c) {
+            snd[l][c] = {d.L[0] + (size_t)mx * mz * ky0[c], (size_t)mx * mz * nky[c] * sizeof(double)};
+            rcv[l][c] = {d.Z[0] + (size_t)c * mz * mx * nky[me], (size_t)mx * mz * nky[me] * sizeof(double)};
+        }
+    }
+    if ((rc = alltoall(m, snd, rcv))) return rc;
+    // (3) z forward, eigenvalue division, z backward on the rank's chunk
+    for (MRank &r : m->loc) {
+        ns3d_device_guard g(r.device);
+        DirectSlab &d = r.ds;
+        const int me = r.rank;
+        if (nky[me] && (rc = launch(ns3d_direct_z(compute(r), d.Z[0], d.Z[1], d.V[2], d.lam[0], d.lam[1] + ky0[me], d.lam[2], mx, nky[me], mzg), "z")))
+            return rc;
+    }
+    // (4) back: rank r gets its planes of every chunk, chunk-major again
+    for (int l = 0; l < n; ++l) {
+        DirectSlab &d = m->loc[l].ds;
+        const int me = m->loc[l].rank;
+        for (int c = 0; c < P; ++c) {
+            snd[l][c] = {d.Z[0] + (size_t)c * mz * mx * nky[me], (size_t)mx * mz * nky[me] * sizeof(double)};
+            rcv[l][c] = {d.L[1] + (size_t)mx * mz * ky0[c], (size_t)mx * mz * nky[c] * sizeof(double)};
+        }
+    }
+    if ((rc = alltoall(m, snd, rcv))) return rc;
+    // … unpacked to plane-major, y and x backward with the scatter into Pr, then set_bc_Pr! per rank (multi.jl:176-181)
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        DirectSlab &d = r.ds;
+        hipStream_t s = compute(r);
+        if ((rc = launch(ns3d_direct_unpack(s, d.L[1], d.L[0], mx, my, mz, P), "unpack"))) return rc;
+        if ((rc = launch(ns3d_direct_inv_yx<T>(s, d.L[0], d.L[1], d.V[0], d.V[1], Pr[l], D[l], p->nx, p->ny, p->nz), "y / x backward")))
+            return rc;
+        const int flags = r.ctx->flags;
+        r.ctx->flags |= NS3D_ASYNC;       // enqueue only: the call as a whole blocks (or not) at its end
+        if constexpr (sizeof(T) == 8)
+            rc = ns3d_set_bc_Pr_f64(r.ctx, Pr[l], NS3D_BC_MULTI, p->owns_outlet, p->outlet_val, p->dz, p->nz, p->g, p->rho, p->nx, p->ny, p->nz);
+        else
+            rc = ns3d_set_bc_Pr_f32(r.ctx, Pr[l], NS3D_BC_MULTI, p->owns_outlet, p->outlet_val, p->dz, p->nz, p->g, p->rho, p->nx, p->ny, p->nz);
+        r.ctx->flags = flags;
+        if (rc) return rc;
+    }
+    // (5) update_halo!(Pr) (multi.jl:182): the seam planes from the neighbours
+    const int ext[3] = {p->nx, p->ny, p->nz};
+    return update_halo_core<T>(m, Pr, ext, 1);
 }
 
 // The inner loop multi.jl:458-471 on a topology that is decomposed in x or y: per iteration ONE fused sweep per rank
@@ -1582,6 +1775,7 @@ void ns3d_mgpu_destroy(ns3d_mgpu *m)
         if (!r.ctx) continue;              // a rank that never came up (failed create) owns nothing
         ns3d_device_guard g(r.device);
         free_slab(r);
+        free_direct(r);
         if (r.gbuf) (void)hipFree(r.gbuf);
         if (r.hbuf) (void)hipFree(r.hbuf);
         if (r.cbuf) (void)hipFree(r.cbuf);
@@ -1780,6 +1974,14 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
                                                     err_div, iters_done, err_hist, max_checks, n_checks)     \
                             : solve_cart<T>(m, Pr, dPrdtau, divV, p, eps, niter, nchk, err_mul, err_div,     \
                                             iters_done, err_hist, max_checks, n_checks);                     \
+        return rc ? rc : finish_m(m);                                                                        \
+    }                                                                                                        \
+    extern "C" int ns3d_poisson_direct_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,      \
+                                                 const ns3d_pt_params *p)                                     \
+    {                                                                                                        \
+        CHECK_M(m);                                                                                          \
+        if (!Pr || !dPrdtau || !divV) return fail(NS3D_ERR_ARG, "ns3d_poisson_direct_slab: null field list"); \
+        int rc = direct_slab<T>(m, Pr, dPrdtau, divV, p);                                                    \
         return rc ? rc : finish_m(m);                                                                        \
     }
 

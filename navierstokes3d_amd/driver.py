@@ -144,9 +144,10 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     fused=False (ImplicitGlobalGrid's own default is MultiGpu.dims_create(P), e.g. (2,2,2) for 8 ranks).
     `shape` (dict: ny, nz, ly_lx, lz_lx) overrides the literals multi.jl:302-303,323-324 for grids the reference cannot
     produce without editing them (BASELINE configs[3]: 512×512×1024 global).
-    pressure="direct" (OUTSIDE PARITY; one rank): the inner loop :458-471 is replaced by ns3d_poisson_direct, the
-    exact solution of the discrete problem that loop stops short of by εit; info.iters is 0 per step and info.errs holds the
-    residual of the solution in the reference's own measure (:466).
+    pressure="direct" (OUTSIDE PARITY): the inner loop :458-471 is replaced by ns3d_poisson_direct, the exact
+    solution of the discrete problem that loop stops short of by εit — on z-slab ranks of a MgpuGrid by
+    ns3d_poisson_direct_slab, the solve of the global grid; info.iters is 0 per step and info.errs holds the (global) residual of
+    the solution in the reference's own measure (:466).
     wide_advect_halo=True (OUTSIDE the reference's multi-rank semantics; z-slabs on the C-ABI grid): :475-477 run as
     ns3d_advect_wide — old fields with a two-plane z halo, C's halo updated too — so that the P-rank run reproduces the one-rank
     run of the same global grid bit for bit (the reference's backtrack! clamps to the local array)."""
@@ -288,9 +289,14 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         if root and do_print:
             print("#it = %d" % it)                                                            # :456
         show = (lambda i, e: print("  #iter = %d, err = %1.3e" % (i, e))) if (root and do_print) else None
-        if pressure == "direct":
-            if P != 1:
-                raise L.Ns3dError("pressure=\"direct\" solves a single rank's closed problem (P = %d ranks here)" % P)
+        if pressure == "direct" and P > 1:
+            if mg is None or not (dims[0] == 1 and dims[1] == 1):
+                raise L.Ns3dError("pressure=\"direct\" on %d ranks needs z-slab ranks on the C-ABI grid (mgpu.MgpuGrid); this grid "
+                                  "is %s with dims = %r" % (P, type(grid).__name__, dims))
+            mg.poisson_direct(col("Pr"), col("dPrdtau"), col("divV"), pt_all)      # ns3d_poisson_direct_slab
+            loc = [K.residual_max(f.Pr, f.divV, q, ctx=c) for f, q, c in zip(fs, pts, ctxs)]
+            done, errs = 0, [grid.max_g(loc if len(loc) > 1 else loc[0]) * (p.ly * p.ly) / p.psc]
+        elif pressure == "direct":
             K.poisson_direct(fs[0].Pr, fs[0].dPrdtau, fs[0].divV, pts[0], ctx=ctxs[0])
             done, errs = 0, [K.residual_max(fs[0].Pr, fs[0].divV, pts[0], ctx=ctxs[0]) * (p.ly * p.ly) / p.psc]
         elif not fused:                                                                       # :458-471

@@ -266,6 +266,15 @@ class MultiGpu:
                                                   C.c_double(err_div), C.byref(it), hist, cap, C.byref(nchecks)))
         return it.value, list(hist[: nchecks.value])
 
+    def poisson_direct(self, Pr, dPrdtau, divV, p):
+        """ns3d_poisson_direct_slab: the direct pressure solve of the GLOBAL grid on z-slab ranks (per-rank lists; p describes the
+        local grid of every rank, its z halo flags are ignored).  Every rank's planes end up as the single-rank
+        ns3d_poisson_direct of the global grid leaves them (halo planes and boundary cells included); dPrdtau becomes 0."""
+        self._follow_torch_streams()
+        ref = _as_list(Pr)[0]
+        L.check(self._typed("poisson_direct_slab", ref)(self.handle, self._ptrs([Pr]), self._ptrs([dPrdtau]), self._ptrs([divV]),
+                                                        C.byref(p)))
+
 
 class MgpuGrid:
     """The driver-facing grid object (same surface as halo.ZSlabGrid) on top of a MultiGpu."""
