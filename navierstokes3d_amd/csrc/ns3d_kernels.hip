@@ -1451,7 +1451,7 @@ hipError_t face_copy(hipStream_t s, T *A, T *buf, int sx, int sy, int sz, int di
 
 // Up to NS3D_SUBBOX_MAX cx·cy·cz blocks, each between two column-major arrays of different pitches (row pitch dpx / spx elements,
 // plane pitch dpl / spl; dst and src point at a block's first element), in ONE launch.  The deep-ghost state of a Cartesian
-// topology (ns3d_mgpu.cpp, solve_box) moves through it: local arrays ↔ ghost-extended box, and the layers next to an x or y seam
+// topology (ns3d_mgpu.cpp, solve_deep) moves through it: local arrays ↔ ghost-extended box, and the layers next to an x or y seam
 // of every array and both sides ↔ packed message buffers.  A block's (i, j) plane is flattened over the threads, so that a block
 // four cells wide (x layers) still fills its waves.
 template <class T>
@@ -1530,7 +1530,7 @@ struct SweepArgs {
     int tx0, ty0; // origin of the launch's tile window in the plane's tile grid (0, 0: the whole grid)
     const ns3d_tile_window *win;  // host side only: the window asked for / the geometry query (ns3d_launch.h); nullptr: everything
     int cus_off;  // host side only: compute units the stream's CU mask leaves out (ns3d_reserve_cus) — the z-chunking counts the rest
-    int no_faces; // NS3D_PASS_SKIP_FACES: no k_pt_faces launch behind the sweep (a split pass completes the boundary cells itself: box_pass)
+    int no_faces; // NS3D_PASS_SKIP_FACES: no k_pt_faces launch behind the sweep (a split pass completes the boundary cells itself: box_pass_overlapped)
 };
 
 // value stored on the x planes for target plane kk (0-based)
@@ -2339,7 +2339,7 @@ static hipError_t launch_faces(hipStream_t s, const SweepArgs<T> &a)
 
 // The boundary cells k_pt_faces writes (y-face rows of the interior planes, whole z-face planes), restricted by where their SOURCE cell —
 // the interior cell they clamp onto — lies: inside the box [c0, c1) of cells (want_core) or outside it.  A pass that is split into
-// shells and a core (ns3d_mgpu.cpp box_pass) completes the boundary cells in two launches this way, each reading only cells its own
+// shells and a core (ns3d_mgpu.cpp box_pass_overlapped) completes the boundary cells in two launches this way, each reading only cells its own
 // sweeps have written, and the second one touching nothing an unpack has filled in the meantime.
 template <class T>
 __global__ __launch_bounds__(256) void k_pt_faces_region(SweepArgs<T> a, int cx0, int cy0, int cz0, int cx1, int cy1, int cz1, int want_core)

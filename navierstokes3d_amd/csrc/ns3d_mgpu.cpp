@@ -102,7 +102,6 @@ struct SlabState {                // deep-ghost pseudo-transient state (library-
     void *Pa[2] = {nullptr, nullptr}, *Da[2] = {nullptr, nullptr}, *Ra = nullptr;   // the allocations (ghost depth at load)
     size_t bytes_P = 0, bytes_D = 0;
     int ip = 0, id = 0;           // current Pr / dPrdτ buffer
-    int glo = 0, ghi = 0, nze = 0;
 };
 struct DirectSlab {               // ns3d_poisson_direct_slab: what a rank keeps while (grid, P, spacings, x rule) stay the same
     int nx = 0, ny = 0, nz = 0, P = 0, xkind = -1;
@@ -120,13 +119,13 @@ struct MRank {
     ns3d_ctx *ctx = nullptr;
     hipStream_t comm = nullptr;                    // halo traffic (high priority)
     hipEvent_t ev_ready = nullptr, ev_landed = nullptr;
-    hipEvent_t ev_pass = nullptr;                  // slab_pass: everything the compute stream held when the pass began
-    int plan_v2 = -1, plan_vn = -1;                // tile shapes ns3d_slab_plan / box_plan measured for this rank's interior sweeps
+    hipEvent_t ev_pass = nullptr;                  // deep_pass: everything the compute stream held when the pass began
+    int plan_v2 = -1, plan_vn = -1;                // tile shapes deep_plan measured for this rank's interior sweeps
     int plan_lo = 0, plan_hi = 0;                  // … and the plane range they were measured on (sub-ranges of it use them too)
     SlabState st;
     void *cbuf = nullptr;                          // solve_cart: the second pressure buffer
     size_t cbuf_bytes = 0;
-    void *bbuf = nullptr;                          // solve_box: packed x / y ghost layers (send lo, send hi, recv lo, recv hi per array)
+    void *bbuf = nullptr;                          // box_exchange: packed x / y ghost layers (send lo, send hi, recv lo, recv hi per array)
     size_t bbuf_bytes = 0;
     void *gbuf = nullptr;                          // gather!: packed halo-stripped block
     size_t gbuf_bytes = 0;
@@ -152,7 +151,7 @@ struct ns3d_mgpu {
     int depth = 4;                // most PT iterations a pass may advance = ghost depth + 1 (1: single sweeps, plain one-plane halo)
     bool serial_seams = false;    // A/B switch (NS3D_SLAB_SERIAL_SEAMS=1): the round-2 schedule, seam sweeps ahead of the interior on one stream
     int interior_chunks = 1;      // ns3d_mgpu_set_interior_chunks: launches the interior sweep of a z-slab pass is cut into
-    int pass_depth = 2;           // iterations per pass actually used (ns3d_slab_plan may raise it to `depth`; same on every rank)
+    int pass_depth = 2;           // iterations per pass actually used (deep_plan may raise it to `depth`; same on every rank)
     // loaded solve
     bool loaded = false;
     int esize = 0, G = 0;
@@ -176,7 +175,7 @@ int cart_rank(const int c[3], const int dims[3]) { return (c[0] * dims[1] + c[1]
 
 // Post the exchange of `blocks[l]` (same count and sizes on every rank): everything up to "the ghosts have landed" is
 // enqueued on the communication streams, ordered after what the compute streams hold NOW.
-// sends_on_comm: what is sent was produced ON the communication streams (slab_pass sweeps the seam planes there), so "ready"
+// sends_on_comm: what is sent was produced ON the communication streams (deep_pass sweeps the seam planes there), so "ready"
 // is a point of those streams instead of the compute streams
 int exchange_begin(ns3d_mgpu *m, const std::vector<std::vector<Block>> &blocks, int dim = 2, bool sends_on_comm = false)
 {
@@ -374,137 +373,7 @@ ns3d_mgpu *new_mgpu(const int *dims, int nx, int ny, int nz, int flags, const ch
     return m;
 }
 
-// ---- deep-ghost slab state --------------------------------------------------------------------------------------
-template <class T>
-struct Ext {                       // geometry of one rank's extended buffers
-    int nx, ny, nz, G, glo, ghi, nze, k0, k1;
-    size_t plane, dplane;
-    Ext(const ns3d_mgpu *m, const MRank &r)
-    {
-        nx = m->nx; ny = m->ny; nz = m->nz; G = m->G;
-        glo = has_lower(m, r) ? G : 0;
-        ghi = has_upper(m, r) ? G : 0;
-        nze = nz + glo + ghi;
-        k0 = 1 + glo; k1 = nz - 1 + glo;
-        plane = (size_t)nx * ny; dplane = (size_t)(nx - 2) * (ny - 2);
-    }
-};
-
-ns3d_pt_params ext_params(const ns3d_mgpu *m, const MRank &r)
-{
-    ns3d_pt_params pe = m->p;
-    const int glo = has_lower(m, r) ? m->G : 0, ghi = has_upper(m, r) ? m->G : 0;
-    pe.nz = m->nz + glo + ghi;
-    // G = 0: the halo planes are the buffers' outermost planes and must not be treated as faces; G > 0: the sweeps never
-    // produce the outermost planes of a seam side at all (output planes start at 1+G)
-    pe.z_lo_is_halo = (m->G == 0 && has_lower(m, r)) ? 1 : 0;
-    pe.z_hi_is_halo = (m->G == 0 && has_upper(m, r)) ? 1 : 0;
-    return pe;
-}
-
-template <class T>
-std::vector<Block> ghost_blocks(const ns3d_mgpu *m, const MRank &r, int ip, int idd)
-{
-    const Ext<T> e(m, r);
-    const int G = m->G;
-    T *Pq = (T *)r.st.P[ip], *Dq = (T *)r.st.D[idd];
-    std::vector<Block> v;
-    // Pr: the depth outermost own planes → the neighbour's ghost + halo planes
-    const int np = G + 1;
-    v.push_back({Pq + e.plane * e.k0, Pq, Pq + e.plane * (e.k1 - np), Pq + e.plane * (e.nze - np), e.plane * np * sizeof(T)});
-    // dPrdτ (plane k ↔ index k−1): the G outermost own planes → the neighbour's ghost planes
-    if (G > 0)
-        v.push_back({Dq + e.dplane * (e.k0 - 1), Dq, Dq + e.dplane * (e.k1 - 1 - G), Dq + e.dplane * (e.nze - 2 - G),
-                     e.dplane * G * sizeof(T)});
-    return v;
-}
-
-template <class T>
-int slab_exchange(ns3d_mgpu *m, int ip_of_all, int id_of_all, bool wait)
-{
-    std::vector<std::vector<Block>> blocks;
-    for (MRank &r : m->loc) blocks.push_back(ghost_blocks<T>(m, r, ip_of_all, id_of_all));
-    int rc = exchange_begin(m, blocks);
-    if (rc) return rc;
-    return wait ? exchange_end(m) : NS3D_OK;
-}
-
-// one pass: `its` (1 … depth) PT iterations on every local rank.  The seam-adjacent output planes are swept on the rank's
-// high-priority COMMUNICATION stream, their exchange follows them there in stream order, and the interior sweep runs on the
-// compute stream AT THE SAME TIME (the three sweeps read the same input buffers and write disjoint planes): no launch of a pass
-// waits for the tail of another one, and the exchange starts as soon as the thin seam sweeps are done.  (Until round 3 the seam
-// sweeps ran on the compute stream ahead of the interior: two more kernel boundaries per pass, 1.5× the global solve's time on
-// 66-plane slabs.)  Ordering: the communication stream first waits for everything the compute stream held when the pass began
-// (the previous pass's interior planes, and through its exchange_end the neighbours' pulls of the planes this pass overwrites).
-template <class T>
-int slab_pass(ns3d_mgpu *m, int its)
-{
-    const int ip = m->loc[0].st.ip, idd = m->loc[0].st.id;          // the ranks advance in lockstep
-    const int idd_out = its >= 2 ? idd ^ 1 : idd;
-    struct Rng { int lo_end, hi_beg; };
-    std::vector<Rng> rng(m->loc.size());
-    auto sweep = [&](MRank &r, hipStream_t st, int a, int b) -> int {
-        if (b <= a) return NS3D_OK;
-        const ns3d_pt_params pe = ext_params(m, r);
-        ns3d_device_guard g(r.device);
-        hipError_t e;
-        if (its >= 2) {
-            const bool planned = a >= r.plan_lo && b <= r.plan_hi;              // the interior (or a chunk of it): the rank's own plan
-            e = ns3d_enqueue_pass<T>(r.ctx, st, its, (const T *)r.st.P[ip], (T *)r.st.P[ip ^ 1], (const T *)r.st.D[idd],
-                                     (T *)r.st.D[idd_out], (const T *)r.st.R, &pe, a, b, planned ? r.plan_v2 : -1, planned ? r.plan_vn : -1);
-        }
-        else
-            e = ns3d_enqueue_pt1<T>(r.ctx, st, (const T *)r.st.P[ip], (T *)r.st.P[ip ^ 1], (T *)r.st.D[idd],
-                                    (const T *)r.st.R, &pe, a, b);
-        return e == hipSuccess ? NS3D_OK : fail(NS3D_ERR_HIP, "slab sweep launch: %s", hipGetErrorString(e));
-    };
-    int rc;
-    const bool split = m->P > 1 && !m->serial_seams;
-    for (size_t l = 0; l < m->loc.size(); ++l) {
-        MRank &r = m->loc[l];
-        const Ext<T> e(m, r);
-        const int np = m->G + 1;                                    // planes the neighbour needs
-        rng[l].lo_end = has_lower(m, r) ? std::min(e.k0 + np, e.k1) : e.k0;
-        rng[l].hi_beg = has_upper(m, r) ? std::max(e.k1 - np, rng[l].lo_end) : e.k1;
-        hipStream_t seam = compute(r);
-        if (split) {
-            ns3d_device_guard g(r.device);
-            HIPCHK(0, hipEventRecord(r.ev_pass, compute(r)));
-            HIPCHK(0, hipStreamWaitEvent(r.comm, r.ev_pass, 0));
-            seam = r.comm;
-        }
-        if ((rc = sweep(r, seam, e.k0, rng[l].lo_end))) return rc;
-        if ((rc = sweep(r, seam, rng[l].hi_beg, e.k1))) return rc;
-    }
-    std::vector<std::vector<Block>> blocks;
-    for (MRank &r : m->loc) blocks.push_back(ghost_blocks<T>(m, r, ip ^ 1, idd_out));
-    if ((rc = exchange_begin(m, blocks, 2, split))) return rc;
-    // the interior, in `interior_chunks` launches over consecutive plane ranges while an exchange is pending (ns3d.h: a kernel of the
-    // exchange finds CUs at the latest when a chunk ends; every chunk pays its own pipeline fill, so one launch unless asked)
-    for (size_t l = 0; l < m->loc.size(); ++l) {
-        const int a = rng[l].lo_end, b = rng[l].hi_beg;
-        const int nch = (m->P > 1 && b - a >= 8 * m->interior_chunks) ? m->interior_chunks : 1;
-        for (int q = 0; q < nch; ++q)
-            if ((rc = sweep(m->loc[l], compute(m->loc[l]), a + (int)((long)(b - a) * q / nch), a + (int)((long)(b - a) * (q + 1) / nch)))) return rc;
-    }
-    if ((rc = exchange_end(m))) return rc;
-    for (MRank &r : m->loc) { r.st.ip = ip ^ 1; r.st.id = idd_out; }
-    return NS3D_OK;
-}
-
-template <class T>
-int slab_iterate(ns3d_mgpu *m, int n)
-{
-    int rc;
-    for (int it = 0; it < n;) {
-        const int rem = n - it, d = std::min(m->pass_depth, m->G + 1);
-        int its = rem >= d ? ((rem == d + 1 && d >= 3) ? d - 1 : d) : rem;      // 4 = 2+2, not 3+1
-        if ((rc = slab_pass<T>(m, its))) return rc;
-        it += its;
-    }
-    return NS3D_OK;
-}
-
+// ---- residual checks --------------------------------------------------------------------------------------------
 // max_g of per-rank keys that sit in each rank's ctx->key_dev (device): host double out
 int reduce_keys(ns3d_mgpu *m, double *out)
 {
@@ -527,103 +396,6 @@ int reduce_keys(ns3d_mgpu *m, double *out)
     return NS3D_OK;
 }
 
-template <class T>
-int slab_residual(ns3d_mgpu *m, double *out)
-{
-    for (MRank &r : m->loc) {
-        const ns3d_pt_params pe = ext_params(m, r);
-        ns3d_device_guard g(r.device);
-        hipError_t e = ns3d_enqueue_residual_key<T>(r.ctx, compute(r), (const T *)r.st.P[r.st.ip], (const T *)r.st.R, &pe,
-                                                    r.ctx->key_dev);
-        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));
-    }
-    return reduce_keys(m, out);
-}
-
-template <class T>
-int slab_load(ns3d_mgpu *m, const T *const *Pr, const T *const *D, const T *const *divV, const ns3d_pt_params *p)
-{
-    if (!z_slabs(m))
-        return fail(NS3D_ERR_STATE, "the fused pseudo-transient path takes z-slab topologies only (dims = (1,1,P)); this grid is "
-                    "(%d,%d,%d): run the loop multi.jl:458-471 with the kernel entry points and ns3d_update_halo", m->dims[0],
-                    m->dims[1], m->dims[2]);
-    int rc = ns3d_check_pt_params(p, "ns3d_slab_load");
-    if (rc) return rc;
-    if (p->nx != m->nx || p->ny != m->ny || p->nz != m->nz)
-        return fail(NS3D_ERR_ARG, "ns3d_slab_load: params grid %dx%dx%d differs from the grid of ns3d_mgpu_create %dx%dx%d", p->nx,
-                    p->ny, p->nz, m->nx, m->ny, m->nz);
-    if (p->bc_kind != NS3D_BC_MULTI && m->P > 1)
-        return fail(NS3D_ERR_ARG, "ns3d_slab_load: gpu.jl's boundary set is single-device");
-    if (m->nz < 4 && m->P > 1) return fail(NS3D_ERR_ARG, "ns3d_slab_load: z-slab ranks need at least two interior planes");
-    m->p = *p;
-    // a rank sends its G+1 outermost OWN planes: slabs thinner than that get fewer ghost planes (and shallower passes)
-    m->G = (m->P > 1 ? std::min(m->depth, m->nz - 2) : m->depth) - 1;
-    m->esize = (int)sizeof(T);
-    for (size_t l = 0; l < m->loc.size(); ++l) {
-        MRank &r = m->loc[l];
-        if (!Pr[l] || !D[l] || !divV[l]) return fail(NS3D_ERR_ARG, "ns3d_slab_load: null field pointer (local rank %zu)", l);
-        const Ext<T> e(m, r);
-        const size_t bp = e.plane * e.nze * sizeof(T), bd = e.dplane * (e.nze - 2) * sizeof(T);
-        ns3d_device_guard g(r.device);
-        hipStream_t s = compute(r);
-        if (r.st.bytes_P != bp || r.st.bytes_D != bd) {
-            HIPCHK(0, hipStreamSynchronize(s));
-            HIPCHK(0, hipStreamSynchronize(r.comm));
-            free_slab(r);
-            for (int q = 0; q < 2; ++q) {
-                HIPCHK(0, hipMalloc(&r.st.Pa[q], bp));
-                HIPCHK(0, hipMalloc(&r.st.Da[q], bd));
-                HIPCHK(0, hipMemsetAsync(r.st.Pa[q], 0, bp, s));
-                HIPCHK(0, hipMemsetAsync(r.st.Da[q], 0, bd, s));
-            }
-            HIPCHK(0, hipMalloc(&r.st.Ra, bp));
-            HIPCHK(0, hipMemsetAsync(r.st.Ra, 0, bp, s));
-            r.st.bytes_P = bp; r.st.bytes_D = bd;
-        }
-        for (int q = 0; q < 2; ++q) { r.st.P[q] = r.st.Pa[q]; r.st.D[q] = r.st.Da[q]; }
-        r.st.R = r.st.Ra;
-        r.st.glo = e.glo; r.st.ghi = e.ghi; r.st.nze = e.nze; r.st.ip = r.st.id = 0;
-        HIPCHK(0, hipMemcpyAsync((T *)r.st.P[0] + e.plane * e.glo, Pr[l], e.plane * e.nz * sizeof(T), hipMemcpyDeviceToDevice, s));
-        HIPCHK(0, hipMemcpyAsync((T *)r.st.D[0] + e.dplane * e.glo, D[l], e.dplane * (e.nz - 2) * sizeof(T), hipMemcpyDeviceToDevice, s));
-        HIPCHK(0, hipMemcpyAsync((T *)r.st.R + e.plane * e.glo, divV[l], e.plane * e.nz * sizeof(T), hipMemcpyDeviceToDevice, s));
-        if (m->G == 0) {    // single sweeps write Pr_out's interior planes only: seed the other buffer's outer planes
-            HIPCHK(0, hipMemcpyAsync(r.st.P[1], r.st.P[0], e.plane * sizeof(T), hipMemcpyDeviceToDevice, s));
-            HIPCHK(0, hipMemcpyAsync((T *)r.st.P[1] + e.plane * (e.nze - 1), (T *)r.st.P[0] + e.plane * (e.nze - 1),
-                                     e.plane * sizeof(T), hipMemcpyDeviceToDevice, s));
-        }
-    }
-    for (MRank &r : m->loc) { r.plan_v2 = r.plan_vn = -1; r.plan_lo = r.plan_hi = 0; }      // a new state: planned again by ns3d_slab_plan
-    m->loaded = true;
-    // deep ghosts of the incoming state — and of the right-hand side: level 1 on a ghost plane needs ∇V there, one or two
-    // planes beyond the one-plane halo the caller's update_halo!(∇V) filled (that plane is re-sent too: same value)
-    std::vector<std::vector<Block>> blocks;
-    for (MRank &r : m->loc) {
-        const Ext<T> e(m, r);
-        const int np = m->G + 1;
-        std::vector<Block> v = ghost_blocks<T>(m, r, 0, 0);
-        T *Rq = (T *)r.st.R;
-        v.push_back({Rq + e.plane * e.k0, Rq, Rq + e.plane * (e.k1 - np), Rq + e.plane * (e.nze - np), e.plane * np * sizeof(T)});
-        blocks.push_back(v);
-    }
-    int rc2 = exchange_begin(m, blocks);
-    return rc2 ? rc2 : exchange_end(m);
-}
-
-template <class T>
-int slab_store(ns3d_mgpu *m, T *const *Pr, T *const *D)
-{
-    for (size_t l = 0; l < m->loc.size(); ++l) {
-        MRank &r = m->loc[l];
-        if (!Pr[l] || !D[l]) return fail(NS3D_ERR_ARG, "ns3d_slab_store: null field pointer (local rank %zu)", l);
-        const Ext<T> e(m, r);
-        ns3d_device_guard g(r.device);
-        hipStream_t s = compute(r);
-        HIPCHK(0, hipMemcpyAsync(Pr[l], (T *)r.st.P[r.st.ip] + e.plane * e.glo, e.plane * e.nz * sizeof(T), hipMemcpyDeviceToDevice, s));
-        HIPCHK(0, hipMemcpyAsync(D[l], (T *)r.st.D[r.st.id] + e.dplane * e.glo, e.dplane * (e.nz - 2) * sizeof(T), hipMemcpyDeviceToDevice, s));
-    }
-    return NS3D_OK;
-}
-
 // the ranks advance in lockstep: the MINIMUM of the depths the processes measured (min through the max reduction)
 int agree_min_depth(ns3d_mgpu *m, int &depth)
 {
@@ -640,89 +412,30 @@ int agree_min_depth(ns3d_mgpu *m, int &depth)
     return NS3D_OK;
 }
 
-// Tile shapes and iterations per pass for the interior range of every rank: measured once, with no exchange in flight.  The
-// ranks must advance in lockstep, so the pass depth is the MINIMUM of what the ranks measured (ncclAllReduce(min) across
-// processes), capped by the ghost depth.
-template <class T>
-int slab_plan(ns3d_mgpu *m)
+struct PtLoop {                    // the loop arguments of ns3d_pt_solve_slab
+    double eps; int niter, nchk; double err_mul, err_div; int *iters_done; double *err_hist; int max_checks; int *n_checks;
+};
+// multi.jl:464-469 for every multi-rank solve: `iterate(n)` advances all local ranks by the n iterations up to the next
+// residual check, `residual(&mx)` is max_g(maximum(abs.(Rp))) of the current iterate
+template <class Iterate, class Residual>
+int check_loop(const PtLoop &lp, Iterate iterate, Residual residual)
 {
-    int depth = m->G + 1;
-    if (depth >= 2) {
-        for (MRank &r : m->loc) {
-            const Ext<T> e(m, r);
-            const int np = m->G + 1;
-            const int a = has_lower(m, r) ? std::min(e.k0 + np, e.k1) : e.k0, b = has_upper(m, r) ? std::max(e.k1 - np, a) : e.k1;
-            // Between ranks a pass costs its sweeps PLUS an exchange, and the deepest pass the ghosts allow wins on every slab
-            // measured (tools/cart_rates.py, virtual ranks: 8 × 130³ 0.46 / 0.38 / 0.28 ms per iteration with two / three / four per
-            // pass, 2 × 258³ 0.25 / 0.22 / 0.20; 512² planes: DESIGN §6) although the sweep alone prefers two or three on small
-            // planes: with neighbours the tile shapes are measured FOR that depth unless the caller pinned one (ns3d_set_pt_depth).
-            const int pinned = r.ctx->pt_depth;
-            const int want = (pinned <= 0 && m->P > 1) ? m->G + 1 : pinned;
-            if (b - a < 2) {        // nothing to measure on
-                depth = std::min(depth, want >= 2 ? want : 2);
-                continue;
-            }
-            const ns3d_pt_params pe = ext_params(m, r);
-            ns3d_device_guard g(r.device);
-            // outputs go to the buffers the next pass overwrites anyway
-            r.ctx->pt_depth = want;
-            const int d = ns3d_plan_pt_internal<T>(r.ctx, (const T *)r.st.P[r.st.ip], (T *)r.st.P[r.st.ip ^ 1],
-                                                   (const T *)r.st.D[r.st.id], (T *)r.st.D[r.st.id ^ 1], (const T *)r.st.R, &pe, a, b);
-            r.ctx->pt_depth = pinned;
-            r.plan_v2 = ns3d_last_pt2_variant(r.ctx); r.plan_vn = ns3d_last_ptn_variant(r.ctx); r.plan_lo = a; r.plan_hi = b;
-            depth = std::min(depth, std::max(2, d));
-        }
-    }
-    { const int rcd = agree_min_depth(m, depth); if (rcd) return rcd; }
-    m->pass_depth = std::max(1, std::min(depth, m->G + 1));
-    // The ghost depth was fixed at load time from the DEEPEST pass allowed (m->depth); when the ranks settle for fewer iterations
-    // per pass (exact-division arithmetic, thin slabs) the outer ghost planes are dead weight: every pass would sweep G+1 seam
-    // planes per side and exchange (G+1) + G planes where pass_depth + (pass_depth−1) suffice.  Dropping them is a change of
-    // base: the buffers keep their allocation, plane 0 moves inwards by the difference on the sides that have a neighbour.
-    const int Gnew = m->pass_depth - 1;
-    if (m->pass_depth >= 2 && Gnew < m->G) {
-        for (MRank &r : m->loc) {
-            const Ext<T> e(m, r);
-            const size_t off = has_lower(m, r) ? (size_t)(m->G - Gnew) : 0;
-            for (int q = 0; q < 2; ++q) {
-                r.st.P[q] = (T *)r.st.P[q] + e.plane * off;
-                r.st.D[q] = (T *)r.st.D[q] + e.dplane * off;
-            }
-            r.st.R = (T *)r.st.R + e.plane * off;
-        }
-        m->G = Gnew;
-        for (MRank &r : m->loc) {
-            const Ext<T> e(m, r);
-            r.st.glo = e.glo; r.st.ghi = e.ghi; r.st.nze = e.nze;
-        }
-    }
-    return NS3D_OK;
-}
-
-template <class T>
-int solve_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, const ns3d_pt_params *p, double eps, int niter,
-               int nchk, double err_mul, double err_div, int *iters_done, double *err_hist, int max_checks, int *n_checks)
-{
-    int rc;
-    if ((rc = slab_load<T>(m, Pr, D, divV, p))) return rc;
-    if ((rc = slab_plan<T>(m))) return rc;
-    int checks = 0, iter = 0, done = niter;
-    while (iter < niter) {
-        const int n = nchk > 0 ? std::min(nchk - iter % nchk, niter - iter) : niter - iter;   // multi.jl:464
-        if ((rc = slab_iterate<T>(m, n))) return rc;
+    int rc, checks = 0, iter = 0, done = lp.niter;
+    while (iter < lp.niter) {
+        const int n = lp.nchk > 0 ? std::min(lp.nchk - iter % lp.nchk, lp.niter - iter) : lp.niter - iter;   // multi.jl:464
+        if ((rc = iterate(n))) return rc;
         iter += n;
-        if (nchk > 0 && iter % nchk == 0) {                                                     // multi.jl:465-469
+        if (lp.nchk > 0 && iter % lp.nchk == 0) {                                                        // multi.jl:465-469
             double mx;
-            if ((rc = slab_residual<T>(m, &mx))) return rc;
-            const double err = mx * err_mul / err_div;
-            if (err_hist && checks < max_checks) err_hist[checks] = err;
+            if ((rc = residual(&mx))) return rc;
+            const double err = mx * lp.err_mul / lp.err_div;
+            if (lp.err_hist && checks < lp.max_checks) lp.err_hist[checks] = err;
             ++checks;
-            if (eps >= 0 && (err < eps || !std::isfinite(err))) { done = iter; break; }
+            if (lp.eps >= 0 && (err < lp.eps || !std::isfinite(err))) { done = iter; break; }
         }
     }
-    if ((rc = slab_store<T>(m, Pr, D))) return rc;
-    if (iters_done) *iters_done = done;
-    if (n_checks) *n_checks = checks;
+    if (lp.iters_done) *lp.iters_done = done;
+    if (lp.n_checks) *lp.n_checks = checks;
     return NS3D_OK;
 }
 
@@ -963,11 +676,10 @@ int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, c
 // entries between a halo face and a physical face arrive from the rank that owns them.  The interior of iterate n+1 reads
 // only iterate n, whose halos are complete: the iterates equal the reference's kernel-by-kernel sequence with its four halo
 // updates per iteration bit for bit (and the single-device solve of the global grid: Jacobi sweeps are decomposition
-// independent).  This is the depth-1 form (ns3d_mgpu_set_temporal(m, 1), NS3D_CART_DEEP=0, ranks too thin for ghosts): solve_box
+// independent).  This is the depth-1 form (ns3d_mgpu_set_temporal(m, 1), NS3D_CART_DEEP=0, ranks too thin for ghosts): solve_deep
 // below advances several iterations per pass on such topologies too.
 template <class T>
-int solve_cart(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, const ns3d_pt_params *p, double eps, int niter,
-               int nchk, double err_mul, double err_div, int *iters_done, double *err_hist, int max_checks, int *n_checks)
+int solve_cart(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, const ns3d_pt_params *p, const PtLoop &lp)
 {
     int rc = ns3d_check_pt_params(p, "ns3d_pt_solve_slab");
     if (rc) return rc;
@@ -995,61 +707,59 @@ int solve_cart(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, co
         pe[l].z_lo_is_halo = pe[l].z_hi_is_halo = 0;                          // every face folded; update_halo! overwrites
     }
     const int ext[3] = {m->nx, m->ny, m->nz};
-    int checks = 0, iter = 0, done = niter;
-    while (iter < niter) {
-        for (int l = 0; l < n; ++l) {
-            MRank &r = m->loc[l];
-            ns3d_device_guard g(r.device);
-            hipError_t e = ns3d_enqueue_pt1<T>(r.ctx, compute(r), cur[l], other[l], D[l], divV[l], &pe[l], 1, m->nz - 1);
-            if (e != hipSuccess) return fail(NS3D_ERR_HIP, "sweep launch: %s", hipGetErrorString(e));
-        }
-        if ((rc = update_halo_core<T>(m, other.data(), ext, 1))) return rc;
-        cur.swap(other);
-        ++iter;
-        if (nchk > 0 && iter % nchk == 0) {                                                     // multi.jl:464-469
+    auto iterate = [&](int k) -> int {
+        for (int it = 0; it < k; ++it) {
             for (int l = 0; l < n; ++l) {
                 MRank &r = m->loc[l];
                 ns3d_device_guard g(r.device);
-                hipError_t e = ns3d_enqueue_residual_key<T>(r.ctx, compute(r), cur[l], divV[l], &pe[l], r.ctx->key_dev);
-                if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));
+                hipError_t e = ns3d_enqueue_pt1<T>(r.ctx, compute(r), cur[l], other[l], D[l], divV[l], &pe[l], 1, m->nz - 1);
+                if (e != hipSuccess) return fail(NS3D_ERR_HIP, "sweep launch: %s", hipGetErrorString(e));
             }
-            double mx;
-            if ((rc = reduce_keys(m, &mx))) return rc;
-            const double err = mx * err_mul / err_div;
-            if (err_hist && checks < max_checks) err_hist[checks] = err;
-            ++checks;
-            if (eps >= 0 && (err < eps || !std::isfinite(err))) { done = iter; break; }
+            const int rc2 = update_halo_core<T>(m, other.data(), ext, 1);
+            if (rc2) return rc2;
+            cur.swap(other);
         }
-    }
+        return NS3D_OK;
+    };
+    auto residual = [&](double *mx) -> int {
+        for (int l = 0; l < n; ++l) {
+            MRank &r = m->loc[l];
+            ns3d_device_guard g(r.device);
+            hipError_t e = ns3d_enqueue_residual_key<T>(r.ctx, compute(r), cur[l], divV[l], &pe[l], r.ctx->key_dev);
+            if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));
+        }
+        return reduce_keys(m, mx);
+    };
+    if ((rc = check_loop(lp, iterate, residual))) return rc;
     for (int l = 0; l < n; ++l)
         if (cur[l] != Pr[l]) {
             MRank &r = m->loc[l];
             ns3d_device_guard g(r.device);
             HIPCHK(0, hipMemcpyAsync(Pr[l], cur[l], bytes, hipMemcpyDeviceToDevice, compute(r)));
         }
-    if (iters_done) *iters_done = done;
-    if (n_checks) *n_checks = checks;
     return NS3D_OK;
 }
 
 // =====================================================================================================================
-// Deep ghosts on ANY Cartesian topology (round 3, second session): `init_global_grid(nx,ny,nz)` as multi.jl:325 calls it leaves the
-// topology to MPI.Dims_create! — (2,1,1), (2,2,1), (2,2,2) for 2, 4, 8 ranks — so a drop-in for the unmodified script never sees
-// z-slabs, and solve_cart's one sweep + one update_halo! per iteration was all it got.  Here every rank keeps its solve state in a
-// BOX extended by G = depth−1 ghost cells on each side that has a neighbour, in x, y and z; a pass advances `its` ≤ G+1
-// iterations on the whole box as if it were a grid of its own (the boundary rule is folded in on every box face: on a physical
-// face that is the reference's rule, on a ghost face it writes values that are wrong — and are at least `its` cells away from the
-// rank's own cells by the end of the pass, Jacobi sweeps move information one cell per iteration), then the G+1 outermost OWN layers
-// of Pr and the G outermost of dPrdτ travel to the neighbours, dimension by dimension with the FULL extents of the other two
-// (x, then y — which carries the fresh x ghosts — then z: edges and corners arrive in two / three hops).  x and y layers are
-// strided and go through k_subbox_copy on both ends; z layers are contiguous.  Same iterates as the global solve, bit for bit.
-// No overlap of exchange and sweep yet: the win is the pass itself (one pass over memory per `its` iterations, one round of
-// exchanges per pass instead of per iteration).
+// Deep ghosts (ns3d_slab_*, ns3d_pt_solve_slab) on any Cartesian topology.  Every rank keeps its solve state in library-owned
+// buffers, a BOX extended by G = depth−1 ghost cells on each side that has a neighbour; z-slabs are the boxes with ghosts in z
+// only.  A pass advances `its` ≤ G+1 iterations on the whole box as if it were a grid of its own (the boundary rule is folded in
+// on every box face: on a physical face that is the reference's rule, on a ghost face it writes values that are wrong — and are
+// at least `its` cells away from the rank's own cells by the end of the pass, Jacobi sweeps move information one cell per
+// iteration), then the G+1 outermost OWN layers of Pr and the G outermost of dPrdτ travel to the neighbours, dimension by
+// dimension with the FULL extents of the other two (x, then y — which carries the fresh x ghosts — then z: edges and corners
+// arrive in two / three hops).  x and y layers are strided and go through k_subbox_copy on both ends; z layers are contiguous.
+// Same iterates as the global solve, bit for bit.  Why not solve_cart's one sweep + one update_halo! per iteration:
+// `init_global_grid(nx,ny,nz)` as multi.jl:325 calls it leaves the topology to MPI.Dims_create! — (2,1,1), (2,2,1), (2,2,2) for
+// 2, 4, 8 ranks — so a drop-in for the unmodified script never sees z-slabs, and one pass over memory plus one round of
+// exchanges per `its` iterations beats one per iteration there too.
 // =====================================================================================================================
 template <class T>
 struct Box {                       // geometry of one rank's extended box
     int n[3], g[3][2], e[3], G;
+    int k0[3], k1[3];              // the own inner layers [k0,k1) of the Pr-shaped arrays, per dimension
     size_t px, pl, dpx, dpl, cells, dcells;
+    size_t op, od;                 // offsets of the rank's own cells in the Pr-shaped and the dPrdτ-shaped arrays
     Box(const ns3d_mgpu *m, const MRank &r)
     {
         n[0] = m->nx; n[1] = m->ny; n[2] = m->nz; G = m->G;
@@ -1057,9 +767,12 @@ struct Box {                       // geometry of one rank's extended box
             g[d][0] = r.nbr[d][0] >= 0 ? G : 0;
             g[d][1] = r.nbr[d][1] >= 0 ? G : 0;
             e[d] = n[d] + g[d][0] + g[d][1];
+            k0[d] = g[d][0] + 1; k1[d] = g[d][0] + n[d] - 1;
         }
         px = (size_t)e[0]; pl = px * e[1]; cells = pl * e[2];
         dpx = (size_t)(e[0] - 2); dpl = dpx * (e[1] - 2); dcells = dpl * (e[2] - 2);
+        op = g[0][0] + px * g[1][0] + pl * g[2][0];
+        od = g[0][0] + dpx * g[1][0] + dpl * g[2][0];
     }
 };
 struct BoxArr { void *base; bool dshape; int layers; };   // an array of the box and how many layers per seam travel
@@ -1085,12 +798,38 @@ ns3d_pt_params box_params(const ns3d_mgpu *m, const MRank &r)
     ns3d_pt_params pe = m->p;
     pe.nx = b.e[0]; pe.ny = b.e[1]; pe.nz = b.e[2];
     pe.owns_outlet = (m->p.owns_outlet && r.nbr[0][1] < 0) ? 1 : 0;       // multi.jl:179: the ranks on the outlet plane
-    pe.z_lo_is_halo = pe.z_hi_is_halo = 0;
+    // G = 0 (z-slabs only): the halo planes are the buffers' outermost planes and must not be treated as faces; G > 0: the
+    // sweeps never produce the outermost layers of a ghost side at all
+    pe.z_lo_is_halo = (b.G == 0 && r.nbr[2][0] >= 0) ? 1 : 0;
+    pe.z_hi_is_halo = (b.G == 0 && r.nbr[2][1] >= 0) ? 1 : 0;
     return pe;
 }
 
+// the z layers of one array: a contiguous block per side (dPrdτ travels nothing at G = 0)
+template <class T>
+void z_block(const Box<T> &b, const BoxArr &a, std::vector<Block> &v)
+{
+    if (a.layers == 0) return;
+    const int sh = a.dshape ? 2 : 0, L = a.layers;
+    const size_t pl = (size_t)(b.e[0] - sh) * (b.e[1] - sh);
+    const int send_lo = b.k0[2] - sh / 2, send_hi = b.k1[2] - sh / 2 - L, recv_hi = b.e[2] - sh - L;
+    T *A = (T *)a.base;
+    v.push_back({A + pl * send_lo, A, A + pl * send_hi, A + pl * recv_hi, pl * L * sizeof(T)});
+}
+
+// The planes a pass's interior launch covers: between the seam sweeps on z-slabs (deep_pass sweeps the G+1 planes next to a seam
+// first), the whole box otherwise
+template <class T>
+void interior_planes(const ns3d_mgpu *m, const MRank &r, const Box<T> &b, int &lo, int &hi)
+{
+    lo = 1; hi = b.e[2] - 1;
+    if (!z_slabs(m)) return;
+    if (r.nbr[2][0] >= 0) lo = std::min(b.k0[2] + b.G + 1, b.k1[2]);
+    if (r.nbr[2][1] >= 0) hi = std::max(b.k1[2] - (b.G + 1), lo);
+}
+
 // ghost layers of `arrs[l]` (same list on every rank) from the neighbours' own layers: x, y, z in turn
-// on_comm: the whole chain — pack, exchange, unpack, dimension after dimension — runs on the ranks' communication streams (box_pass
+// on_comm: the whole chain — pack, exchange, unpack, dimension after dimension — runs on the ranks' communication streams (box_pass_overlapped
 // with the shells swept there first, the core sweep on the compute streams meanwhile); the caller joins the streams afterwards
 template <class T>
 int box_exchange(ns3d_mgpu *m, const std::vector<std::vector<BoxArr>> &arrs, bool on_comm = false)
@@ -1135,18 +874,14 @@ int box_exchange(ns3d_mgpu *m, const std::vector<std::vector<BoxArr>> &arrs, boo
             size_t off = 0;
             ns3d_subbox_batch<T> pack;                  // every array's layers for both neighbours: one launch
             for (const BoxArr &a : arrs[l]) {
+                if (d == 2) { z_block(b, a, blocks[l]); continue; }
                 const int sh = a.dshape ? 2 : 0, L = a.layers;
                 const int s[3] = {b.e[0] - sh, b.e[1] - sh, b.e[2] - sh};
                 const size_t px = (size_t)s[0], pl = px * s[1];
                 const size_t pitch[3] = {1, px, pl};
-                const int k0 = b.g[d][0] + 1, k1 = b.g[d][0] + b.n[d] - 1;               // own inner layers [k0,k1) of the P-shaped arrays
-                const int send_lo = a.dshape ? k0 - 1 : k0, send_hi = (a.dshape ? k1 - 1 : k1) - L;
+                const int send_lo = a.dshape ? b.k0[d] - 1 : b.k0[d], send_hi = (a.dshape ? b.k1[d] - 1 : b.k1[d]) - L;
                 const int recv_lo = 0, recv_hi = s[d] - L;
                 T *A = (T *)a.base;
-                if (d == 2) {
-                    blocks[l].push_back({A + pl * send_lo, A + pl * recv_lo, A + pl * send_hi, A + pl * recv_hi, pl * L * sizeof(T)});
-                    continue;
-                }
                 int c[3] = {s[0], s[1], s[2]};
                 c[d] = L;
                 const size_t face = (size_t)c[0] * c[1] * c[2];
@@ -1201,71 +936,97 @@ int box_exchange(ns3d_mgpu *m, const std::vector<std::vector<BoxArr>> &arrs, boo
     return NS3D_OK;
 }
 
+// The state from the caller's arrays: the own cells in, then the ghosts of Pr, dPrdτ — and of the right-hand side: level 1 on a
+// ghost layer needs ∇V there, beyond the one-layer halo the caller's update_halo!(∇V) filled (that layer is re-sent: same value).
+// The buffers are zeroed once per size: every pass writes all the cells a later pass or the store reads.
 template <class T>
-int box_load(ns3d_mgpu *m, const T *const *Pr, const T *const *D, const T *const *divV, const ns3d_pt_params *p)
+int deep_load(ns3d_mgpu *m, const T *const *Pr, const T *const *D, const T *const *divV, const ns3d_pt_params *p, const char *fn)
 {
+    int rc = ns3d_check_pt_params(p, fn);
+    if (rc) return rc;
+    if (p->nx != m->nx || p->ny != m->ny || p->nz != m->nz)
+        return fail(NS3D_ERR_ARG, "%s: params grid %dx%dx%d differs from the grid of ns3d_mgpu_create %dx%dx%d", fn, p->nx, p->ny,
+                    p->nz, m->nx, m->ny, m->nz);
+    if (p->bc_kind != NS3D_BC_MULTI && m->P > 1) return fail(NS3D_ERR_ARG, "%s: gpu.jl's boundary set is single-device", fn);
+    if (m->nz < 4 && m->dims[2] > 1) return fail(NS3D_ERR_ARG, "%s: z-slab ranks need at least two interior planes", fn);
     m->p = *p;
     m->G = box_ghost_depth(m);
     m->esize = (int)sizeof(T);
+    const bool z = z_slabs(m);
     std::vector<std::vector<BoxArr>> arrs;
     for (size_t l = 0; l < m->loc.size(); ++l) {
         MRank &r = m->loc[l];
-        if (!Pr[l] || !D[l] || !divV[l]) return fail(NS3D_ERR_ARG, "ns3d_pt_solve_slab: null field pointer (local rank %zu)", l);
+        if (!Pr[l] || !D[l] || !divV[l]) return fail(NS3D_ERR_ARG, "%s: null field pointer (local rank %zu)", fn, l);
         const Box<T> b(m, r);
         const size_t bp = b.cells * sizeof(T), bd = b.dcells * sizeof(T);
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
         if (r.st.bytes_P != bp || r.st.bytes_D != bd) {
-            int rc = sync_all(m);
-            if (rc) return rc;
+            if ((rc = sync_all(m))) return rc;          // a neighbour may still be pulling from the old buffers
             free_slab(r);
             for (int q = 0; q < 2; ++q) {
                 HIPCHK(0, hipMalloc(&r.st.Pa[q], bp));
                 HIPCHK(0, hipMalloc(&r.st.Da[q], bd));
+                HIPCHK(0, hipMemsetAsync(r.st.Pa[q], 0, bp, s));
+                HIPCHK(0, hipMemsetAsync(r.st.Da[q], 0, bd, s));
             }
             HIPCHK(0, hipMalloc(&r.st.Ra, bp));
+            HIPCHK(0, hipMemsetAsync(r.st.Ra, 0, bp, s));
             r.st.bytes_P = bp; r.st.bytes_D = bd;
         }
-        for (int q = 0; q < 2; ++q) {
-            r.st.P[q] = r.st.Pa[q]; r.st.D[q] = r.st.Da[q];
-            HIPCHK(0, hipMemsetAsync(r.st.P[q], 0, bp, s));
-            HIPCHK(0, hipMemsetAsync(r.st.D[q], 0, bd, s));
-        }
+        for (int q = 0; q < 2; ++q) { r.st.P[q] = r.st.Pa[q]; r.st.D[q] = r.st.Da[q]; }
         r.st.R = r.st.Ra;
-        HIPCHK(0, hipMemsetAsync(r.st.R, 0, bp, s));
         r.st.ip = r.st.id = 0;
-        const size_t op = b.g[0][0] + b.px * b.g[1][0] + b.pl * b.g[2][0], od = b.g[0][0] + b.dpx * b.g[1][0] + b.dpl * b.g[2][0];
-        const long nx = b.n[0], ny = b.n[1];
-        ns3d_subbox_batch<T> in;
-        in.add((T *)r.st.P[0] + op, (long)b.px, (long)b.pl, Pr[l], nx, nx * ny, b.n[0], b.n[1], b.n[2]);
-        in.add((T *)r.st.R + op, (long)b.px, (long)b.pl, divV[l], nx, nx * ny, b.n[0], b.n[1], b.n[2]);
-        in.add((T *)r.st.D[0] + od, (long)b.dpx, (long)b.dpl, D[l], nx - 2, (nx - 2) * (ny - 2), b.n[0] - 2, b.n[1] - 2, b.n[2] - 2);
-        hipError_t e = ns3d_enqueue_subbox_copy<T>(r.ctx, s, in);
-        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "box load launch: %s", hipGetErrorString(e));
+        r.plan_v2 = r.plan_vn = -1; r.plan_lo = r.plan_hi = 0;       // a new state: planned again by deep_plan
+        T *P0 = (T *)r.st.P[0] + b.op, *D0 = (T *)r.st.D[0] + b.od, *R0 = (T *)r.st.R + b.op;
+        const int nx = b.n[0], ny = b.n[1], nz = b.n[2];
+        if (z) {        // the own planes are one contiguous block
+            HIPCHK(0, hipMemcpyAsync(P0, Pr[l], b.pl * nz * sizeof(T), hipMemcpyDeviceToDevice, s));
+            HIPCHK(0, hipMemcpyAsync(D0, D[l], b.dpl * (nz - 2) * sizeof(T), hipMemcpyDeviceToDevice, s));
+            HIPCHK(0, hipMemcpyAsync(R0, divV[l], b.pl * nz * sizeof(T), hipMemcpyDeviceToDevice, s));
+        } else {
+            ns3d_subbox_batch<T> in;
+            in.add(P0, (long)b.px, (long)b.pl, Pr[l], nx, (long)nx * ny, nx, ny, nz);
+            in.add(R0, (long)b.px, (long)b.pl, divV[l], nx, (long)nx * ny, nx, ny, nz);
+            in.add(D0, (long)b.dpx, (long)b.dpl, D[l], nx - 2, (long)(nx - 2) * (ny - 2), nx - 2, ny - 2, nz - 2);
+            hipError_t e = ns3d_enqueue_subbox_copy<T>(r.ctx, s, in);
+            if (e != hipSuccess) return fail(NS3D_ERR_HIP, "box load launch: %s", hipGetErrorString(e));
+        }
+        if (m->G == 0) {    // single sweeps write Pr_out's interior planes only: seed the other buffer's outer planes
+            HIPCHK(0, hipMemcpyAsync(r.st.P[1], r.st.P[0], b.pl * sizeof(T), hipMemcpyDeviceToDevice, s));
+            HIPCHK(0, hipMemcpyAsync((T *)r.st.P[1] + b.pl * (b.e[2] - 1), (T *)r.st.P[0] + b.pl * (b.e[2] - 1), b.pl * sizeof(T),
+                                     hipMemcpyDeviceToDevice, s));
+        }
         arrs.push_back({{r.st.P[0], false, m->G + 1}, {r.st.D[0], true, m->G}, {r.st.R, false, m->G + 1}});
     }
+    m->loaded = z;      // ns3d_slab_iterate / _plan / _residual / _store take z-slab state only
     return box_exchange<T>(m, arrs);
 }
 
 template <class T>
-int box_store(ns3d_mgpu *m, T *const *Pr, T *const *D)
+int deep_store(ns3d_mgpu *m, T *const *Pr, T *const *D)
 {
     for (size_t l = 0; l < m->loc.size(); ++l) {
         MRank &r = m->loc[l];
+        if (!Pr[l] || !D[l]) return fail(NS3D_ERR_ARG, "ns3d_slab_store: null field pointer (local rank %zu)", l);
         const Box<T> b(m, r);
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
-        const size_t op = b.g[0][0] + b.px * b.g[1][0] + b.pl * b.g[2][0], od = b.g[0][0] + b.dpx * b.g[1][0] + b.dpl * b.g[2][0];
-        const long nx = b.n[0], ny = b.n[1];
+        const T *P0 = (const T *)r.st.P[r.st.ip] + b.op, *D0 = (const T *)r.st.D[r.st.id] + b.od;
+        const int nx = b.n[0], ny = b.n[1], nz = b.n[2];
+        if (z_slabs(m)) {
+            HIPCHK(0, hipMemcpyAsync(Pr[l], P0, b.pl * nz * sizeof(T), hipMemcpyDeviceToDevice, s));
+            HIPCHK(0, hipMemcpyAsync(D[l], D0, b.dpl * (nz - 2) * sizeof(T), hipMemcpyDeviceToDevice, s));
+            continue;
+        }
         ns3d_subbox_batch<T> out;
-        out.add(Pr[l], nx, nx * ny, (const T *)r.st.P[r.st.ip] + op, (long)b.px, (long)b.pl, b.n[0], b.n[1], b.n[2]);
-        out.add(D[l], nx - 2, (nx - 2) * (ny - 2), (const T *)r.st.D[r.st.id] + od, (long)b.dpx, (long)b.dpl, b.n[0] - 2, b.n[1] - 2, b.n[2] - 2);
+        out.add(Pr[l], nx, (long)nx * ny, P0, (long)b.px, (long)b.pl, nx, ny, nz);
+        out.add(D[l], nx - 2, (long)(nx - 2) * (ny - 2), D0, (long)b.dpx, (long)b.dpl, nx - 2, ny - 2, nz - 2);
         hipError_t e = ns3d_enqueue_subbox_copy<T>(r.ctx, s, out);
         if (e != hipSuccess) return fail(NS3D_ERR_HIP, "box store launch: %s", hipGetErrorString(e));
     }
     return NS3D_OK;
 }
-
 // The shells first (round 4; the reference reserves b_width = (8,8,4) "for comm / comp overlap", multi.jl:326, and never
 // uses it).  A pass of `its` ≥ 2 iterations is issued in pieces: on the COMMUNICATION stream the tiles / planes that produce every own
 // cell within G+1 layers of a decomposed face — two plane ranges in z, two strips of tile rows, two strips of tile columns (sub-rectangles
@@ -1303,8 +1064,7 @@ int box_pass_overlapped(ns3d_mgpu *m, int its, bool &done)
         const int S[2] = {q.ge.TX - q.ge.OV, q.ge.TY - q.ge.OV}, nt[2] = {q.ge.ntx, q.ge.nty}, half = q.ge.OV / 2;
         int tlo[2], thi[2];
         for (int d = 0; d < 3; ++d) {
-            const int k0 = b.g[d][0] + 1, k1 = b.g[d][0] + b.n[d] - 1;            // own inner cells [k0,k1) of the box
-            int lo = r.nbr[d][0] >= 0 ? std::min(k0 + b.G + 1, b.e[d] - 1) : 1, hi = r.nbr[d][1] >= 0 ? std::max(k1 - (b.G + 1), lo) : b.e[d] - 1;
+            int lo = r.nbr[d][0] >= 0 ? std::min(b.k0[d] + b.G + 1, b.e[d] - 1) : 1, hi = r.nbr[d][1] >= 0 ? std::max(b.k1[d] - (b.G + 1), lo) : b.e[d] - 1;
             if (d < 2) {     // whole tiles: tile t produces the cells [begin(t), begin(t+1))
                 auto begin = [&](int t) { return t <= 0 ? 1 : (t >= nt[d] ? b.e[d] - 1 : 1 + t * S[d] + half); };
                 int a = 0;
@@ -1377,104 +1137,174 @@ int box_pass_overlapped(ns3d_mgpu *m, int its, bool &done)
     return NS3D_OK;
 }
 
-// one pass: `its` (1 … G+1) PT iterations on every local rank's box, then the ghosts of the new state
+// One pass: `its` (1 … G+1) PT iterations on every local rank, then the ghosts of the new state.
+//   * z-slabs: the seam-adjacent output planes are swept on the rank's high-priority COMMUNICATION stream, their exchange follows
+//     them there in stream order, and the interior sweep runs on the compute stream AT THE SAME TIME (the three sweeps read the
+//     same input buffers and write disjoint planes): no launch of a pass waits for the tail of another one, and the exchange starts
+//     as soon as the thin seam sweeps are done (seam sweeps ahead of the interior on the compute stream cost two more kernel
+//     boundaries per pass, 1.5× the global solve's time on 66-plane slabs).  Ordering: the communication stream first waits for
+//     everything the compute stream held when the pass began (the previous pass's interior planes, and through its exchange_end
+//     the neighbours' pulls of the planes this pass overwrites).
+//   * x/y-decomposed boxes: box_pass_overlapped where it applies, else the whole box, then box_exchange.
 template <class T>
-int box_pass(ns3d_mgpu *m, int its)
+int deep_pass(ns3d_mgpu *m, int its)
 {
-    {
+    const bool z = z_slabs(m);
+    int rc;
+    if (!z) {
         bool done = false;
-        const int rc = box_pass_overlapped<T>(m, its, done);
-        if (rc || done) return rc;
+        if ((rc = box_pass_overlapped<T>(m, its, done)) || done) return rc;
     }
-    const int ip = m->loc[0].st.ip, idd = m->loc[0].st.id;
+    const int ip = m->loc[0].st.ip, idd = m->loc[0].st.id;          // the ranks advance in lockstep
     const int idd_out = its >= 2 ? idd ^ 1 : idd;
-    std::vector<std::vector<BoxArr>> arrs;
-    for (MRank &r : m->loc) {
+    auto sweep = [&](MRank &r, hipStream_t st, int a, int b) -> int {
+        if (b <= a) return NS3D_OK;
         const ns3d_pt_params pe = box_params<T>(m, r);
         ns3d_device_guard g(r.device);
         hipError_t e;
-        if (its >= 2)
-            e = ns3d_enqueue_pass<T>(r.ctx, compute(r), its, (const T *)r.st.P[ip], (T *)r.st.P[ip ^ 1], (const T *)r.st.D[idd],
-                                     (T *)r.st.D[idd_out], (const T *)r.st.R, &pe, 1, pe.nz - 1, r.plan_v2, r.plan_vn);
+        if (its >= 2) {
+            const bool planned = a >= r.plan_lo && b <= r.plan_hi;              // the interior (or a chunk of it): the rank's own plan
+            e = ns3d_enqueue_pass<T>(r.ctx, st, its, (const T *)r.st.P[ip], (T *)r.st.P[ip ^ 1], (const T *)r.st.D[idd],
+                                     (T *)r.st.D[idd_out], (const T *)r.st.R, &pe, a, b, planned ? r.plan_v2 : -1, planned ? r.plan_vn : -1);
+        }
         else
-            e = ns3d_enqueue_pt1<T>(r.ctx, compute(r), (const T *)r.st.P[ip], (T *)r.st.P[ip ^ 1], (T *)r.st.D[idd], (const T *)r.st.R,
-                                    &pe, 1, pe.nz - 1);
-        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "box sweep launch: %s", hipGetErrorString(e));
-        arrs.push_back({{r.st.P[ip ^ 1], false, m->G + 1}, {r.st.D[idd_out], true, m->G}});
+            e = ns3d_enqueue_pt1<T>(r.ctx, st, (const T *)r.st.P[ip], (T *)r.st.P[ip ^ 1], (T *)r.st.D[idd],
+                                    (const T *)r.st.R, &pe, a, b);
+        return e == hipSuccess ? NS3D_OK : fail(NS3D_ERR_HIP, "sweep launch: %s", hipGetErrorString(e));
+    };
+    auto sent = [&](MRank &r) { return std::vector<BoxArr>{{r.st.P[ip ^ 1], false, m->G + 1}, {r.st.D[idd_out], true, m->G}}; };
+    if (!z) {
+        std::vector<std::vector<BoxArr>> arrs;
+        for (MRank &r : m->loc) {
+            if ((rc = sweep(r, compute(r), 1, Box<T>(m, r).e[2] - 1))) return rc;
+            arrs.push_back(sent(r));
+        }
+        if ((rc = box_exchange<T>(m, arrs))) return rc;
+    } else {
+        const bool split = m->P > 1 && !m->serial_seams;
+        std::vector<int> lo(m->loc.size()), hi(m->loc.size());
+        std::vector<std::vector<Block>> blocks(m->loc.size());
+        for (size_t l = 0; l < m->loc.size(); ++l) {
+            MRank &r = m->loc[l];
+            const Box<T> b(m, r);
+            interior_planes(m, r, b, lo[l], hi[l]);
+            hipStream_t seam = compute(r);
+            if (split) {
+                ns3d_device_guard g(r.device);
+                HIPCHK(0, hipEventRecord(r.ev_pass, compute(r)));
+                HIPCHK(0, hipStreamWaitEvent(r.comm, r.ev_pass, 0));
+                seam = r.comm;
+            }
+            if ((rc = sweep(r, seam, b.k0[2], lo[l]))) return rc;
+            if ((rc = sweep(r, seam, hi[l], b.k1[2]))) return rc;
+            for (const BoxArr &a : sent(r)) z_block(b, a, blocks[l]);
+        }
+        if ((rc = exchange_begin(m, blocks, 2, split))) return rc;
+        // the interior, in `interior_chunks` launches over consecutive plane ranges while an exchange is pending (ns3d.h: a kernel of
+        // the exchange finds CUs at the latest when a chunk ends; every chunk pays its own pipeline fill, so one launch unless asked)
+        for (size_t l = 0; l < m->loc.size(); ++l) {
+            const int a = lo[l], b = hi[l];
+            const int nch = (m->P > 1 && b - a >= 8 * m->interior_chunks) ? m->interior_chunks : 1;
+            for (int q = 0; q < nch; ++q)
+                if ((rc = sweep(m->loc[l], compute(m->loc[l]), a + (int)((long)(b - a) * q / nch), a + (int)((long)(b - a) * (q + 1) / nch)))) return rc;
+        }
+        if ((rc = exchange_end(m))) return rc;
     }
-    const int rc = box_exchange<T>(m, arrs);
-    if (rc) return rc;
     for (MRank &r : m->loc) { r.st.ip = ip ^ 1; r.st.id = idd_out; }
     return NS3D_OK;
 }
 
 template <class T>
-int box_plan(ns3d_mgpu *m)
+int deep_iterate(ns3d_mgpu *m, int n)
 {
-    int depth = m->G + 1;
-    if (depth >= 2)
-        for (MRank &r : m->loc) {
-            const ns3d_pt_params pe = box_params<T>(m, r);
-            ns3d_device_guard g(r.device);
-            // A pass costs its sweep plus one round of exchanges (three dimensions, pack and unpack kernels on both ends), so the
-            // deepest pass the ghosts allow wins whatever the sweep alone would prefer (tools/cart_rates.py: (2,2,2) ranks of 130³
-            // 0.85 / 0.70 / 0.64 ms per iteration with two / three / four per pass): the tile shapes are measured FOR that depth,
-            // unless the caller pinned one (ns3d_set_pt_depth).  Outputs go to the buffers the next pass overwrites anyway.
-            const int pinned = r.ctx->pt_depth;
-            if (pinned <= 0) r.ctx->pt_depth = m->G + 1;
-            const int d = ns3d_plan_pt_internal<T>(r.ctx, (const T *)r.st.P[r.st.ip], (T *)r.st.P[r.st.ip ^ 1], (const T *)r.st.D[r.st.id],
-                                                   (T *)r.st.D[r.st.id ^ 1], (const T *)r.st.R, &pe, 1, pe.nz - 1);
-            r.ctx->pt_depth = pinned;
-            r.plan_v2 = ns3d_last_pt2_variant(r.ctx); r.plan_vn = ns3d_last_ptn_variant(r.ctx);
-            depth = std::min(depth, std::max(2, d));
-        }
-    const int rc = agree_min_depth(m, depth);
-    if (rc) return rc;
-    m->pass_depth = std::max(1, std::min(depth, m->G + 1));
+    for (int it = 0; it < n;) {
+        const int rem = n - it, d = std::min(m->pass_depth, m->G + 1);
+        const int its = rem >= d ? ((rem == d + 1 && d >= 3) ? d - 1 : d) : rem;      // 4 = 2+2, not 3+1
+        const int rc = deep_pass<T>(m, its);
+        if (rc) return rc;
+        it += its;
+    }
     return NS3D_OK;
 }
 
 template <class T>
-int solve_box(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, const ns3d_pt_params *p, double eps, int niter,
-              int nchk, double err_mul, double err_div, int *iters_done, double *err_hist, int max_checks, int *n_checks)
+int deep_residual(ns3d_mgpu *m, double *out)
 {
-    int rc = ns3d_check_pt_params(p, "ns3d_pt_solve_slab");
-    if (rc) return rc;
-    if (p->nx != m->nx || p->ny != m->ny || p->nz != m->nz)
-        return fail(NS3D_ERR_ARG, "ns3d_pt_solve_slab: params grid %dx%dx%d differs from the grid of ns3d_mgpu_create %dx%dx%d", p->nx,
-                    p->ny, p->nz, m->nx, m->ny, m->nz);
-    if ((rc = box_load<T>(m, Pr, D, divV, p))) return rc;
-    if ((rc = box_plan<T>(m))) return rc;
-    int checks = 0, iter = 0, done = niter;
-    while (iter < niter) {
-        const int n = nchk > 0 ? std::min(nchk - iter % nchk, niter - iter) : niter - iter;   // multi.jl:464
-        for (int it = 0; it < n;) {
-            const int rem = n - it, d = m->pass_depth;
-            const int its = rem >= d ? ((rem == d + 1 && d >= 3) ? d - 1 : d) : rem;            // 4 = 2+2, not 3+1
-            if ((rc = box_pass<T>(m, its))) return rc;
-            it += its;
-        }
-        iter += n;
-        if (nchk > 0 && iter % nchk == 0) {                                                     // multi.jl:465-469
-            for (MRank &r : m->loc) {
-                const ns3d_pt_params pe = box_params<T>(m, r);
-                ns3d_device_guard g(r.device);
-                hipError_t e = ns3d_enqueue_residual_key<T>(r.ctx, compute(r), (const T *)r.st.P[r.st.ip], (const T *)r.st.R, &pe,
-                                                            r.ctx->key_dev);
-                if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));
+    for (MRank &r : m->loc) {
+        const ns3d_pt_params pe = box_params<T>(m, r);
+        ns3d_device_guard g(r.device);
+        hipError_t e = ns3d_enqueue_residual_key<T>(r.ctx, compute(r), (const T *)r.st.P[r.st.ip], (const T *)r.st.R, &pe,
+                                                    r.ctx->key_dev);
+        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));
+    }
+    return reduce_keys(m, out);
+}
+
+// Tile shapes and iterations per pass for the interior launch of every rank: measured once, with no exchange in flight.  The
+// ranks must advance in lockstep, so the pass depth is the MINIMUM of what the ranks measured (ncclAllReduce(min) across
+// processes), capped by the ghost depth.
+template <class T>
+int deep_plan(ns3d_mgpu *m)
+{
+    const bool z = z_slabs(m);
+    int depth = m->G + 1;
+    if (depth >= 2) {
+        for (MRank &r : m->loc) {
+            const Box<T> b(m, r);
+            int a, e;
+            interior_planes(m, r, b, a, e);
+            // Between ranks a pass costs its sweeps PLUS an exchange, and the deepest pass the ghosts allow wins on every topology
+            // measured (tools/cart_rates.py, virtual ranks, ms per iteration with two / three / four per pass: z-slabs 8 × 130³
+            // 0.46 / 0.38 / 0.28, 2 × 258³ 0.25 / 0.22 / 0.20, 512² planes: DESIGN §6; (2,2,2) ranks of 130³ 0.85 / 0.70 / 0.64)
+            // although the sweep alone prefers two or three on small planes: with neighbours the tile shapes are measured FOR that
+            // depth unless the caller pinned one (ns3d_set_pt_depth).
+            const int pinned = r.ctx->pt_depth;
+            const int want = (pinned <= 0 && m->P > 1) ? m->G + 1 : pinned;
+            if (z && e - a < 2) {       // no interior between the seams: nothing to measure on
+                depth = std::min(depth, want >= 2 ? want : 2);
+                continue;
             }
-            double mx;
-            if ((rc = reduce_keys(m, &mx))) return rc;
-            const double err = mx * err_mul / err_div;
-            if (err_hist && checks < max_checks) err_hist[checks] = err;
-            ++checks;
-            if (eps >= 0 && (err < eps || !std::isfinite(err))) { done = iter; break; }
+            const ns3d_pt_params pe = box_params<T>(m, r);
+            ns3d_device_guard g(r.device);
+            // outputs go to the buffers the next pass overwrites anyway
+            r.ctx->pt_depth = want;
+            const int d = ns3d_plan_pt_internal<T>(r.ctx, (const T *)r.st.P[r.st.ip], (T *)r.st.P[r.st.ip ^ 1],
+                                                   (const T *)r.st.D[r.st.id], (T *)r.st.D[r.st.id ^ 1], (const T *)r.st.R, &pe, a, e);
+            r.ctx->pt_depth = pinned;
+            r.plan_v2 = ns3d_last_pt2_variant(r.ctx); r.plan_vn = ns3d_last_ptn_variant(r.ctx); r.plan_lo = a; r.plan_hi = e;
+            depth = std::min(depth, std::max(2, d));
         }
     }
-    if ((rc = box_store<T>(m, Pr, D))) return rc;
-    if (iters_done) *iters_done = done;
-    if (n_checks) *n_checks = checks;
+    { const int rcd = agree_min_depth(m, depth); if (rcd) return rcd; }
+    m->pass_depth = std::max(1, std::min(depth, m->G + 1));
+    // The ghost depth was fixed at load time from the DEEPEST pass allowed (m->depth); when the ranks settle for fewer iterations
+    // per pass (exact-division arithmetic, thin slabs) the outer ghost planes are dead weight: every pass would sweep G+1 seam
+    // planes per side and exchange (G+1) + G planes where pass_depth + (pass_depth−1) suffice.  On z-slabs dropping them is a
+    // change of base: the buffers keep their allocation, plane 0 moves inwards by the difference on the sides that have a
+    // neighbour.  Not on x/y-decomposed boxes: there a smaller G would change the pitches too, not just the base.
+    const int Gnew = m->pass_depth - 1;
+    if (z && m->pass_depth >= 2 && Gnew < m->G) {
+        for (MRank &r : m->loc) {
+            const Box<T> b(m, r);
+            const size_t off = r.nbr[2][0] >= 0 ? (size_t)(m->G - Gnew) : 0;
+            for (int q = 0; q < 2; ++q) {
+                r.st.P[q] = (T *)r.st.P[q] + b.pl * off;
+                r.st.D[q] = (T *)r.st.D[q] + b.dpl * off;
+            }
+            r.st.R = (T *)r.st.R + b.pl * off;
+        }
+        m->G = Gnew;
+    }
     return NS3D_OK;
+}
+
+template <class T>
+int solve_deep(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, const ns3d_pt_params *p, const PtLoop &lp)
+{
+    int rc = deep_load<T>(m, Pr, D, divV, p, z_slabs(m) ? "ns3d_slab_load" : "ns3d_pt_solve_slab");
+    if (rc || (rc = deep_plan<T>(m))) return rc;
+    rc = check_loop(lp, [&](int n) { return deep_iterate<T>(m, n); }, [&](double *mx) { return deep_residual<T>(m, mx); });
+    return rc ? rc : deep_store<T>(m, Pr, D);
 }
 
 // {X_o .= X; advect!; update_halo!} (multi.jl:475-477) with a z halo of width TWO for the old fields — an option outside the
@@ -1895,7 +1725,7 @@ int ns3d_slab_iterate(ns3d_mgpu *m, int n_iters)
     CHECK_M(m);
     if (!m->loaded) return fail(NS3D_ERR_STATE, "ns3d_slab_iterate: no state loaded (ns3d_slab_load)");
     if (n_iters < 0) return fail(NS3D_ERR_ARG, "ns3d_slab_iterate: negative count");
-    int rc = m->esize == 8 ? slab_iterate<double>(m, n_iters) : slab_iterate<float>(m, n_iters);
+    int rc = m->esize == 8 ? deep_iterate<double>(m, n_iters) : deep_iterate<float>(m, n_iters);
     return rc ? rc : finish_m(m);
 }
 // the tile shape of the interior sweeps, measured now (ns3d_plan_pt on every local rank)
@@ -1903,7 +1733,7 @@ int ns3d_slab_plan(ns3d_mgpu *m)
 {
     CHECK_M(m);
     if (!m->loaded) return fail(NS3D_ERR_STATE, "ns3d_slab_plan: no state loaded (ns3d_slab_load)");
-    return m->esize == 8 ? slab_plan<double>(m) : slab_plan<float>(m);
+    return m->esize == 8 ? deep_plan<double>(m) : deep_plan<float>(m);
 }
 // max_g(maximum(abs.(Rp))) of the loaded state's current iterate (multi.jl:465-466,21)
 int ns3d_slab_residual(ns3d_mgpu *m, double *out)
@@ -1911,7 +1741,7 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
     CHECK_M(m);
     if (!m->loaded) return fail(NS3D_ERR_STATE, "ns3d_slab_residual: no state loaded (ns3d_slab_load)");
     if (!out) return fail(NS3D_ERR_ARG, "ns3d_slab_residual: null output");
-    return m->esize == 8 ? slab_residual<double>(m, out) : slab_residual<float>(m, out);
+    return m->esize == 8 ? deep_residual<double>(m, out) : deep_residual<float>(m, out);
 }
 
 } // extern "C"
@@ -1947,7 +1777,11 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
         CHECK_M(m);                                                                                          \
         if (!Pr || !dPrdtau || !divV) return fail(NS3D_ERR_ARG, "ns3d_slab_load: null field list");          \
         m->loaded = false;                                                                                   \
-        int rc = slab_load<T>(m, Pr, dPrdtau, divV, p);                                                      \
+        if (!z_slabs(m))                                                                                     \
+            return fail(NS3D_ERR_STATE, "the fused pseudo-transient path takes z-slab topologies only (dims = "  \
+                        "(1,1,P)); this grid is (%d,%d,%d): run the loop multi.jl:458-471 with the kernel entry "    \
+                        "points and ns3d_update_halo", m->dims[0], m->dims[1], m->dims[2]);                   \
+        int rc = deep_load<T>(m, Pr, dPrdtau, divV, p, "ns3d_slab_load");                                    \
         return rc ? rc : finish_m(m);                                                                        \
     }                                                                                                        \
     extern "C" int ns3d_slab_store_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau)                        \
@@ -1956,7 +1790,7 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
         if (!m->loaded || m->esize != (int)sizeof(T))                                                        \
             return fail(NS3D_ERR_STATE, "ns3d_slab_store: no state of this element type loaded");            \
         if (!Pr || !dPrdtau) return fail(NS3D_ERR_ARG, "ns3d_slab_store: null field list");                  \
-        int rc = slab_store<T>(m, Pr, dPrdtau);                                                              \
+        int rc = deep_store<T>(m, Pr, dPrdtau);                                                              \
         return rc ? rc : finish_m(m);                                                                        \
     }                                                                                                        \
     extern "C" int ns3d_pt_solve_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,\
@@ -1968,12 +1802,9 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
         if (!Pr || !dPrdtau || !divV) return fail(NS3D_ERR_ARG, "ns3d_pt_solve_slab: null field list");      \
         if (niter < 0 || nchk < 0) return fail(NS3D_ERR_ARG, "ns3d_pt_solve_slab: negative niter/nchk");     \
         m->loaded = false;                                                                                   \
-        int rc = z_slabs(m) ? solve_slab<T>(m, Pr, dPrdtau, divV, p, eps, niter, nchk, err_mul, err_div,     \
-                                            iters_done, err_hist, max_checks, n_checks)                      \
-                 : box_enabled(m, p) ? solve_box<T>(m, Pr, dPrdtau, divV, p, eps, niter, nchk, err_mul,      \
-                                                    err_div, iters_done, err_hist, max_checks, n_checks)     \
-                            : solve_cart<T>(m, Pr, dPrdtau, divV, p, eps, niter, nchk, err_mul, err_div,     \
-                                            iters_done, err_hist, max_checks, n_checks);                     \
+        const PtLoop lp{eps, niter, nchk, err_mul, err_div, iters_done, err_hist, max_checks, n_checks};    \
+        int rc = (z_slabs(m) || box_enabled(m, p)) ? solve_deep<T>(m, Pr, dPrdtau, divV, p, lp)              \
+                                                   : solve_cart<T>(m, Pr, dPrdtau, divV, p, lp);             \
         return rc ? rc : finish_m(m);                                                                        \
     }                                                                                                        \
     extern "C" int ns3d_poisson_direct_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,      \

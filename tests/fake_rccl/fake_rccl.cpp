@@ -4,7 +4,7 @@
 // nothing under navierstokes3d_amd/ knows it exists.
 //
 // Why: RCCL refuses two ranks on one device, and the builder's box has one GPU — so the one-process-per-GPU arm of the
-// multi-GPU layer (exchange_begin's send/recv group, gather_impl's send/recv, slab_plan's and the residual's all-reduce)
+// multi-GPU layer (exchange_begin's send/recv group, gather_impl's send/recv, deep_plan's and the residual's all-reduce)
 // would first run on the driver's 8-GPU node.  This library lets SEVERAL PROCESSES ON ONE GPU run that arm for real:
 // pairing, grouping, byte counts, in-order matching per peer, stream ordering and the all-reduce — everything but xGMI.
 //

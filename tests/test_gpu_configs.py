@@ -117,7 +117,7 @@ def test_config_E_eight_z_slabs_equal_global_poisson_solve(hip, n, nz_loc, dtype
 def test_default_topologies_of_init_global_grid_at_full_size(hip, dims, n):
     """What `init_global_grid(nx, ny, nz)` itself picks for 2 and 4 ranks — (2,1,1) and (2,2,1), never z-slabs — at configs[3]'s
     scale: two ranks of 514×512×512 (global 1026×512×512, 269 M cells) and four of 258×258×512.  ns3d_pt_solve_slab takes the
-    deep-ghost box path there (solve_box: three ghost cells per decomposed direction, four iterations per pass); after 9
+    deep-ghost box path there (solve_deep: three ghost cells per decomposed direction, four iterations per pass); after 9
     iterations (4+4+1) with a residual check every 4 the counts, the error history and every local array — halo cells
     included — equal ns3d_pt_solve on the global grid, compared on the device."""
     import torch

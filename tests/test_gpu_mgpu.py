@@ -267,7 +267,7 @@ def test_pt_solve_on_a_cartesian_topology_equals_global_pt_solve(hip, dims, dtyp
                                           ((2, 3, 1), (9, 6, 8), 4), ((1, 2, 2), (66, 12, 5), 4),
                                           ((2, 2, 1), (130, 70, 34), 4), ((1, 2, 2), (200, 40, 30), 3)])   # several tiles per box
 def test_deep_ghosts_on_a_cartesian_topology_equal_the_global_pt_solve(hip, dims, n, depth, dtype, monkeypatch):
-    """solve_box (ns3d_mgpu.cpp): the solve state of every rank in a box extended by depth−1 ghost cells in x, y and z, passes of
+    """solve_deep (ns3d_mgpu.cpp): the solve state of every rank in a box extended by depth−1 ghost cells in x, y and z, passes of
     up to `depth` iterations on the whole box, ghost layers exchanged dimension by dimension (x/y layers packed by k_subbox_copy).
     Same iteration count, error history and fields as ns3d_pt_solve on the global grid, bit for bit — with the planner's pass
     depth and with every depth forced; a thin dimension (6 cells: four own layers) caps the ghost depth; NS3D_CART_DEEP=0 takes

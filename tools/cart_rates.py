@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """PT loop of P virtual ranks on ONE GPU through the multi-GPU C ABI, by topology: z-slabs (deep-ghost passes), a Cartesian
-topology with deep ghosts in x, y and z (solve_box: passes of up to four iterations on the extended box), the same topology with
+topology with deep ghosts in x, y and z (solve_deep: passes of up to four iterations on the extended box), the same topology with
 one sweep + one halo update per iteration (NS3D_CART_DEEP=0) and kernel by kernel (multi.jl:458-471 as written).
 
     python tools/cart_rates.py [--local 130] [--iters 120] [--dims "1,1,8;2,2,2"]

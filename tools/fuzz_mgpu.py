@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised check of ns3d_pt_solve_slab on virtual ranks of ONE GPU against ns3d_pt_solve on the global grid, bit for bit:
-random topologies (z-slabs and Cartesian: solve_slab / solve_box / the depth-1 form), local extents, ghost depths, pinned pass
+random topologies (z-slabs and Cartesian: solve_deep / the depth-1 form), local extents, ghost depths, pinned pass
 depths, iteration counts, residual-check intervals, element types, outlet rule on / off.
 
     python tools/fuzz_mgpu.py [--cases 60] [--seed 1]
