@@ -11,9 +11,10 @@ must zero it to rounding, and the oracle's PT loop run to a tight tolerance must
 import numpy as np
 
 
-def eig1d(m, d, kind):
+def eig1d(m, d, kind, work=np.float64):
     """columns of V: orthonormal eigenvectors of the 1-D second difference on m interior cells; lam: eigenvalues.
-    kind 0: copies on both ends; 1: copy below, zero cell above; 2: zero cells on both ends."""
+    kind 0: copies on both ends; 1: copy below, zero cell above; 2: zero cells on both ends.
+    Built in long double and returned in the working precision `work`."""
     i = np.arange(m, dtype=np.longdouble)
     q = np.arange(m, dtype=np.longdouble)
     pi = np.longdouble(np.pi) if np.finfo(np.longdouble).eps >= 1e-16 else np.arccos(np.longdouble(-1))
@@ -30,17 +31,19 @@ def eig1d(m, d, kind):
     lam = -4 * np.sin(th / 2) ** 2 / (np.longdouble(d) ** 2)
     if kind == 0:
         lam[0] = 0
-    return V.astype(np.float64), lam.astype(np.float64)
+    return V.astype(work), lam.astype(work)
 
 
-def poisson_direct(divV, rho, dt, dx, dy, dz, bc_kind=0, owns_outlet=True, outlet_val=0.0, g=0.0):
-    """Returns Pr (nx,ny,nz) with the interior solved and the boundary cells of set_bc_Pr! (bc_kind 0: multi.jl, 1: gpu.jl)."""
+def poisson_direct(divV, rho, dt, dx, dy, dz, bc_kind=0, owns_outlet=True, outlet_val=0.0, g=0.0, work=np.float64):
+    """Returns Pr (nx,ny,nz) with the interior solved and the boundary cells of set_bc_Pr! (bc_kind 0: multi.jl, 1: gpu.jl).
+    `work` is the precision every array and every sum is carried in: np.float64 is the twin the HIP solve is compared with;
+    np.longdouble (80-bit where the host has it) measures that twin's own rounding level on a given grid."""
     nx, ny, nz = divV.shape
     mx, my, mz = nx - 2, ny - 2, nz - 2
-    F = (rho / dt) * np.asarray(divV[1:-1, 1:-1, 1:-1], dtype=np.float64).copy()
+    F = (rho / dt) * np.asarray(divV[1:-1, 1:-1, 1:-1], dtype=work).copy()
     hyd = None
     if bc_kind == 1:                                                   # gpu.jl:258-259, 1-based iz = plane + 1
-        hyd = np.array([(rho * g * ((nz - (k + 1)) + 0.5)) * dz for k in range(nz)])
+        hyd = np.array([(rho * g * ((nz - (k + 1)) + 0.5)) * dz for k in range(nz)], dtype=work)
         F[0, :, :] -= (hyd[1:-1] + 100.0)[None, :] / (dx * dx)
         F[-1, :, :] -= hyd[1:-1][None, :] / (dx * dx)
         xkind = 2
@@ -49,9 +52,9 @@ def poisson_direct(divV, rho, dt, dx, dy, dz, bc_kind=0, owns_outlet=True, outle
         xkind = 1
     else:
         xkind = 0
-    Vx, lx = eig1d(mx, dx, xkind)
-    Vy, ly = eig1d(my, dy, 0)
-    Vz, lz = eig1d(mz, dz, 0)
+    Vx, lx = eig1d(mx, dx, xkind, work)
+    Vy, ly = eig1d(my, dy, 0, work)
+    Vz, lz = eig1d(mz, dz, 0, work)
     U = np.einsum("ia,ijk->ajk", Vx, F)
     U = np.einsum("jb,ajk->abk", Vy, U)
     U = np.einsum("kc,abk->abc", Vz, U)
@@ -61,7 +64,7 @@ def poisson_direct(divV, rho, dt, dx, dy, dz, bc_kind=0, owns_outlet=True, outle
     U = np.einsum("kc,abc->abk", Vz, U)
     U = np.einsum("jb,abk->ajk", Vy, U)
     U = np.einsum("ia,ajk->ijk", Vx, U)
-    Pr = np.zeros((nx, ny, nz), order="F")
+    Pr = np.zeros((nx, ny, nz), dtype=work, order="F")
     Pr[1:-1, 1:-1, 1:-1] = U
     if bc_kind == 1:                                                   # gpu.jl:282-284: bc_y!, bc_z!, bc_xhydstatic!
         Pr[:, 0, :] = Pr[:, 1, :]; Pr[:, -1, :] = Pr[:, -2, :]

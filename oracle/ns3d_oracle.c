@@ -387,6 +387,13 @@ void FN(ns3d_ref_set_cylinder_local)(REAL *C, REAL *Vx, REAL *Vy, REAL *Vz, doub
 /* lerp(a,b,t) = b*t + a*(1-t)                                  multi.jl:211, gpu.jl:306 */
 static inline REAL lerp_(REAL a, REAL b, REAL t) { return b * t + a * (R(1) - t); }
 static inline int clampi(long v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
+/* clamp(floor(Int, t), lo, hi) of multi.jl:192-194 for a t that is already floored, with the clamp applied BEFORE the conversion.
+ * For every t whose conversion to an integer is defined this is clampi((long)t, lo, hi).  Beyond that range `(long)t` is undefined
+ * behaviour in C (x86 returns LONG_MIN for +1e295 and the clamp then picks lo, the wrong end) and floor(Int, t) throws
+ * InexactError in Julia; here the clamp is the one of unbounded integers — hi for +huge and +Inf, lo for −huge and −Inf — and lo
+ * for NaN, so that a run which follows the reference into its instability (velocities of 1e295 after an err = Inf exit) is
+ * reproducible at all. */
+static inline int clampf(REAL t, int lo, int hi) { return !(t >= (REAL)lo) ? lo : (t > (REAL)hi ? hi : (int)t); }
 static inline REAL fmod_(REAL a, REAL b) { return sizeof(REAL) == 4 ? (REAL)fmodf((float)a, (float)b) : (REAL)fmod((double)a, (double)b); }
 static inline REAL floor_(REAL a) { return sizeof(REAL) == 4 ? (REAL)floorf((float)a) : (REAL)floor((double)a); }
 
@@ -402,9 +409,9 @@ static inline void backtrack(REAL *A, const REAL *A_o, REAL vxc, REAL vyc, REAL 
 {
     REAL ddx = dt * vxc / dx, ddy = dt * vyc / dy, ddz = dt * vzc / dz;
     const int koff = g_koff, szg = g_nzg > 0 ? g_nzg + (sz - g_nz_local) : sz;
-    int ix1 = clampi((long)floor_(R(ix) - ddx), 1, sx);
-    int iy1 = clampi((long)floor_(R(iy) - ddy), 1, sy);
-    int iz1 = clampi((long)floor_(R(iz + koff) - ddz), 1, szg);
+    int ix1 = clampf(floor_(R(ix) - ddx), 1, sx);
+    int iy1 = clampf(floor_(R(iy) - ddy), 1, sy);
+    int iz1 = clampf(floor_(R(iz + koff) - ddz), 1, szg);
     int ix2 = clampi(ix1 + 1, 1, sx), iy2 = clampi(iy1 + 1, 1, sy), iz2 = clampi(iz1 + 1, 1, szg);
     iz1 = clampi(iz1 - koff, 1, sz); iz2 = clampi(iz2 - koff, 1, sz);
     /* δ = (δ>0) − (δ % 1): Julia `%` on floats is rem = C fmod (sign of the dividend) */

@@ -7,7 +7,9 @@ shape, 512×512×258 per rank = 1026 global (SURVEY.md §8d Config 4).  The rank
 configs[4] "1024³, 8×MI355X": its decomposition — eight z-slabs of 1024×1024×130, fp32 and fp64 — and the 512³ strong-scaling shape
 (eight of 512×512×66) run here as eight virtual ranks (round 4); its one-GPU point (1024³) is
 tests/test_gpu_pt.py::test_full_size_1024_cubed_properties.
-configs[1] (255×153×153) uncapped: one full second time step, 2 280 PT iterations, against the oracle."""
+configs[1] (255×153×153) uncapped: one full second time step, 2 280 PT iterations, against the oracle — STRICT bit for bit, and FAST
+(the mode bench.py runs on this grid) with identical counts.  The single-GPU script on the same grid, whole steps in Float32 and the
+literal 63×63×63 of configs[0] are in tests/test_gpu_reference_grid.py."""
 import numpy as np
 import pytest
 
@@ -194,7 +196,7 @@ def test_config_D_cylinder_chorin_steps_on_two_slabs(hip):
 def test_explicit_shape_entry_vs_oracle(hip, P):
     """The shape overrides (ny, nz, ly_lx, lz_lx) against the oracle driver with the same overrides: 48×30×(P·15+2), 2 steps
     (the second one runs the PT loop; a third step of this anisotropic grid blows up to 1e300 in the oracle as well, where
-    the out-of-range float→int conversions of backtrack! are undefined in C and an InexactError in Julia)."""
+    the out-of-range float→int conversions of backtrack! are an InexactError in Julia; the oracle clamps before it converts)."""
     from navierstokes3d_amd.driver import run_navierstokes3D
     from navierstokes3d_amd.mgpu import MgpuGrid, MultiGpu
     from oracle.driver_ref import run_navierstokes3D_ref
@@ -211,15 +213,34 @@ def test_explicit_shape_entry_vs_oracle(hip, P):
         assert np.array_equal(a, b), n
 
 
-def test_config_B_uncapped_second_step_vs_oracle(hip):
+@pytest.fixture(scope="module")
+def config_B_uncapped_ref():
+    from oracle.driver_ref import run_navierstokes3D_ref
+    return run_navierstokes3D_ref(nx=255, nt=2)
+
+
+def test_config_B_uncapped_second_step_vs_oracle(hip, config_B_uncapped_ref):
     """BASELINE.json configs[1] without a cap on the PT loop: 255×153×153, two time steps; the second one runs the full
     2 280 iterations to err < 1e-3.  Iteration counts, error history and all five returned fields bit-identical to the
     oracle (≈1 minute of CPU time for the oracle's 2 432 unfused iterations)."""
     from navierstokes3d_amd.driver import run_navierstokes3D
-    from oracle.driver_ref import run_navierstokes3D_ref
-    ref = run_navierstokes3D_ref(nx=255, nt=2)
+    ref = config_B_uncapped_ref
     out = run_navierstokes3D(nx=255, nt=2, mode="strict", return_info=True)
     assert out[-1].iters == ref[-1].iters == [152, 2280]
     assert out[-1].errs == ref[-1].errs
     for n, a, b in zip(NAMES, out[:5], ref[:5]):
         assert np.array_equal(a, b), n
+
+
+def test_config_B_uncapped_second_step_fast_mode(hip, config_B_uncapped_ref):
+    """FAST — what bench.py runs on this grid — with the loop left to stop by itself, on the same oracle run.  First, on the
+    reference's err history alone: no residual check lies within 1e-3 (relative) of ε (the nearest is 1.10592e-3, 10.6 % above),
+    so FAST's rounding cannot move the stop, and its counts must be the reference's."""
+    from navierstokes3d_amd.driver import run_navierstokes3D
+    from util import assert_fields_close, checks_inside_margin
+    ref = config_B_uncapped_ref
+    assert ref[-1].iters == [152, 2280]
+    assert checks_inside_margin(ref[-1].errs, ref[-1].params.eps) == []
+    out = run_navierstokes3D(nx=255, nt=2, mode="fast", return_info=True)
+    assert out[-1].iters == ref[-1].iters
+    assert_fields_close(out[:5], ref[:5])

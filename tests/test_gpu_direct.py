@@ -11,12 +11,50 @@ from util import fields, geometry, rel_l2
 pytestmark = pytest.mark.gpu
 
 
+REF_GRID = (255, 153, 153)            # what gpu.jl:44 and multi.jl's nx = 255 give: K = 253 and 151 in the six matrix products
+_twin_levels = {}
+
+
+def _fp64_bar(grid, bc, rhs, g):
+    """The fp64 bar on a grid whose sums are longer than the 129 terms the 1e-11 was set on: max(1e-11, 20 × the twin's own rounding
+    level), that level being rel-L2 between the float64 twin and the same computation carried in 80-bit long double.  The factor 20
+    allows for the GPU's different summation order (blocked MFMA accumulation against einsum's)."""
+    import warnings
+    from oracle.direct_ref import poisson_direct
+    if np.finfo(np.longdouble).eps >= 1e-18:
+        warnings.warn("np.longdouble is not an 80-bit float on this host: the twin's rounding level at %r is not derived; the fp64 "
+                      "bar stays 1e-11" % (grid,))
+        return 1e-11
+    if (grid, bc) not in _twin_levels:
+        a = (rhs, g["rho"], g["dt"], g["dx"], g["dy"], g["dz"], bc[0], bc[1], bc[2], g["g"])
+        lo, hi = poisson_direct(*a), poisson_direct(*a, work=np.longdouble)
+        _twin_levels[grid, bc] = float(np.sqrt(((lo - hi) ** 2).sum()) / np.sqrt((hi * hi).sum()))
+    print("twin rounding level at %r, rule %r: %.3e" % (grid, bc, _twin_levels[grid, bc]))
+    return max(1e-11, 20.0 * _twin_levels[grid, bc])
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("bc", [(0, True, 0.0), (0, True, 0.75), (0, False, 0.0), (1, False, 0.0)])
 @pytest.mark.parametrize("grid", [(17, 9, 6), (24, 15, 15), (70, 35, 21), (131, 66, 37)])
 def test_poisson_direct_against_the_numpy_twin_and_the_reference_residual(hip, oracle, grid, bc, dtype):
     """Every tile-edge case of k_gemm_f64 (extents below, at and above multiples of 16/32/64, K not a multiple of 4), the three
     x boundary rules, fp32 fields solved in fp64."""
+    _direct_against_the_twin(hip, oracle, grid, bc, dtype)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("bc", [(1, False, 0.0), (0, True, 0.75)])
+def test_poisson_direct_at_the_reference_grid(hip, oracle, bc, dtype):
+    """The same assertions at the reference's own 255×153×153 (K = 253 and 151 in the matrix products — multiples neither of the
+    MFMA K step 4 nor of a tile edge — and 38 000 rows), under the gpu.jl rule and the outlet rule.  Tolerances: the twin's own
+    rounding level at this size (float64 against long double, _fp64_bar), measured on the oracle, is 1.04e-15 under rule
+    (1, False, 0.0) and 2.77e-15 under (0, True, 0.75); 20 × that stays below 1e-11, so the fp64 bar is 1e-11 here as well.  The
+    fp32 rounding of the input alone (twin on rhs.astype(float32) against twin on rhs) moves the solution by 1.5e-11 and
+    6.6e-8: below 2e-6, which therefore stays.  (The long-double twin takes about half a minute per rule.)"""
+    _direct_against_the_twin(hip, oracle, REF_GRID, bc, dtype)
+
+
+def _direct_against_the_twin(hip, oracle, grid, bc, dtype):
     import torch
     from oracle.direct_ref import poisson_direct
     nx, ny, nz = grid
@@ -35,6 +73,17 @@ def test_poisson_direct_against_the_numpy_twin_and_the_reference_residual(hip, o
     torch.cuda.synchronize()
     got = hip.to_numpy(dP)
     tol = 1e-11 if dtype == np.float64 else 2e-6
+    if grid == REF_GRID and dtype == np.float64:
+        tol = _fp64_bar(grid, bc, rhs, g)
+    elif grid == REF_GRID:
+        # the bar 2e-6 holds as long as the fp32 rounding of the input alone stays below it (rhs here is exactly representable
+        # in fp32; the unrounded field of the same seed is its fp64 parent)
+        rhs64 = fields(nx, ny, nz, ["c"], 57, np.float64)[0]
+        assert np.array_equal(rhs64.astype(np.float32), rhs)
+        rounding = rel_l2(ref, poisson_direct(rhs64, g["rho"], g["dt"], g["dx"], g["dy"], g["dz"], bc_kind, owns, val, g["g"]))
+        print("fp32 input rounding at %r, rule %r: %.3e" % (grid, bc, rounding))
+        assert rounding < tol, rounding
+    print("rel-L2 against the twin at %r, rule %r, %s: %.3e (bar %.1e)" % (grid, bc, np.dtype(dtype).name, rel_l2(got, ref), tol))
     assert rel_l2(got, ref) < tol, rel_l2(got, ref)
     assert not hip.to_numpy(dD).any() and np.array_equal(hip.to_numpy(drhs), rhs)
     # boundary cells = what set_bc_Pr! makes of the interior (the oracle's restatement)
@@ -85,19 +134,58 @@ def test_driver_with_direct_pressure_equals_the_oracle_driver_with_the_same_opti
     """Whole runs with the inner loop replaced by the direct solve, product driver against oracle driver (NumPy twin): the
     pressure agrees to solver rounding, and the velocities with it (≤ 1e-9; the direct solves differ in summation order, every
     other kernel is bit-exact)."""
+    _direct_driver_against_the_oracle_driver(hip, script, 36 if script == "multi" else 20, 3 if script == "multi" else 2)
+
+
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_driver_with_direct_pressure_at_the_reference_grid(hip, script):
+    """Both scripts at their own 255×153×153, two steps: 1e-8 on the reference's err measure of the solution, and on the fields
+    1e-9 for multi.jl (measured: 2e-14).  gpu.jl's run does not admit 1e-9 at this size — not for any solver: the ORACLE driver with
+    its own twin carried in long double instead of float64 (a 1e-15 change of the pressure) ends its two steps 2.8e-5 (C), 1.5e-5
+    (Pr), 1.8e-5 / 3.6e-5 / 1.9e-5 (Vx / Vy / Vz) away from itself, because the reference's backtrack! rounds a departure point
+    to a cell and the rounding flips along whole lines beside the cylinder (21 475 cells of C move by up to 2.6e-3).  The bar is
+    therefore derived as the solve's own is (_fp64_bar): per field, max(1e-9, 20 × that level), the level measured here on the
+    oracle driver each time (about a minute of long-double sums)."""
+    levels = None
+    if script == "gpu":
+        import warnings
+        import oracle.direct_ref as D
+        from oracle.driver_ref import runme_ref
+        if np.finfo(np.longdouble).eps < 1e-18:
+            twin = D.poisson_direct
+            rf, _ = runme_ref(nx=255, nt=2, pressure="direct")
+            D.poisson_direct = lambda *a, **k: twin(*a, work=np.longdouble, **k).astype(np.float64)
+            try:
+                rl, _ = runme_ref(nx=255, nt=2, pressure="direct")
+            finally:
+                D.poisson_direct = twin
+            vnorm = max(np.sqrt(np.sum(np.asarray(rf[n], dtype=np.float64) ** 2)) for n in ("Vx", "Vy", "Vz"))
+            levels = {n: rel_l2(rl[n], rf[n], vnorm if n.startswith("V") else None) for n in ("C", "Pr", "Vx", "Vy", "Vz")}
+            print("the oracle driver's own rounding level (float64 twin against long-double twin):", levels)
+        else:
+            warnings.warn("np.longdouble is not an 80-bit float on this host: the oracle driver's own level is not derived; the "
+                          "bar stays 1e-9")
+    _direct_driver_against_the_oracle_driver(hip, script, 255, 2, levels)
+
+
+def _direct_driver_against_the_oracle_driver(hip, script, nx, nt, levels=None):
     from navierstokes3d_amd.driver import run_navierstokes3D, runme
     from oracle.driver_ref import run_navierstokes3D_ref, runme_ref
     if script == "multi":
-        out = run_navierstokes3D(nx=36, nt=3, mode="strict", pressure="direct", return_info=True)
-        ref = run_navierstokes3D_ref(nx=36, nt=3, pressure="direct")
+        out = run_navierstokes3D(nx=nx, nt=nt, mode="strict", pressure="direct", return_info=True)
+        ref = run_navierstokes3D_ref(nx=nx, nt=nt, pressure="direct")
         info, rinfo = out[-1], ref[-1]
         pairs = list(zip(("C", "Pr", "Vx", "Vy", "Vz"), out[:5], ref[:5]))
     else:
-        f, info = runme(nx=20, nt=2, mode="strict", pressure="direct")
-        rf, rinfo = runme_ref(nx=20, nt=2, pressure="direct")
+        f, info = runme(nx=nx, nt=nt, mode="strict", pressure="direct")
+        rf, rinfo = runme_ref(nx=nx, nt=nt, pressure="direct")
         pairs = [(n, hip.to_numpy(getattr(f, n)), rf[n]) for n in ("C", "Pr", "Vx", "Vy", "Vz")]
     assert info.iters == rinfo.iters == [0] * len(info.iters)
+    print("direct-solve err per step:", [e[0] for e in info.errs])
     assert all(e[0] < 1e-8 for e in info.errs)            # the reference's err measure (multi.jl:466) of the direct solution
     vnorm = max(np.sqrt(np.sum(np.asarray(b, dtype=np.float64) ** 2)) for n, a, b in pairs if n.startswith("V"))
     for n, a, b in pairs:
-        assert np.isfinite(a).all() and rel_l2(a, b, vnorm if n.startswith("V") else None) < 1e-9, (n, rel_l2(a, b))
+        bar = max(1e-9, 20.0 * levels[n]) if levels else 1e-9
+        e = rel_l2(a, b, vnorm if n.startswith("V") else None)
+        print("%s: %.3e (bar %.2e)" % (n, e, bar))
+        assert np.isfinite(a).all() and e < bar, (n, e, bar)
