@@ -174,7 +174,46 @@ typedef struct ns3d_step_params {
     int write_stress;           /* also run update_τ! into txx … tyz (the reference's state after its last step) */
 } ns3d_step_params;
 
+/* ns3d_diagnostics: what a run reports about itself, in ONE read-only pass over Vx, Vy, Vz, Pr, C where they live (nothing is
+ * stored into the fields, no full-size scratch).  Every quantity covers the part of the arrays this rank OWNS, so that P ranks
+ * count the global array exactly once: in a decomposed dimension an array of extent n+s (s = 0 cell-centred, 1 staggered)
+ * overlaps its neighbour by 2+s entries; at an interior seam (seam_lo / seam_hi) a rank leaves out its first 1+s entries on the
+ * low side and its last entry (the halo) on the high side — owned 0-based range [seam_lo ? 1+s : 0, seam_hi ? n+s-1 : n+s) —
+ * and physical ends are counted in full.
+ *   vmax[q]      maximum(abs.(Vx)) / Vy / Vz over the owned entries, NaN-propagating like ns3d_max_abs
+ *   div_max      max|∇V| over the interior cells (@inn(∇V): 1 ≤ i ≤ n−2 per direction, which partition the global interior whatever
+ *                the seam flags), ∇V formed on the fly with ns3d_update_divV's expression and arithmetic build; NaN-propagating
+ *   pr_min/max   over the owned cells, NaN-propagating               c_vol   Σ C·dx·dy·dz over the owned cells
+ *   ke           Σ ½ρ(u²+v²+w²)·dx·dy·dz over the owned cells, u = 0.5·(Vx[i,j,k]+Vx[i+1,j,k]) etc.; terms and sums in fp64
+ *   mom[q], n_masked[q]   Σ Vx (Vy, Vz) over the owned nodes set_cylinder!'s velocity test q < 1.0 selects at that field's own
+ *                stagger location — what the next set_cylinder! call zeroes — and their number; 0 unless `cylinder` is set
+ *                (1: the predicate of ns3d_set_cylinder, multi.jl:249-281; 2: ns3d_set_cylinder_local, gpu.jl:336-368)
+ *   nonfinite    1 if an owned entry of any of the five arrays is NaN or ±Inf.  ke and div_max read one entry beyond the owned
+ *                ones where a low side is a seam (the staggered entry 1 of Vx / Vy / Vz in that direction, which the lower
+ *                neighbour owns and reports): a NaN only there reaches this rank's ke / div_max without setting its flag —
+ *                with consistent halos the neighbour's flag and the global record carry it
+ * The sums are reduced in a fixed order (per thread down its planes, wave64 butterfly, one LDS slot per wave, per-workgroup
+ * partials in the context's scratch, a second small launch over the partials): two calls on the same input return the same
+ * bits.  fp32 fields are converted on load and reduced in fp64. */
+typedef struct ns3d_diag {
+    double vmax[3], div_max, pr_min, pr_max, ke, c_vol, mom[3];
+    long long n_masked[3];
+    int nonfinite;
+} ns3d_diag;
+typedef struct ns3d_diag_params {
+    int nx, ny, nz;
+    double dx, dy, dz, rho;
+    int seam_lo[3], seam_hi[3]; /* side is an interior seam (ignored by the mgpu form: set per rank inside) */
+    int cylinder;               /* 0 none | 1 multi.jl form | 2 gpu.jl form */
+    double a2, b2, ox, oy, sinb, cosb, xco_g, yco_g, zco_g, lx, ly, lz;
+} ns3d_diag_params;
+
 #define NS3D_DECL(T, S)                                                                                     \
+    /* The monitor above on one rank.  Pr or C may be NULL: pr_min / pr_max resp. c_vol then come back as NaN (and take no    \
+     * part in `nonfinite`).  Blocks for its read-back like ns3d_max_abs.  NS3D_ERR_ARG: null context / velocity / params /   \
+     * output, a grid below 3×3×3, a cylinder form other than 0, 1, 2. */                                    \
+    int ns3d_diagnostics_##S(ns3d_ctx *, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C,    \
+                             const ns3d_diag_params *p, ns3d_diag *out_host);                               \
     /* the whole step (above); iters_done / err_hist / n_checks as in ns3d_pt_solve */                          \
     int ns3d_time_step_##S(ns3d_ctx *, ns3d_step_fields *f, const ns3d_step_params *p, int *iters_done,        \
                            double *err_hist, int max_checks, int *n_checks);                                   \
@@ -424,7 +463,16 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out);
      * the x rule stay the same.  fp32 fields are solved in fp64.  NS3D_ERR_ARG: NS3D_BC_GPU, x/y-decomposed topologies, null \
      * pointers, local grids below 4×4×3. */                                                                \
     int ns3d_poisson_direct_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,   \
-                                     const ns3d_pt_params *p);
+                                     const ns3d_pt_params *p);                                              \
+    /* ns3d_diagnostics of the GLOBAL arrays on any topology (z-slabs or Cartesian dims): every local rank runs the monitor on \
+     * its own arrays with the seam flags of its coordinates (those of per_rank are ignored; per_rank[l] carries the rank's     \
+     * grid, spacings and cylinder origin xco_g …), out_local[l] (may be NULL) receives the rank's own record.  out_global:    \
+     * maxima, pr_min and nonfinite combined as ns3d_max_g does (NaN included), sums and counts added in rank order in the     \
+     * one-process form — out_local's sums add up to out_global's exactly in that order — and by an all-reduce in the          \
+     * one-process-per-GPU form (every process receives the global record).  Pr or C may be NULL (as a list).  Blocks. */      \
+    int ns3d_diagnostics_mgpu_##S(ns3d_mgpu *m, const T *const *Vx, const T *const *Vy, const T *const *Vz,  \
+                                  const T *const *Pr, const T *const *C, const ns3d_diag_params *per_rank,   \
+                                  ns3d_diag *out_global, ns3d_diag *out_local);
 NS3D_MGPU_DECL(double, f64)
 NS3D_MGPU_DECL(float, f32)
 #undef NS3D_MGPU_DECL

@@ -40,6 +40,7 @@ export @init_parallel_stencil, @parallel, @parallel_indices, @zeros, Data
 export update_τ!, predict_V!, set_cylinder!, update_∇V!, update_dPrdτ!, update_Pr!, compute_res!, correct_V!, advect!
 export bc_x!, bc_y!, bc_z!, bc_zV!, bc_xhydstatic!, bc_x_Vx!, bc_x_Pr!, bc_xVx!, bc_xVyz!
 export init_global_grid, finalize_global_grid, nx_g, ny_g, nz_g, x_g, y_g, z_g, update_halo!, gather!
+export diagnostics, Diag, DiagParams
 export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
 
 const libns3d = get(ENV, "NS3D_LIB", joinpath(@__DIR__, "..", "navierstokes3d_amd", "libns3d.so"))
@@ -306,6 +307,52 @@ function poisson_direct!(Pr, dPrdτ, ∇V, ρ, dt, dx, dy, dz; bc_kind = 0, owns
     p = Ref(PtParams(ρ, dt, 0.0, 0.0, dx, dy, dz, nx, ny, nz, bc_kind, owns_outlet ? 1 : 0, 0.0, g, 0, 0)); _sync()
     check(ccall((:ns3d_poisson_direct_f64, libns3d), Cint, (Ptr{Cvoid}, PF, PF, PF, Ref{PtParams}),
                 _ctx(), ptr(Pr), ptr(dPrdτ), ptr(∇V), p))
+end
+struct Diag                        # struct ns3d_diag (include/ns3d.h), field for field
+    vmax::NTuple{3,Cdouble}; div_max::Cdouble; pr_min::Cdouble; pr_max::Cdouble; ke::Cdouble; c_vol::Cdouble
+    mom::NTuple{3,Cdouble}; n_masked::NTuple{3,Clonglong}; nonfinite::Cint
+end
+struct DiagParams                  # struct ns3d_diag_params (include/ns3d.h), field for field
+    nx::Cint; ny::Cint; nz::Cint
+    dx::Cdouble; dy::Cdouble; dz::Cdouble; rho::Cdouble
+    seam_lo::NTuple{3,Cint}; seam_hi::NTuple{3,Cint}
+    cylinder::Cint
+    a2::Cdouble; b2::Cdouble; ox::Cdouble; oy::Cdouble; sinb::Cdouble; cosb::Cdouble
+    xco_g::Cdouble; yco_g::Cdouble; zco_g::Cdouble
+    lx::Cdouble; ly::Cdouble; lz::Cdouble
+end
+_diag_zero() = Ref(Diag((0.0, 0.0, 0.0), 0.0, 0.0, 0.0, 0.0, 0.0, (0.0, 0.0, 0.0), (0, 0, 0), 0))
+"""
+    diagnostics(Vx, Vy, Vz, Pr, C, ρ, dx, dy, dz; cylinder = nothing) -> Diag
+
+The flow monitor (`ns3d_diagnostics_f64`, or `ns3d_diagnostics_mgpu_f64` after `init_global_grid`: the record of the GLOBAL arrays,
+every rank counting the entries it owns): max|V| per direction, max|∇V|, min / max Pr, kinetic energy, Σ C·dV, a non-finite flag and —
+with `cylinder` = the scalars of the script's own `set_cylinder!` call after the four arrays (15 in multi.jl, 12 in gpu.jl) — the
+momentum that call is about to zero (`mom`, `n_masked`).  One read-only pass on the device; `Pr` / `C` may be `nothing`.
+"""
+function diagnostics(Vx, Vy, Vz, Pr, C, ρ, dx, dy, dz; cylinder = nothing)
+    nx, ny, nz = size(Vx, 1) - 1, size(Vx, 2), size(Vx, 3)
+    z3 = (Cint(0), Cint(0), Cint(0))
+    cyl = cylinder === nothing ? (0, ntuple(_ -> 0.0, 12)) :
+          length(cylinder) == 15 ? (1, Tuple(Float64.(cylinder[1:12]))) :
+          length(cylinder) == 12 ? (2, (Float64.(cylinder[1:6])..., 0.0, 0.0, 0.0, Float64.(cylinder[7:9])...)) :
+          error("diagnostics: cylinder takes set_cylinder!'s 15 (multi.jl) or 12 (gpu.jl) scalars")
+    p = Ref(DiagParams(nx, ny, nz, dx, dy, dz, ρ, z3, z3, cyl[1], cyl[2]...))
+    out = _diag_zero()
+    pr = Pr === nothing ? PF(C_NULL) : ptr(Pr)
+    c = C === nothing ? PF(C_NULL) : ptr(C)
+    _sync()
+    if MGPU[] == C_NULL
+        check(ccall((:ns3d_diagnostics_f64, libns3d), Cint, (Ptr{Cvoid}, PF, PF, PF, PF, PF, Ref{DiagParams}, Ref{Diag}),
+                    _ctx(), ptr(Vx), ptr(Vy), ptr(Vz), pr, c, p, out))
+    else
+        X_, Y_, Z_, P_, C_ = [ptr(Vx)], [ptr(Vy)], [ptr(Vz)], [pr], [c]
+        GC.@preserve X_ Y_ Z_ P_ C_ check(ccall((:ns3d_diagnostics_mgpu_f64, libns3d), Cint,
+                    (Ptr{Cvoid}, Ptr{PF}, Ptr{PF}, Ptr{PF}, Ptr{PF}, Ptr{PF}, Ref{DiagParams}, Ref{Diag}, Ptr{Diag}),
+                    MGPU[], X_, Y_, Z_, Pr === nothing ? Ptr{PF}(C_NULL) : pointer(P_), C === nothing ? Ptr{PF}(C_NULL) : pointer(C_),
+                    p, out, Ptr{Diag}(C_NULL)))
+    end
+    return out[]
 end
 mutable struct StepFields          # struct ns3d_step_fields (include/ns3d.h): device pointers, IN/OUT (the fused step swaps X and X_o)
     Pr::PF; dPrdtau::PF; divV::PF

@@ -159,6 +159,8 @@ void ns3d_destroy(ns3d_ctx *c)
         if (c->tune_ev[q]) (void)hipEventDestroy(c->tune_ev[q]);
     if (c->pingpong) (void)hipFree(c->pingpong);
     if (c->pingpong_d) (void)hipFree(c->pingpong_d);
+    if (c->diag_dev) (void)hipFree(c->diag_dev);
+    if (c->diag_host) (void)hipHostFree(c->diag_host);
     if (c->key_dev) (void)hipFree(c->key_dev);
     if (c->key_host) (void)hipHostFree(c->key_host);
     if (c->masked_stream) { (void)hipStreamSynchronize(c->masked_stream); (void)hipStreamDestroy(c->masked_stream); }
@@ -297,6 +299,54 @@ static int fetch_key(ns3d_ctx *c, hipStream_t s, double *out)
     std::memcpy(&v, c->key_host, sizeof v);
     *out = v;
     return NS3D_OK;
+}
+
+// ---- ns3d_diagnostics ------------------------------------------------------------------------------------------------
+int ns3d_diag_check(const ns3d_diag_params *p, const char *fn)
+{
+    if (!p) return fail(NS3D_ERR_ARG, "%s: null parameters", fn);
+    if (p->nx < 3 || p->ny < 3 || p->nz < 3)
+        return fail(NS3D_ERR_ARG, "%s: grid %dx%dx%d too small (need >= 3 per direction)", fn, p->nx, p->ny, p->nz);
+    if (p->cylinder < 0 || p->cylinder > 2) return fail(NS3D_ERR_ARG, "%s: cylinder form %d (0 none | 1 multi.jl | 2 gpu.jl)", fn, p->cylinder);
+    return NS3D_OK;
+}
+template <class T>
+int ns3d_diag_enqueue(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C, const ns3d_diag_params *p)
+{
+    const size_t need = NS3D_DIAG_RESULT_WORDS + (size_t)NS3D_DIAG_SLOTS * ns3d_diag_geometry(p->nx, p->ny, p->nz, nullptr);
+    if (!c->diag_host) HIPCHK(c, hipHostMalloc((void **)&c->diag_host, NS3D_DIAG_RESULT_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+    if (c->diag_words < need) {
+        if (c->diag_dev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->diag_dev); c->diag_dev = nullptr; c->diag_words = 0; }
+        HIPCHK(c, hipMalloc((void **)&c->diag_dev, need * sizeof(unsigned long long)));
+        c->diag_words = need;
+    }
+    hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, diagnostics<T>(c->stream, Vx, Vy, Vz, Pr, C, *p, c->diag_dev + NS3D_DIAG_RESULT_WORDS, c->diag_dev));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "diagnostics launch: %s", hipGetErrorString(e)); }
+    HIPCHK(c, hipMemcpyAsync(c->diag_host, c->diag_dev, NS3D_DIAG_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    return NS3D_OK;
+}
+template int ns3d_diag_enqueue<double>(ns3d_ctx *, const double *, const double *, const double *, const double *, const double *, const ns3d_diag_params *);
+template int ns3d_diag_enqueue<float>(ns3d_ctx *, const float *, const float *, const float *, const float *, const float *, const ns3d_diag_params *);
+static double diag_f64(unsigned long long w) { double v; std::memcpy(&v, &w, sizeof v); return v; }
+static double diag_unkey(unsigned long long k)      // inverse of ord_key (ns3d_kernels.hip); 0 = nothing was reduced
+{
+    if (k == ~0ull || k == 0ull) return NAN;
+    return diag_f64((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k);
+}
+void ns3d_diag_decode(const unsigned long long *w, const ns3d_diag_params *p, bool has_pr, bool has_c, ns3d_diag *out)
+{
+    const double dV = p->dx * p->dy * p->dz;
+    out->ke = diag_f64(w[0]) * (0.5 * p->rho * dV);
+    out->c_vol = has_c ? diag_f64(w[1]) * dV : NAN;
+    for (int q = 0; q < 3; ++q) {
+        out->mom[q] = diag_f64(w[2 + q]);
+        out->n_masked[q] = (long long)w[5 + q];
+        out->vmax[q] = diag_f64(w[8 + q]);          // abs_key: the bit pattern of a non-negative double, NaN = 0x7FF8…
+    }
+    out->div_max = diag_f64(w[11]);
+    out->pr_max = has_pr ? diag_unkey(w[12]) : NAN;
+    out->pr_min = has_pr ? -diag_unkey(w[13]) : NAN;
+    out->nonfinite = w[14] != 0ull;
 }
 
 // After a synchronisation of the stream the persist launches ran on: did a bounded wait expire in any of them since the last check?
@@ -1041,6 +1091,18 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
         hipError_t e = DISPATCH(c, max_abs_key<T>(c->stream, A, n, c->key_dev));                             \
         if (e != hipSuccess) return fail(NS3D_ERR_HIP, "max_abs launch: %s", hipGetErrorString(e));          \
         return fetch_key(c, c->stream, out_host);                                                                       \
+    }                                                                                                        \
+    extern "C" int ns3d_diagnostics_##S(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C, \
+                                        const ns3d_diag_params *p, ns3d_diag *out_host)                      \
+    {                                                                                                        \
+        CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, out_host);                                                      \
+        int rc = ns3d_diag_check(p, "ns3d_diagnostics");                                                     \
+        if (rc) return rc;                                                                                   \
+        rc = ns3d_diag_enqueue<T>(c, Vx, Vy, Vz, Pr, C, p);                                                  \
+        if (rc) return rc;                                                                                   \
+        HIPCHK(c, hipStreamSynchronize(c->stream));                                                          \
+        ns3d_diag_decode(c->diag_host, p, Pr != nullptr, C != nullptr, out_host);                            \
+        return NS3D_OK;                                                                                      \
     }                                                                                                        \
     extern "C" int ns3d_correct_V_##S(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *Pr, double dt, double rho,  \
                                       double dx, double dy, double dz, int nx, int ny, int nz)               \

@@ -45,6 +45,9 @@ struct ns3d_ctx {
     };
     std::vector<BlockGraph> graphs;
     ns3d_persist_state persist;             // k_pt_persist's exchange area
+    unsigned long long *diag_dev = nullptr;  // ns3d_diagnostics: NS3D_DIAG_RESULT_WORDS result / staging words, then the workgroups' partials
+    size_t diag_words = 0;
+    unsigned long long *diag_host = nullptr; // pinned mirror of the result / staging words
     void *direct_plan = nullptr;            // ns3d_direct.hip: eigenvector matrices and scratch of the direct Poisson solve
     void (*direct_free)(void *) = nullptr;
     void clear_graphs()
@@ -147,6 +150,13 @@ hipError_t ns3d_enqueue_face_copy(ns3d_ctx *c, hipStream_t s, T *A, T *buf, int 
 // up to NS3D_SUBBOX_MAX blocks between column-major arrays of different pitches in one launch (ns3d_launch.h: ns3d_subbox_batch)
 template <class T>
 hipError_t ns3d_enqueue_subbox_copy(ns3d_ctx *c, hipStream_t s, const ns3d_subbox_batch<T> &batch);
+
+// ns3d_diagnostics in pieces, for the multi-GPU layer: argument check; the two launches and the copy of the result words into
+// c->diag_host on the context's stream (no synchronisation); the record from those words once the stream has been synchronised
+int ns3d_diag_check(const ns3d_diag_params *p, const char *fn);
+template <class T>
+int ns3d_diag_enqueue(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C, const ns3d_diag_params *p);
+void ns3d_diag_decode(const unsigned long long *words, const ns3d_diag_params *p, bool has_pr, bool has_c, ns3d_diag *out);
 
 // ---- ns3d_direct.hip: the stages of the direct Poisson solve, shared by ns3d_poisson_direct (one rank) and ns3d_poisson_direct_slab
 // (z-slab ranks, ns3d_mgpu.cpp).  Fields in fp64 scratch, plane-major [k][i + mx·j] over a rank's mz interior planes unless said

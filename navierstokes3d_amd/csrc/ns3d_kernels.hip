@@ -926,15 +926,17 @@ __device__ __forceinline__ bool in_ellipse(T xq, T yq, T ox, T oy, T sinb, T cos
 // thread per column and chunk of planes evaluates them once and stores down its chunk where a flag is set — nearly every
 // thread leaves after the tests.  One thread per (i, j, k) cost 0.70 ms per call at 512³, twice per time step; 32 planes per
 // thread: 0.038 ms (NS3D_CYL_KZ=1 / 8 / 16 / 32 / 64: 0.695 / 0.099 / 0.056 / 0.038 / 0.037).
+// The four tests of set_cylinder! at column (i, j), 0 ≤ i ≤ nx, 0 ≤ j ≤ ny: bit 0 — C (q < 1.05 at the cell centre), bits 1, 2, 3 —
+// Vx, Vy, Vz (q < 1.0 at that field's own stagger location).  One body for k_set_cylinder and for the monitor k_diag, which
+// sums what the former is about to zero.
+#define NS3D_CYL_C 1u
+#define NS3D_CYL_X 2u
+#define NS3D_CYL_Y 4u
+#define NS3D_CYL_Z 8u
 template <class T>
-__global__ __launch_bounds__(256) void k_set_cylinder(T *__restrict__ C, T *__restrict__ Vx, T *__restrict__ Vy,
-                                                      T *__restrict__ Vz, T a2, T b2, T ox, T oy, T sinb, T cosb,
-                                                      int local_form, T xco, T yco, T lx, T ly, T dx, T dy, int nx,
-                                                      int ny, int nz, int kz)
+__device__ __forceinline__ unsigned cyl_flags(int i, int j, int nx, int ny, T a2, T b2, T ox, T oy, T sinb, T cosb, int local_form,
+                                              T xco, T yco, T lx, T ly, T dx, T dy)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int j = blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > nx || j > ny) return;
     T xc, yc, xv, yv;
     if (!local_form) {
         xc = xco + (T)i * dx; yc = yco + (T)j * dy;
@@ -947,7 +949,20 @@ __global__ __launch_bounds__(256) void k_set_cylinder(T *__restrict__ C, T *__re
     const bool fX = j < ny && in_ellipse<T>(xv, yc, ox, oy, sinb, cosb, a2, b2, (T)1.0);
     const bool fY = i < nx && in_ellipse<T>(xc, yv, ox, oy, sinb, cosb, a2, b2, (T)1.0);
     const bool fZ = i < nx && j < ny && in_ellipse<T>(xc, yc, ox, oy, sinb, cosb, a2, b2, (T)1.0);
-    if (!(fC | fX | fY | fZ)) return;
+    return (fC ? NS3D_CYL_C : 0u) | (fX ? NS3D_CYL_X : 0u) | (fY ? NS3D_CYL_Y : 0u) | (fZ ? NS3D_CYL_Z : 0u);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_set_cylinder(T *__restrict__ C, T *__restrict__ Vx, T *__restrict__ Vy,
+                                                      T *__restrict__ Vz, T a2, T b2, T ox, T oy, T sinb, T cosb,
+                                                      int local_form, T xco, T yco, T lx, T ly, T dx, T dy, int nx,
+                                                      int ny, int nz, int kz)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i > nx || j > ny) return;
+    const unsigned fl = cyl_flags<T>(i, j, nx, ny, a2, b2, ox, oy, sinb, cosb, local_form, xco, yco, lx, ly, dx, dy);
+    if (!fl) return;
+    const bool fC = fl & NS3D_CYL_C, fX = fl & NS3D_CYL_X, fY = fl & NS3D_CYL_Y, fZ = fl & NS3D_CYL_Z;
     const int k0 = blockIdx.z * kz, k1 = min(k0 + kz, nz + 1);
     for (int k = k0; k < k1; ++k) {
         if (k < nz) {
@@ -3958,6 +3973,209 @@ hipError_t residual_max_key(hipStream_t s, const T *Pr, const T *divV, const ns3
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// ns3d_diagnostics: the flow monitor.  One read-only pass over Vx, Vy, Vz, Pr, C; thread (i, j) of the (nx+1)×(ny+1) column range
+// marches kz planes of the nz+1 plane range like k_residual_max and keeps the Vz plane it has just read for the next cell plane
+// (∇V and w need Vz[k] and Vz[k+1]); the i+1 / j+1 neighbours of Vx / Vy are loads of their own that L1 / L2 serve.  Sums are
+// fp64 and combined in a FIXED order — per thread down its planes, wave64 butterfly, one LDS slot per wave, the four waves in
+// order, per-workgroup partials in global memory, k_diag_final over the partials — no float atomics anywhere, so two calls give
+// the same bits.  Maxima travel as monotone unsigned keys with NaN on top (abs_key / ord_key).
+// Longest chain of additions: kz + 6 + 3 in k_diag, ⌈workgroups/256⌉ + 6 + 3 in k_diag_final.
+// ---------------------------------------------------------------------------------------------------------
+// order-preserving image of a double: NaN → all ones, otherwise sign-magnitude turned into an unsigned order (never 0)
+__device__ __forceinline__ unsigned long long ord_key(double a)
+{
+    if (a != a) return ~0ull;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(a);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // a + b = b + a: every lane ends with the same bits
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// slot kinds of NS3D_DIAG_SLOTS: [0,5) fp64 sums, [5,8) integer sums, [8,15) key maxima
+__device__ __forceinline__ unsigned long long diag_combine(int slot, unsigned long long a, unsigned long long b)
+{
+    if (slot < 5) return (unsigned long long)__double_as_longlong(__longlong_as_double((long long)a) + __longlong_as_double((long long)b));
+    if (slot < 8) return a + b;
+    return a > b ? a : b;
+}
+template <class T>
+struct DiagArgs {
+    const T *Vx, *Vy, *Vz, *Pr, *C;
+    int nx, ny, nz, kz;
+    int own[3][2][2];       // [dimension][s][lo, hi): owned 0-based index range of an extent n+s
+    int cyl;                // 0 none | 1 multi.jl form | 2 gpu.jl form
+    T a2, b2, ox, oy, sinb, cosb, xco, yco, lx, ly, dx, dy;
+    Geo<T> g;
+    unsigned long long *part;
+    unsigned nblocks;
+};
+template <class T>
+__global__ __launch_bounds__(256) void k_diag(const DiagArgs<T> a)
+{
+    typedef unsigned long long u64;
+    const Geo<T> &g = a.g;
+    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y;
+    const int kb = blockIdx.z * a.kz, ke = min(kb + a.kz, nz + 1);
+    double s_ke = 0.0, s_c = 0.0, s_mx = 0.0, s_my = 0.0, s_mz = 0.0;
+    u64 n_x = 0, n_y = 0, n_z = 0, k_vx = 0, k_vy = 0, k_vz = 0, k_div = 0, k_pmax = 0, k_pmin = 0, bad = 0;
+    const u64 INF_KEY = 0x7FF0000000000000ull;      // abs_key of ±Inf; NaN sorts above
+    if (i <= nx && j <= ny) {
+        const bool cx = i < nx, cy = j < ny, cc = cx && cy;
+        const bool ox0 = i >= a.own[0][0][0] && i < a.own[0][0][1], ox1 = i >= a.own[0][1][0] && i < a.own[0][1][1];
+        const bool oy0 = j >= a.own[1][0][0] && j < a.own[1][0][1], oy1 = j >= a.own[1][1][0] && j < a.own[1][1][1];
+        const bool inn2 = i >= 1 && i <= nx - 2 && j >= 1 && j <= ny - 2;
+        const unsigned fl = a.cyl ? cyl_flags<T>(i, j, nx, ny, a.a2, a.b2, a.ox, a.oy, a.sinb, a.cosb, a.cyl == 2, a.xco, a.yco,
+                                                 a.lx, a.ly, a.dx, a.dy)
+                                  : 0u;
+        const bool mX = fl & NS3D_CYL_X, mY = fl & NS3D_CYL_Y, mZ = fl & NS3D_CYL_Z;
+        const idx_t pVx = (idx_t)(nx + 1) * ny, pVy = (idx_t)nx * (ny + 1), pC = (idx_t)nx * ny;
+        const idx_t oVx = (idx_t)i + (idx_t)(nx + 1) * j, oVy = (idx_t)i + (idx_t)nx * j, oC = oVy;
+        T vz = cc ? a.Vz[oC + pC * kb] : (T)0;
+        for (int k = kb; k < ke; ++k) {
+            T vz1 = (T)0;
+            if (k < nz) {
+                const bool oz0 = k >= a.own[2][0][0] && k < a.own[2][0][1];
+                T vx = (T)0, vy = (T)0;
+                if (cy) {                                   // node (i, j, k) of Vx
+                    vx = a.Vx[oVx + pVx * k];
+                    if (ox1 && oy0 && oz0) {
+                        const u64 u = abs_key((double)vx);
+                        k_vx = u > k_vx ? u : k_vx;
+                        bad |= (u64)(u >= INF_KEY);
+                        if (mX) { s_mx += (double)vx; ++n_x; }
+                    }
+                }
+                if (cx) {                                   // node (i, j, k) of Vy
+                    vy = a.Vy[oVy + pVy * k];
+                    if (ox0 && oy1 && oz0) {
+                        const u64 u = abs_key((double)vy);
+                        k_vy = u > k_vy ? u : k_vy;
+                        bad |= (u64)(u >= INF_KEY);
+                        if (mY) { s_my += (double)vy; ++n_y; }
+                    }
+                }
+                if (cc) {                                   // cell (i, j, k)
+                    const T vx1 = a.Vx[oVx + 1 + pVx * k], vy1 = a.Vy[oVy + nx + pVy * k];
+                    vz1 = a.Vz[oC + pC * (k + 1)];
+                    if (inn2 && k >= 1 && k <= nz - 2) {
+                        const T dVx = vx1 - vx, dVy = vy1 - vy, dVz = vz1 - vz;
+                        const T dv = (DIV_X(dVx) + DIV_Y(dVy)) + DIV_Z(dVz);    // @∇V()  multi.jl:15, as k_update_divV
+                        const u64 u = abs_key((double)dv);
+                        k_div = u > k_div ? u : k_div;
+                    }
+                    if (ox0 && oy0 && oz0) {
+                        const double uu = 0.5 * ((double)vx + (double)vx1), vv = 0.5 * ((double)vy + (double)vy1),
+                                     ww = 0.5 * ((double)vz + (double)vz1);
+                        s_ke += (uu * uu + vv * vv) + ww * ww;
+                        if (a.Pr) {
+                            const double pr = (double)a.Pr[oC + pC * k];
+                            const u64 u1 = ord_key(pr), u2 = ord_key(-pr);
+                            k_pmax = u1 > k_pmax ? u1 : k_pmax;
+                            k_pmin = u2 > k_pmin ? u2 : k_pmin;
+                            bad |= (u64)(abs_key(pr) >= INF_KEY);
+                        }
+                        if (a.C) {
+                            const double c = (double)a.C[oC + pC * k];
+                            s_c += c;
+                            bad |= (u64)(abs_key(c) >= INF_KEY);
+                        }
+                    }
+                }
+            }
+            if (cc) {                                       // node (i, j, k) of Vz, k ≤ nz
+                if (ox0 && oy0 && k >= a.own[2][1][0] && k < a.own[2][1][1]) {
+                    const u64 u = abs_key((double)vz);
+                    k_vz = u > k_vz ? u : k_vz;
+                    bad |= (u64)(u >= INF_KEY);
+                    if (mZ) { s_mz += (double)vz; ++n_z; }
+                }
+                vz = vz1;
+            }
+        }
+    }
+    __shared__ u64 wpart[NS3D_DIAG_SLOTS][4];
+    const int tid = threadIdx.x + 64 * threadIdx.y, w = tid >> 6;
+    u64 v[NS3D_DIAG_SLOTS];
+    v[0] = (u64)__double_as_longlong(wave_sum_f64(s_ke));
+    v[1] = (u64)__double_as_longlong(wave_sum_f64(s_c));
+    v[2] = (u64)__double_as_longlong(wave_sum_f64(s_mx));
+    v[3] = (u64)__double_as_longlong(wave_sum_f64(s_my));
+    v[4] = (u64)__double_as_longlong(wave_sum_f64(s_mz));
+    v[5] = wave_sum_u64(n_x); v[6] = wave_sum_u64(n_y); v[7] = wave_sum_u64(n_z);
+    v[8] = wave_max_u64(k_vx); v[9] = wave_max_u64(k_vy); v[10] = wave_max_u64(k_vz);
+    v[11] = wave_max_u64(k_div); v[12] = wave_max_u64(k_pmax); v[13] = wave_max_u64(k_pmin); v[14] = wave_max_u64(bad);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NS3D_DIAG_SLOTS; ++q) wpart[q][w] = v[q];
+    }
+    __syncthreads();
+    if (tid < NS3D_DIAG_SLOTS) {
+        u64 r = wpart[tid][0];
+        for (int q = 1; q < 4; ++q) r = diag_combine(tid, r, wpart[tid][q]);
+        const unsigned bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+        a.part[(size_t)tid * a.nblocks + bid] = r;
+    }
+}
+// one workgroup per slot: thread t combines partials t, t+256, … in order, then the butterfly, then the four waves in order
+__global__ __launch_bounds__(256) void k_diag_final(const unsigned long long *__restrict__ part, unsigned nblocks,
+                                                    unsigned long long *__restrict__ result)
+{
+    typedef unsigned long long u64;
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const u64 *p = part + (size_t)slot * nblocks;
+    u64 r = slot < 5 ? (u64)__double_as_longlong(0.0) : 0ull;
+    for (unsigned q = tid; q < nblocks; q += 256) r = diag_combine(slot, r, p[q]);
+    if (slot < 5) r = (u64)__double_as_longlong(wave_sum_f64(__longlong_as_double((long long)r)));
+    else if (slot < 8) r = wave_sum_u64(r);
+    else r = wave_max_u64(r);
+    __shared__ u64 wv[4];
+    if ((tid & 63) == 0) wv[tid >> 6] = r;
+    __syncthreads();
+    if (tid == 0) {
+        u64 t = wv[0];
+        for (int q = 1; q < 4; ++q) t = diag_combine(slot, t, wv[q]);
+        result[slot] = t;
+    }
+}
+template <class T>
+hipError_t diagnostics(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C, const ns3d_diag_params &p,
+                       unsigned long long *part, unsigned long long *result)
+{
+    DiagArgs<T> a;
+    a.Vx = Vx; a.Vy = Vy; a.Vz = Vz; a.Pr = Pr; a.C = C;
+    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
+    const int n[3] = {p.nx, p.ny, p.nz};
+    for (int d = 0; d < 3; ++d)
+        for (int st = 0; st < 2; ++st) {
+            a.own[d][st][0] = p.seam_lo[d] ? 1 + st : 0;
+            a.own[d][st][1] = p.seam_hi[d] ? n[d] + st - 1 : n[d] + st;
+        }
+    a.cyl = p.cylinder;
+    a.a2 = (T)p.a2; a.b2 = (T)p.b2; a.ox = (T)p.ox; a.oy = (T)p.oy; a.sinb = (T)p.sinb; a.cosb = (T)p.cosb;
+    a.xco = (T)p.xco_g; a.yco = (T)p.yco_g; a.lx = (T)p.lx; a.ly = (T)p.ly; a.dx = (T)p.dx; a.dy = (T)p.dy;
+    a.g = make_geo<T>(p.dx, p.dy, p.dz);
+    a.part = part;
+    a.nblocks = ns3d_diag_geometry(p.nx, p.ny, p.nz, &a.kz);
+    const dim3 blk(64, 4, 1);
+    const dim3 grd((unsigned)((p.nx + 1 + 63) / 64), (unsigned)((p.ny + 1 + 3) / 4), (unsigned)((p.nz + 1 + a.kz - 1) / a.kz));
+    hipLaunchKernelGGL(k_diag<T>, grd, blk, 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_diag_final, dim3(NS3D_DIAG_SLOTS), dim3(256), 0, s, part, a.nblocks, result);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Self-test of div_by_known against the hardware's IEEE division: n pseudo-random dividends per launch (random
 // significands over 120 binades — one in four over the whole guarded range and beyond it —, plus quotients planted next
 // to representable numbers and rounding midpoints).
@@ -4061,6 +4279,8 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
     template hipError_t pt_faces_region<T>(hipStream_t, T *, const ns3d_pt_params &, const int *, const int *, int); \
     template hipError_t residual_max_key<T>(hipStream_t, const T *, const T *, const ns3d_pt_params &,       \
                                             unsigned long long *);                                           \
+    template hipError_t diagnostics<T>(hipStream_t, const T *, const T *, const T *, const T *, const T *,   \
+                                       const ns3d_diag_params &, unsigned long long *, unsigned long long *); \
     template hipError_t divtest<T>(hipStream_t, double, long, unsigned long long, unsigned long long *);   \
     template hipError_t strip_inner<T>(hipStream_t, const T *, T *, int, int, int);                          \
     template hipError_t face_copy<T>(hipStream_t, T *, T *, int, int, int, int, int, int);                  \

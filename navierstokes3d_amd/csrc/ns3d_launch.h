@@ -58,6 +58,20 @@ struct ns3d_subbox_batch {
     }
 };
 
+// ns3d_diagnostics (k_diag): 64×4 columns per workgroup over the (nx+1)×(ny+1) column range, kz planes of the nz+1 plane range per
+// workgroup — 32, halved down to 8 while the launch has fewer than 2 048 workgroups.  Every workgroup leaves NS3D_DIAG_SLOTS 8-byte
+// partials ([slot][workgroup]); k_diag_final (one workgroup per slot) combines them into NS3D_DIAG_SLOTS result words.
+#define NS3D_DIAG_SLOTS 15      /* 0 ke, 1 c, 2-4 mom | 5-7 n_masked | 8-10 vmax keys, 11 div, 12 pr_max, 13 -pr_min, 14 nonfinite */
+#define NS3D_DIAG_RESULT_WORDS 32   /* result words, then a staging area for the all-reduce of the one-process-per-GPU form */
+inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
+{
+    const unsigned gx = (unsigned)(nx + 1 + 63) / 64, gy = (unsigned)(ny + 1 + 3) / 4;
+    int kz = 32;
+    while (kz > 8 && gx * gy * ((unsigned)(nz + 1 + kz - 1) / kz) < 2048u) kz /= 2;
+    if (kz_out) *kz_out = kz;
+    return gx * gy * ((unsigned)(nz + 1 + kz - 1) / kz);
+}
+
 #define NS3D_LAUNCHER_DECLS(NS)                                                                              \
     namespace NS {                                                                                           \
     template <class T>                                                                                       \
@@ -119,6 +133,10 @@ struct ns3d_subbox_batch {
     template <class T>                                                                                       \
     hipError_t residual_max_key(hipStream_t, const T *, const T *, const ns3d_pt_params &,                   \
                                 unsigned long long *key_dev);                                                \
+    /* part: NS3D_DIAG_SLOTS × ns3d_diag_geometry() words, result: NS3D_DIAG_SLOTS words (both on the device) */ \
+    template <class T>                                                                                       \
+    hipError_t diagnostics(hipStream_t, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C,     \
+                           const ns3d_diag_params &, unsigned long long *part, unsigned long long *result); \
     template <class T>                                                                                       \
     hipError_t divtest(hipStream_t, double d, long n, unsigned long long seed, unsigned long long *bad_dev); \
     template <class T>                                                                                       \

@@ -1458,6 +1458,74 @@ int gather_impl(ns3d_mgpu *m, const T *const *A, int sx, int sy, int sz, T *out_
     return NS3D_OK;
 }
 
+// ns3d_diagnostics on every local rank (seam flags from the rank's neighbours), then the global record: key maxima and sums in
+// rank order on the host (one-process form), or three all-reduces over the staging words of the rank's context (RCCL form)
+template <class T>
+int diag_mgpu(ns3d_mgpu *m, const T *const *Vx, const T *const *Vy, const T *const *Vz, const T *const *Pr, const T *const *C,
+              const ns3d_diag_params *per_rank, ns3d_diag *out_global, ns3d_diag *out_local)
+{
+    const int n = (int)m->loc.size();
+    std::vector<ns3d_diag_params> ps(per_rank, per_rank + n);
+    for (int l = 0; l < n; ++l) {
+        const MRank &r = m->loc[l];
+        for (int d = 0; d < 3; ++d) { ps[l].seam_lo[d] = r.nbr[d][0] >= 0; ps[l].seam_hi[d] = r.nbr[d][1] >= 0; }
+        int rc = ns3d_diag_check(&ps[l], "ns3d_diagnostics_mgpu");
+        if (rc) return rc;
+        if (!Vx[l] || !Vy[l] || !Vz[l] || (Pr && !Pr[l]) || (C && !C[l]))
+            return fail(NS3D_ERR_ARG, "ns3d_diagnostics_mgpu: null field pointer (local rank %d)", l);
+    }
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        int rc = ns3d_diag_enqueue<T>(r.ctx, Vx[l], Vy[l], Vz[l], Pr ? Pr[l] : nullptr, C ? C[l] : nullptr, &ps[l]);
+        if (rc) return rc;
+    }
+    unsigned long long gw[NS3D_DIAG_SLOTS] = {0};
+    ns3d_diag tot;
+    std::memset(&tot, 0, sizeof tot);
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        HIPCHK(0, hipStreamSynchronize(compute(r)));
+        ns3d_diag d;
+        ns3d_diag_decode(r.ctx->diag_host, &ps[l], Pr != nullptr, C != nullptr, &d);
+        if (out_local) out_local[l] = d;
+        for (int q = 8; q < NS3D_DIAG_SLOTS; ++q) gw[q] = std::max(gw[q], r.ctx->diag_host[q]);
+        if (l == 0) { tot.ke = d.ke; tot.c_vol = d.c_vol; } else { tot.ke += d.ke; tot.c_vol += d.c_vol; }
+        for (int q = 0; q < 3; ++q) {
+            if (l == 0) tot.mom[q] = d.mom[q]; else tot.mom[q] += d.mom[q];
+            tot.n_masked[q] += d.n_masked[q];
+        }
+    }
+    if (m->rccl) {
+        MRank &r = m->loc[0];
+        ns3d_device_guard g(r.device);
+        hipStream_t s = compute(r);
+        unsigned long long *hw = r.ctx->diag_host + 16, *dw = r.ctx->diag_dev + 16;
+        const double sums[5] = {tot.ke, tot.c_vol, tot.mom[0], tot.mom[1], tot.mom[2]};
+        std::memcpy(hw, sums, sizeof sums);
+        for (int q = 0; q < 3; ++q) hw[5 + q] = (unsigned long long)tot.n_masked[q];
+        for (int q = 8; q < NS3D_DIAG_SLOTS; ++q) hw[q] = gw[q];
+        HIPCHK(0, hipMemcpyAsync(dw, hw, NS3D_DIAG_SLOTS * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        NCCLCHK(g_rccl.AllReduce(dw, dw, 5, ncclFloat64, ncclSum, m->comm, s));
+        NCCLCHK(g_rccl.AllReduce(dw + 5, dw + 5, 3, ncclUint64, ncclSum, m->comm, s));
+        NCCLCHK(g_rccl.AllReduce(dw + 8, dw + 8, NS3D_DIAG_SLOTS - 8, ncclUint64, ncclMax, m->comm, s));
+        HIPCHK(0, hipMemcpyAsync(hw, dw, NS3D_DIAG_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(0, hipStreamSynchronize(s));
+        double back[5];
+        std::memcpy(back, hw, sizeof back);
+        tot.ke = back[0]; tot.c_vol = back[1];
+        for (int q = 0; q < 3; ++q) { tot.mom[q] = back[2 + q]; tot.n_masked[q] = (long long)hw[5 + q]; }
+        for (int q = 8; q < NS3D_DIAG_SLOTS; ++q) gw[q] = hw[q];
+    }
+    ns3d_diag glob;
+    ns3d_diag_decode(gw, &ps[0], Pr != nullptr, C != nullptr, &glob);      // the key words: maxima, pr_min, nonfinite
+    glob.ke = tot.ke; glob.c_vol = tot.c_vol;
+    for (int q = 0; q < 3; ++q) { glob.mom[q] = tot.mom[q]; glob.n_masked[q] = tot.n_masked[q]; }
+    *out_global = glob;
+    return NS3D_OK;
+}
+
 } // namespace
 
 #define CHECK_M(m)                                                                                          \
@@ -1806,6 +1874,14 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
         int rc = (z_slabs(m) || box_enabled(m, p)) ? solve_deep<T>(m, Pr, dPrdtau, divV, p, lp)              \
                                                    : solve_cart<T>(m, Pr, dPrdtau, divV, p, lp);             \
         return rc ? rc : finish_m(m);                                                                        \
+    }                                                                                                        \
+    extern "C" int ns3d_diagnostics_mgpu_##S(ns3d_mgpu *m, const T *const *Vx, const T *const *Vy, const T *const *Vz, \
+                                             const T *const *Pr, const T *const *C, const ns3d_diag_params *per_rank, \
+                                             ns3d_diag *out_global, ns3d_diag *out_local)                    \
+    {                                                                                                        \
+        CHECK_M(m);                                                                                          \
+        if (!Vx || !Vy || !Vz || !per_rank || !out_global) return fail(NS3D_ERR_ARG, "ns3d_diagnostics_mgpu: null argument"); \
+        return diag_mgpu<T>(m, Vx, Vy, Vz, Pr, C, per_rank, out_global, out_local);                          \
     }                                                                                                        \
     extern "C" int ns3d_poisson_direct_slab_##S(ns3d_mgpu *m, T *const *Pr, T *const *dPrdtau, const T *const *divV,      \
                                                  const ns3d_pt_params *p)                                     \

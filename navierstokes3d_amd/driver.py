@@ -72,6 +72,33 @@ def _save_frame(grid, fields_v, iframe):
         save_array("out_save/out_%s_v_%04d" % (name, iframe), A.astype(np.float32))
 
 
+def _diag_step_record(full, mom_predict, mom_correct, p):
+    """One entry of info.diag: the monitor's full set after the step's boundary rules, plus
+    courant[q] = dt·max|V_q|/d_q — a bound on every |δ| backtrack! forms in that direction, which averages those very values
+    (multi.jl:190-199) — and force[q] = ρ·dx·dy·dz/dt·(mom₁[q] + mom₂[q]): the momentum the two set_cylinder! calls of the step
+    (:452, :473 / gpu.jl:123, :139) remove from the fluid, per unit time — the force the fluid exerts on the body (drag, lift,
+    and z) as the masking method itself produces it (no surface integral)."""
+    rec = SimpleNamespace(**vars(full))
+    d3 = (p.dx, p.dy, p.dz)
+    rec.courant = tuple(p.dt * full.vmax[q] / d3[q] for q in range(3))
+    rec.mom_predict, rec.mom_correct = tuple(mom_predict), tuple(mom_correct)
+    rec.force = tuple(p.rho * p.dx * p.dy * p.dz / p.dt * (mom_predict[q] + mom_correct[q]) for q in range(3))
+    return rec
+
+
+def _check_wide_precondition(it, courant):
+    """ns3d_advect_wide reproduces the one-rank step only while |δz| < 2 cells; courant[2] bounds |δz|.  Anything that is not
+    below 2 — a NaN included — stops the run before it advects."""
+    if not courant[2] < 2.0:
+        raise L.Ns3dError("step %d: courant[2] = dt*max|Vz|/dz = %r is not below 2 — outside the precondition of "
+                          "wide_advect_halo (ns3d_advect_wide is exact only while |δz| < 2 cells); reduce dt" % (it, courant[2]))
+
+
+def _diag_line(rec):
+    return ("  diag: courant = %.3f %.3f %.3f, max|divV| = %.3e, Pr in [%.3e, %.3e], ke = %.6e, force = %.4e %.4e %.4e%s"
+            % (rec.courant + (rec.div_max, rec.pr_min, rec.pr_max, rec.ke) + rec.force + (", NON-FINITE" if rec.nonfinite else "",)))
+
+
 def pt_loop_reference(ctxs, grid, fs, ps, niter, do_print=False):
     """The inner loop exactly as written in multi.jl:458-471 (including its redundant halo updates); `fs`, `ps`, `ctxs`
     hold one entry per local rank."""
@@ -136,7 +163,7 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
-                       return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True):
+                       return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -150,7 +177,15 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     the solution in the reference's own measure (:466).
     wide_advect_halo=True (OUTSIDE the reference's multi-rank semantics; z-slabs on the C-ABI grid): :475-477 run as
     ns3d_advect_wide — old fields with a two-plane z halo, C's halo updated too — so that the P-rank run reproduces the one-rank
-    run of the same global grid bit for bit (the reference's backtrack! clamps to the local array)."""
+    run of the same global grid bit for bit (the reference's backtrack! clamps to the local array).
+    diagnostics=True: the flow monitor (ns3d_diagnostics, on the device) runs three times per step — before each of the two
+    set_cylinder! calls :452 and :473 for the momentum they are about to remove, and after :474's halo update for the full set —
+    and info.diag gets one record per step (_diag_step_record: the monitor's fields of the GLOBAL arrays, courant, force); with
+    do_print the root prints one line per step after the reference's.  The step then runs call by call: `one_call` is not used.
+    Fields, iteration counts and errs are those of the run without it, bit for bit.  With wide_advect_halo a step whose
+    courant[2] is not below 2 raises Ns3dError instead of advecting outside ns3d_advect_wide's precondition (|δz| < 2 cells; on
+    more than one rank only — on one rank wide_advect_halo has no effect and nothing is checked).
+    One rank or the C-ABI grid (mgpu.MgpuGrid), any topology."""
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -221,6 +256,19 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                             p.owns_outlet, 0.0, p.g)
     scratch = K.clone(fs[0].Pr) if (fused and P > 1 and mg is None and slab is None) else None
     info = SimpleNamespace(iters=[], errs=[], params=p)
+    monitor = None
+    if diagnostics:
+        if P > 1 and mg is None:
+            raise L.Ns3dError("diagnostics on %d ranks needs the C-ABI grid (mgpu.MgpuGrid)" % P)
+        info.diag = []
+        dps = [K.diag_params(nx, ny, nz, p.dx, p.dy, p.dz, p.rho, cylinder=cyl) for cyl in cyls]   # seam flags: set by the grid
+
+        def monitor(full):
+            """the monitor of the global arrays; full=False: velocities only (the masked momentum)"""
+            pr, cf = (col("Pr"), col("C")) if full else (None, None)
+            if mg is not None:
+                return grid.diagnostics(col("Vx"), col("Vy"), col("Vz"), pr, cf, dps)[0]
+            return K.diagnostics(fs[0].Vx, fs[0].Vy, fs[0].Vz, pr and pr[0], cf and cf[0], dps[0], ctx=ctxs[0])
     nsave = nvis = 10                                                                         # :330,332
     root = _is_root(grid)
     # :450's halo update of the normal stresses may only go with the stress arrays where the interior planes two ranks both compute
@@ -231,7 +279,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     # one rank, fused: the whole step :449-477 is ONE library call (ns3d_time_step: the same entry points, enqueued from C) — a step
     # of the 255×153×153 case with the direct pressure solve is otherwise mostly this loop's ≈40 calls
     step_params = None
-    if fused and one_call and P == 1 and getattr(grid, "mg", None) is None:
+    if fused and one_call and P == 1 and getattr(grid, "mg", None) is None and not diagnostics:
         q = ps[0]
         step_params = L.StepParams(script=L.NS3D_BC_MULTI, nx=nx, ny=ny, nz=nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau,
                                    damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz, eps=p.eps, niter=niter, nchk=p.nchk, err_mul=p.ly * p.ly,
@@ -280,6 +328,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             for f, c in zip(fs, ctxs):
                 K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
                             ctx=c)                                                            # :451
+        if monitor:
+            mom_predict = monitor(False).mom
         for f, c, cyl in zip(fs, ctxs, cyls):
             K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                                # :452
         grid.update_halo(col("C"), col("Vx"), col("Vy"), col("Vz"))                           # :453
@@ -319,11 +369,21 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             for q, e in enumerate(errs):
                 show((q + 1) * p.nchk, e)
         info.iters.append(done); info.errs.append(errs)
-        for f, c, cyl, q in zip(fs, ctxs, cyls, ps):
+        for f, c in zip(fs, ctxs):
             K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=c)          # :472
+        if monitor:
+            mom_correct = monitor(False).mom
+        for f, c, cyl, q in zip(fs, ctxs, cyls, ps):
             K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                                # :473
             K.set_bc_Vel_multi(f.Vx, f.Vy, f.Vz, q.owns_inlet, p.vin, ctx=c)                   # :474 → :157-166
         grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                     # :167
+        if monitor:
+            rec = _diag_step_record(monitor(True), mom_predict, mom_correct, p)
+            info.diag.append(rec)
+            if root and do_print:
+                print(_diag_line(rec))
+            if wide_advect_halo and P > 1:
+                _check_wide_precondition(it, rec.courant)
         if wide_advect_halo and P > 1:                                                         # :475-477, decomposition-independent
             if mg is None or not (dims[0] == 1 and dims[1] == 1):
                 raise L.Ns3dError("wide_advect_halo needs z-slab ranks on the C-ABI grid (mgpu.MgpuGrid)")
@@ -403,11 +463,15 @@ def _save_mat(path, f, p, step0):
 
 
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
-          faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True):
+          faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
+          diagnostics=False):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
-    every nvis = 10 steps)."""
+    every nvis = 10 steps).
+    diagnostics=True: as in run_navierstokes3D — the monitor before the set_cylinder! calls :123 and :139 and after :140, one
+    record per step in info.diag (gpu.jl's form of the cylinder test, its dx-for-dy quirk included), a line per step with
+    do_print; the step runs call by call (`one_call` is not used) and returns the same bits."""
     if device is None:
         device = torch.cuda.current_device()
     dev = torch.device("cuda", device)
@@ -434,7 +498,12 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         save_frame_gpu(host(), ny, nz, iframe)
         iframe += 1
     step_params = None
-    if fused and one_call:      # the whole step :121-142 as ONE library call (ns3d_time_step)
+    monitor = None
+    if diagnostics:
+        info.diag = []
+        dp = K.diag_params(nx, ny, nz, p.dx, p.dy, p.dz, p.rho, cylinder=cyl)
+        monitor = lambda full: K.diagnostics(f.Vx, f.Vy, f.Vz, f.Pr if full else None, f.C if full else None, dp, ctx=ctx)
+    if fused and one_call and not diagnostics:      # the whole step :121-142 as ONE library call (ns3d_time_step)
         step_params = L.StepParams(script=L.NS3D_BC_GPU, nx=nx, ny=ny, nz=nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau,
                                    damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz, eps=p.eps, niter=niter, nchk=p.nchk, err_mul=p.ly * p.ly,
                                    err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy, sinb=p.sinb, cosb=p.cosb, xco_g=0.0, yco_g=0.0,
@@ -465,6 +534,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)  # :121
             K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
                         ctx=ctx)                                                              # :122
+        if monitor:
+            mom_predict = monitor(False).mom
         K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                                  # :123
         K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=ctx)                    # :124
         if do_print:
@@ -492,8 +563,14 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
                 print("  #iter = %d, err = %1.3e" % ((q + 1) * p.nchk, e))                    # :134
         info.iters.append(done); info.errs.append(errs)
         K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=ctx)            # :138
+        if monitor:
+            mom_correct = monitor(False).mom
         K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                                  # :139
         K.set_bc_Vel_gpu(f.Vx, f.Vy, f.Vz, ctx=ctx)                                           # :140
+        if monitor:
+            info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
+            if do_print:
+                print(_diag_line(info.diag[-1]))
         if fused:
             _copy_advect_swap(f, p, faithful, ctx)                                            # :141-142 in one pass
         else:

@@ -296,6 +296,47 @@ def max_abs(A, ctx=None):
     return out.value
 
 
+def diag_params(nx, ny, nz, dx, dy, dz, rho, seam_lo=(0, 0, 0), seam_hi=(0, 0, 0), cylinder=None):
+    """lib.DiagParams for ns3d_diagnostics.  cylinder: None, or set_cylinder!'s scalars in the reference's own order —
+    15 values (a2,b2,ox,oy,sinβ,cosβ,xco_g,yco_g,zco_g,lx,ly,lz,dx,dy,dz: multi.jl:249) or 12 (…,cosβ,lx,ly,lz,dx,dy,dz: gpu.jl:336),
+    told apart by their number like set_cylinder's own arguments."""
+    dp = L.DiagParams(nx=int(nx), ny=int(ny), nz=int(nz), dx=dx, dy=dy, dz=dz, rho=rho)
+    dp.seam_lo[:] = [int(bool(q)) for q in seam_lo]
+    dp.seam_hi[:] = [int(bool(q)) for q in seam_hi]
+    if cylinder is not None:
+        cyl = tuple(float(q) for q in cylinder)
+        if len(cyl) == 15:
+            dp.cylinder = 1
+            dp.a2, dp.b2, dp.ox, dp.oy, dp.sinb, dp.cosb, dp.xco_g, dp.yco_g, dp.zco_g, dp.lx, dp.ly, dp.lz = cyl[:12]
+        elif len(cyl) == 12:
+            dp.cylinder = 2
+            dp.a2, dp.b2, dp.ox, dp.oy, dp.sinb, dp.cosb, dp.lx, dp.ly, dp.lz = cyl[:9]
+        else:
+            raise TypeError("diag_params: cylinder takes set_cylinder!'s 15 (multi.jl) or 12 (gpu.jl) scalars")
+    return dp
+
+
+def diag_record(d):
+    """lib.Diag → a namespace of Python values (vmax, mom, n_masked: tuples per direction)."""
+    from types import SimpleNamespace
+    return SimpleNamespace(vmax=tuple(d.vmax), div_max=d.div_max, pr_min=d.pr_min, pr_max=d.pr_max, ke=d.ke, c_vol=d.c_vol,
+                           mom=tuple(d.mom), n_masked=tuple(int(q) for q in d.n_masked), nonfinite=int(d.nonfinite))
+
+
+def diagnostics(Vx, Vy, Vz, Pr, Cf, dp, ctx=None):
+    """ns3d_diagnostics: the flow monitor — one read-only pass over the fields on the device (include/ns3d.h): max|V| per
+    direction, max|∇V|, min / max Pr, kinetic energy, Σ C·dV, the momentum set_cylinder! is about to remove and a non-finite flag,
+    over the entries this rank owns (dp.seam_lo / seam_hi).  Pr or Cf may be None (their entries come back NaN).  Blocks."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    if (dp.nx, dp.ny, dp.nz) != (nx, ny, nz):
+        raise L.Ns3dError("diagnostics: params grid %r differs from the fields' %r" % ((dp.nx, dp.ny, dp.nz), (nx, ny, nz)))
+    out = L.Diag()
+    opt = lambda t, n: None if t is None else _chk(t, (nx, ny, nz), n)
+    _ctx(ctx, Vx).call("diagnostics", Vx, _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
+                       _chk(Vz, (nx, ny, nz + 1), "Vz"), opt(Pr, "Pr"), opt(Cf, "C"), C.byref(dp), C.byref(out))
+    return diag_record(out)
+
+
 def correct_V(Vx, Vy, Vz, Pr, dt, rho, dx, dy, dz, ctx=None):
     """correct_V!  multi.jl:97-102 / gpu.jl:214-219"""
     nx, ny, nz = Pr.shape

@@ -45,6 +45,21 @@ class StepParams(C.Structure):
                 ("write_stress", C.c_int)]
 
 
+class Diag(C.Structure):
+    """struct ns3d_diag (include/ns3d.h): what ns3d_diagnostics returns."""
+    _fields_ = [("vmax", C.c_double * 3), ("div_max", C.c_double), ("pr_min", C.c_double), ("pr_max", C.c_double),
+                ("ke", C.c_double), ("c_vol", C.c_double), ("mom", C.c_double * 3), ("n_masked", C.c_longlong * 3),
+                ("nonfinite", C.c_int)]
+
+
+class DiagParams(C.Structure):
+    """struct ns3d_diag_params (include/ns3d.h)."""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int)] + \
+               [(n, C.c_double) for n in ("dx", "dy", "dz", "rho")] + \
+               [("seam_lo", C.c_int * 3), ("seam_hi", C.c_int * 3), ("cylinder", C.c_int)] + \
+               [(n, C.c_double) for n in ("a2", "b2", "ox", "oy", "sinb", "cosb", "xco_g", "yco_g", "zco_g", "lx", "ly", "lz")]
+
+
 _P, _D, _I, _L = C.c_void_p, C.c_double, C.c_int, C.c_long
 
 # name → argument ctypes after the leading ctx pointer (same for _f64 and _f32)
@@ -60,6 +75,7 @@ SIGNATURES = {
     "compute_res": [_P] * 3 + [_D] * 5 + [_I] * 3,
     "max_abs": [_P, _L, C.POINTER(_D)],
     "correct_V": [_P] * 4 + [_D] * 5 + [_I] * 3,
+    "diagnostics": [_P] * 5 + [C.POINTER(DiagParams), C.POINTER(Diag)],
     "bc_x": [_P] + [_I] * 3,
     "bc_y": [_P] + [_I] * 3,
     "bc_z": [_P] + [_I] * 3,
@@ -129,6 +145,7 @@ MGPU_SIGNATURES = {   # typed (_f64/_f32), after the leading ns3d_mgpu*
     "pt_solve_slab": [_PP, _PP, _PP, C.POINTER(PtParams), _D, _I, _I, _D, _D, C.POINTER(_I), C.POINTER(_D), _I,
                       C.POINTER(_I)],
     "poisson_direct_slab": [_PP, _PP, _PP, C.POINTER(PtParams)],
+    "diagnostics_mgpu": [_PP] * 5 + [C.POINTER(DiagParams), C.POINTER(Diag), C.POINTER(Diag)],
 }
 
 

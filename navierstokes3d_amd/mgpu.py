@@ -275,6 +275,22 @@ class MultiGpu:
         L.check(self._typed("poisson_direct_slab", ref)(self.handle, self._ptrs([Pr]), self._ptrs([dPrdtau]), self._ptrs([divV]),
                                                         C.byref(p)))
 
+    # ---- the flow monitor on every topology ----------------------------------------------------------------------
+    def diagnostics(self, Vx, Vy, Vz, Pr, Cf, dps):
+        """ns3d_diagnostics_mgpu: the monitor of the GLOBAL arrays (per-rank lists; dps: one lib.DiagParams per local rank, their
+        seam flags are set inside from the ranks' coordinates; Pr / Cf may be None).  Returns (global record, [local records])."""
+        self._follow_torch_streams()
+        ref = _as_list(Vx)[0]
+        dps = _as_list(dps)
+        if len(dps) != self.nlocal:
+            raise L.Ns3dError("expected one DiagParams per local rank (%d), got %d" % (self.nlocal, len(dps)))
+        arr = (L.DiagParams * self.nlocal)(*dps)
+        glob, loc = L.Diag(), (L.Diag * self.nlocal)()
+        opt = lambda f: None if f is None else self._ptrs([f])
+        L.check(self._typed("diagnostics_mgpu", ref)(self.handle, self._ptrs([Vx]), self._ptrs([Vy]), self._ptrs([Vz]), opt(Pr), opt(Cf),
+                                                     arr, C.byref(glob), loc))
+        return K.diag_record(glob), [K.diag_record(d) for d in loc]
+
 
 class MgpuGrid:
     """The driver-facing grid object (same surface as halo.ZSlabGrid) on top of a MultiGpu."""
@@ -316,6 +332,10 @@ class MgpuGrid:
 
     def max_g(self, local_max):
         return self.mg.max_g(local_max)
+
+    def diagnostics(self, Vx, Vy, Vz, Pr, Cf, dps):
+        """The monitor of the global arrays (MultiGpu.diagnostics): (global record, [local records])."""
+        return self.mg.diagnostics(Vx, Vy, Vz, Pr, Cf, dps)
 
     def gather_fields(self, A):
         return self.mg.gather(A)
