@@ -196,6 +196,12 @@ int ns3d_reserve_cus(ns3d_ctx *c, int n)
     HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     if (n < 0 || n > cus / 2) return fail(NS3D_ERR_ARG, "ns3d_reserve_cus: %d of %d compute units (0 … half the device)", n, cus);
     n = (n + 7) / 8 * 8;
+    if (n != c->reserved_cus && !c->graphs.empty()) {
+        // a captured block holds the z-chunking of the CU count it was captured for: it is captured again for the new one
+        if (c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->own_stream));
+        c->clear_graphs();
+    }
     if (c->masked_stream) {
         HIPCHK(c, hipStreamSynchronize(c->masked_stream));
         if (c->stream == c->masked_stream) c->stream = c->own_stream;
@@ -801,7 +807,7 @@ static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, T *
         // next (persist_failed below) redoes the block by launches
         T *dout = ddst;
         if (!dout && ensure_pingpong_d<T>(c, p, &dout) != NS3D_OK) return hipErrorOutOfMemory;
-        e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, n, &c->persist));
+        e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, n, &c->persist, (c->reserved_cus / 8) << 8));
         if (e == hipSuccess) {
             T *t = src; src = dst; dst = t;
             if (ddst) { t = dsrc; dsrc = ddst; ddst = t; }
@@ -885,9 +891,10 @@ static bool use_persist(const ns3d_ctx *c, const ns3d_pt_params *p)
         // where it was measured to win (profiles/r3_persist_ab.log): up to ≈170 000 cells, one workgroup across x
         if ((long long)p->nx * p->ny * p->nz > 170ll * 1000 || p->nx > 66) return false;
     }
-    const hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, *p, 2, nullptr));
+    const hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, *p, 2, nullptr,
+                                                                      (c->reserved_cus / 8) << 8));
     if (e != hipSuccess) (void)hipGetLastError();
-    return e == hipSuccess;                                         // the chip holds the whole grid at once
+    return e == hipSuccess;                                         // the CUs this context launches on hold the whole grid at once
 }
 template <class T>
 static bool use_graphs(const ns3d_ctx *c, const ns3d_pt_params *p, int nchk)
@@ -934,7 +941,8 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
         T *dout = ddst;
         if (!dout && (rc = ensure_pingpong_d<T>(c, p, &dout))) return rc;
         hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz,
-                                 pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, niter, &c->persist, nchk, eps, err_mul, err_div));
+                                 pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, niter, &c->persist, (c->reserved_cus / 8) << 8, nchk, eps,
+                                               err_mul, err_div));
         if (e == hipSuccess) {
             HIPCHK(c, hipStreamSynchronize(s));
             if (!persist_failed(c)) {

@@ -3820,7 +3820,9 @@ static hipError_t pt_persist_shape(hipStream_t s, const SweepArgs<T> &a, int n_i
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_pt_persist<T, BY, BZ>, 64 * BY * BZ, 0) != hipSuccess) { (void)hipGetLastError(); n = 1; }
         return max(1, min(2, min(n, workgroups_per_cu((const void *)k_pt_persist<T, BY, BZ>, 64 * BY * BZ))));
     }();
-    if (blocks > (long)device_cus() * per_cu) return hipErrorInvalidValue;
+    // the CUs the stream's mask leaves (ns3d_reserve_cus), as the sweeps count them: a grid sized for the whole chip would not be resident
+    // together on the rest, and its hand-overs would run into the bounded waits
+    if (blocks > (long)max(8, device_cus() - a.cus_off) * per_cu) return hipErrorInvalidValue;
     if (!ps) return hipSuccess;                          // probe: the form applies
     hipError_t e = persist_scratch(ps, s, (size_t)blocks * R * FACE * 2 * sizeof(unsigned long long));
     if (e != hipSuccess) return e;
@@ -3871,7 +3873,7 @@ static hipError_t pt_persist_shape(hipStream_t s, const SweepArgs<T> &a, int n_i
 
 template <class T>
 hipError_t pt_persist(hipStream_t s, const T *Pin, T *Pout, const T *Din, T *Dout, const T *RHS, const ns3d_pt_params &p, int n_iters,
-                      ns3d_persist_state *st, int nchk, double eps, double err_mul, double err_div)
+                      ns3d_persist_state *st, int pass_flags, int nchk, double eps, double err_mul, double err_div)
 {
     if (n_iters < 1 || n_iters > 60000 || p.z_lo_is_halo || p.z_hi_is_halo) return hipErrorInvalidValue;
     SweepArgs<T> a;
@@ -3881,7 +3883,8 @@ hipError_t pt_persist(hipStream_t s, const T *Pin, T *Pout, const T *Din, T *Dou
     a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
     a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
     a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = 0; a.zhi_halo = 0;
-    a.k0 = 1; a.k1 = p.nz - 1; a.kz = 1; a.no_faces = 0; a.cus_off = 0; a.win = nullptr; a.tx0 = a.ty0 = 0;
+    a.k0 = 1; a.k1 = p.nz - 1; a.kz = 1; a.no_faces = 0; a.win = nullptr; a.tx0 = a.ty0 = 0;
+    a.cus_off = ((pass_flags >> 8) & 0xff) * 8;
     // the iteration is arithmetic on the CUs the grid occupies plus one hand-over: the smallest workgroup the chip still holds
     // all at once spreads the cells over the most CUs.  NS3D_PERSIST_SHAPE=22|42|44 pins a shape (A/B).
     static const int pin = std::getenv("NS3D_PERSIST_SHAPE") ? std::atoi(std::getenv("NS3D_PERSIST_SHAPE")) : 0;
@@ -4271,7 +4274,7 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
     template hipError_t pt_sweep<T>(hipStream_t, int, const T *, T *, T *, const T *, const ns3d_pt_params &,\
                                     int, int);                                                               \
     template hipError_t pt_persist<T>(hipStream_t, const T *, T *, const T *, T *, const T *, const ns3d_pt_params &, int, ns3d_persist_state *, \
-                                      int, double, double, double);                                             \
+                                      int, int, double, double, double);                                        \
     template hipError_t pt_sweep2<T>(hipStream_t, int, const T *, T *, const T *, T *, const T *,            \
                                      const ns3d_pt_params &, int, int, int, const ns3d_tile_window *);       \
     template hipError_t pt_sweepn<T>(hipStream_t, int, int, const T *, T *, const T *, T *, const T *,       \

@@ -116,10 +116,11 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
     template <class T>                                                                                       \
     hipError_t predict_fused(hipStream_t, T *, T *, T *, const T *, const T *, const T *, double mu, double rho, \
                              double g, double dt, double dx, double dy, double dz, int, int, int);           \
+    /* pass_flags: bits 8… = compute units the launch must not count on, in eights (as pt_sweep2 / pt_sweepn take them) */ \
     template <class T>                                                                                       \
     hipError_t pt_persist(hipStream_t, const T *, T *, const T *, T *, const T *, const ns3d_pt_params &,    \
-                          int n_iters, ns3d_persist_state *, int nchk = 0, double eps = -1.0, double err_mul = 1.0,   \
-                          double err_div = 1.0);                                                              \
+                          int n_iters, ns3d_persist_state *, int pass_flags, int nchk = 0, double eps = -1.0,\
+                          double err_mul = 1.0, double err_div = 1.0);                                        \
     template <class T>                                                                                       \
     hipError_t pt_sweep2(hipStream_t, int variant, const T *, T *, const T *, T *, const T *,                \
                          const ns3d_pt_params &, int k0, int k1, int pass_flags, const ns3d_tile_window *win = nullptr); \

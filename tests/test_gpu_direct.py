@@ -33,12 +33,24 @@ def _fp64_bar(grid, bc, rhs, g):
     return max(1e-11, 20.0 * _twin_levels[grid, bc])
 
 
+# thin and mixed extents: gemm() takes the LDS-staged MFMA kernel with its fused epilogues for M ≥ 32 and N ≥ 16 and the register-only
+# k_gemm_f64 followed by k_direct_scale / k_direct_scatter otherwise, so a grid with one short extent mixes the two within one solve
+MIXED_GRIDS = [(70, 35, 12),    # z products on the register kernel at M = 2244, k_direct_scale beside LDS x / y products, fused scatter
+               (70, 12, 40),    # y products on the register kernel, batched
+               (20, 40, 40),    # x products on the register kernel with N = 1444, k_direct_scatter; z on the LDS kernel, e_mx = 18
+               (34, 18, 18),    # M = 32 and N = 16 exactly
+               (33, 17, 17),    # one below both thresholds
+               (6, 70, 5),      # mx = 4, mz = 3
+               (4, 4, 4)]       # the documented minimum
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("bc", [(0, True, 0.0), (0, True, 0.75), (0, False, 0.0), (1, False, 0.0)])
-@pytest.mark.parametrize("grid", [(17, 9, 6), (24, 15, 15), (70, 35, 21), (131, 66, 37)])
+@pytest.mark.parametrize("grid", [(17, 9, 6), (24, 15, 15), (70, 35, 21), (131, 66, 37)] + MIXED_GRIDS)
 def test_poisson_direct_against_the_numpy_twin_and_the_reference_residual(hip, oracle, grid, bc, dtype):
     """Every tile-edge case of k_gemm_f64 (extents below, at and above multiples of 16/32/64, K not a multiple of 4), the three
-    x boundary rules, fp32 fields solved in fp64."""
+    x boundary rules, fp32 fields solved in fp64; thin channels whose products split between the two GEMM kernels (MIXED_GRIDS: sums
+    of at most 68 terms, shorter than the 129 the bars 1e-11 / 2e-6 were set on)."""
     _direct_against_the_twin(hip, oracle, grid, bc, dtype)
 
 

@@ -78,7 +78,9 @@ def _slab_direct(hip, mg, rhs, g, n, owns, val, seed=3):
     return Ps, Ds, Rs, p
 
 
-CASES = [(2, (17, 9, 6)), (3, (24, 15, 7)), (4, (70, 35, 8)), (2, (131, 66, 37)), (3, (20, 4, 6)), (4, (24, 15, 7))]
+CASES = [(2, (17, 9, 6)), (3, (24, 15, 7)), (4, (70, 35, 8)), (2, (131, 66, 37)), (3, (20, 4, 6)), (4, (24, 15, 7)),
+         (3, (70, 50, 8)),      # my = 48: 16 y columns per rank — the z products on the LDS-staged kernel at N = 16, with a column offset
+         (2, (70, 34, 8))]      # my = 32: 16 columns per rank on two ranks
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
