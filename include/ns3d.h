@@ -208,7 +208,46 @@ typedef struct ns3d_diag_params {
     double a2, b2, ox, oy, sinb, cosb, xco_g, yco_g, zco_g, lx, ly, lz;
 } ns3d_diag_params;
 
+/* Running statistics: the companion of the monitor above — that one gives the time series, this one the time-averaged FIELDS
+ * (mean velocity and pressure, the Reynolds stresses u'u' … v'w', the pressure variance).  The caller owns the state S: a `double`
+ * device array of NS3D_STATS_SLOTS consecutive column-major blocks of extent (nx,ny,nz), one per slot below, fp64 whatever the
+ * element type of the fields.  The cell-centred values are those of the monitor's kinetic energy,
+ *     u = 0.5·(Vx[i,j,k] + Vx[i+1,j,k])   v = 0.5·(Vy[i,j,k] + Vy[i,j+1,k])   w = 0.5·(Vz[i,j,k] + Vz[i,j,k+1])   p = Pr[i,j,k]
+ * (fp32 fields are converted on load, everything after that is fp64).  EVERY cell of the local array is accumulated, halo and
+ * boundary cells included: a rank's S has the shape of a cell-centred field, and ns3d_gather_f64 assembles the global,
+ * halo-stripped statistics of a multi-rank run unchanged.  There is no ns3d_mgpu form: a multi-rank caller makes the calls below
+ * on the context of each local rank (ns3d_mgpu_ctx), like every once-per-step kernel, and gathers the blocks of `mean` / `rs`.
+ * Read-only with respect to the flow. */
+enum {
+    NS3D_STATS_U = 0,
+    NS3D_STATS_V = 1,
+    NS3D_STATS_W = 2,
+    NS3D_STATS_P = 3,
+    NS3D_STATS_UU = 4,
+    NS3D_STATS_VV = 5,
+    NS3D_STATS_WW = 6,
+    NS3D_STATS_UV = 7,
+    NS3D_STATS_UW = 8,
+    NS3D_STATS_VW = 9,
+    NS3D_STATS_PP = 10,
+    NS3D_STATS_SLOTS = 11
+};
+/* S = 0 (all NS3D_STATS_SLOTS blocks) on the context's stream. */
+int ns3d_stats_reset(ns3d_ctx *, double *S, int nx, int ny, int nz);
+/* From sums to statistics: `mean` receives 4 blocks S[q]/wsum (q = U, V, W, P), `rs` — 7 blocks, may be NULL — the blocks
+ * S[UU … VW]/wsum − ā·b̄ of the six velocity pairs in slot order, then S[PP]/wsum − p̄·p̄ (ā, b̄, p̄: the entries of `mean`).  The
+ * division is the plain IEEE quotient; product and subtraction are not contracted in STRICT.  wsum is the sum of the weights
+ * accumulated so far.  NS3D_ERR_ARG: null context / S / mean, a grid below 3×3×3, wsum not finite or not greater than 0. */
+int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, double *rs, int nx, int ny, int nz);
+
 #define NS3D_DECL(T, S)                                                                                     \
+    /* One sample: per cell and slot S = S + weight·term, term = u, v, w, p, u·u, v·v, w·w, u·v, u·w, v·w, p·p evaluated in   \
+     * exactly that written order (STRICT: no contraction — the bits of the same NumPy expression; FAST may contract).  One   \
+     * pass that reads the four fields once and updates the accumulators in place.  Pr may be NULL: the slots P and PP are    \
+     * then neither read nor written.  Enqueued on the context's stream, no read-back (blocks only as every call does          \
+     * without NS3D_ASYNC).  NS3D_ERR_ARG: null context / S / velocity, a grid below 3×3×3, a weight that is not finite. */    \
+    int ns3d_stats_accumulate_##S(ns3d_ctx *, double *S_, const T *Vx, const T *Vy, const T *Vz, const T *Pr,  \
+                                  double weight, int nx, int ny, int nz);                                    \
     /* The monitor above on one rank.  Pr or C may be NULL: pr_min / pr_max resp. c_vol then come back as NaN (and take no    \
      * part in `nonfinite`).  Blocks for its read-back like ns3d_max_abs.  NS3D_ERR_ARG: null context / velocity / params /   \
      * output, a grid below 3×3×3, a cylinder form other than 0, 1, 2. */                                    \

@@ -41,6 +41,7 @@ export update_τ!, predict_V!, set_cylinder!, update_∇V!, update_dPrdτ!, upda
 export bc_x!, bc_y!, bc_z!, bc_zV!, bc_xhydstatic!, bc_x_Vx!, bc_x_Pr!, bc_xVx!, bc_xVyz!
 export init_global_grid, finalize_global_grid, nx_g, ny_g, nz_g, x_g, y_g, z_g, update_halo!, gather!
 export diagnostics, Diag, DiagParams
+export stats_zeros, stats_reset!, stats_accumulate!, stats_finalize
 export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
 
 const libns3d = get(ENV, "NS3D_LIB", joinpath(@__DIR__, "..", "navierstokes3d_amd", "libns3d.so"))
@@ -353,6 +354,35 @@ function diagnostics(Vx, Vy, Vz, Pr, C, ρ, dx, dy, dz; cylinder = nothing)
                     p, out, Ptr{Diag}(C_NULL)))
     end
     return out[]
+end
+# ---- running statistics (ns3d_stats_*): time-averaged fields, accumulated where the flow lives ---------------------
+const NS3D_STATS_SLOTS = 11        # u v w p uu vv ww uv uw vw pp (enum NS3D_STATS_* of include/ns3d.h)
+"The state S for fields of Pr's shape: NS3D_STATS_SLOTS blocks of (nx,ny,nz) Float64, zero."
+stats_zeros(Pr) = AMDGPU.zeros(Float64, size(Pr, 1), size(Pr, 2), size(Pr, 3) * NS3D_STATS_SLOTS)
+function stats_reset!(S, Pr)
+    nx, ny, nz = _cint3(Pr); _sync()
+    check(ccall((:ns3d_stats_reset, libns3d), Cint, (Ptr{Cvoid}, PF, Cint, Cint, Cint), _ctx(), ptr(S), nx, ny, nz))
+end
+"""
+    stats_accumulate!(S, Vx, Vy, Vz, Pr; weight = 1.0)
+
+One sample: S .+= weight .* (u, v, w, p, u², v², w², uv, uw, vw, p²) of the cell-centred values, one pass on the device
+(`ns3d_stats_accumulate_f64`).  `Pr` may be `nothing` (slots p and pp are left alone).  After `init_global_grid` call it on every
+rank as it stands: every rank accumulates its own local array, `gather!` assembles the blocks of `stats_finalize`.
+"""
+function stats_accumulate!(S, Vx, Vy, Vz, Pr; weight = 1.0)
+    nx, ny, nz = Cint(size(Vx, 1) - 1), Cint(size(Vx, 2)), Cint(size(Vx, 3)); _sync()
+    check(ccall((:ns3d_stats_accumulate_f64, libns3d), Cint, (Ptr{Cvoid}, PF, PF, PF, PF, PF, Cdouble, Cint, Cint, Cint),
+                _ctx(), ptr(S), ptr(Vx), ptr(Vy), ptr(Vz), Pr === nothing ? PF(C_NULL) : ptr(Pr), weight, nx, ny, nz))
+end
+"(mean, rs): 4 blocks S[u,v,w,p]/wsum and 7 blocks S[uu…vw,pp]/wsum − ā·b̄, each (nx,ny,nz) (`ns3d_stats_finalize`)."
+function stats_finalize(S, wsum, Pr)
+    nx, ny, nz = _cint3(Pr)
+    mean = AMDGPU.zeros(Float64, size(Pr, 1), size(Pr, 2), size(Pr, 3) * 4)
+    rs = AMDGPU.zeros(Float64, size(Pr, 1), size(Pr, 2), size(Pr, 3) * 7); _sync()
+    check(ccall((:ns3d_stats_finalize, libns3d), Cint, (Ptr{Cvoid}, PF, Cdouble, PF, PF, Cint, Cint, Cint),
+                _ctx(), ptr(S), wsum, ptr(mean), ptr(rs), nx, ny, nz))
+    return mean, rs
 end
 mutable struct StepFields          # struct ns3d_step_fields (include/ns3d.h): device pointers, IN/OUT (the fused step swaps X and X_o)
     Pr::PF; dPrdtau::PF; divV::PF

@@ -355,6 +355,28 @@ void ns3d_diag_decode(const unsigned long long *w, const ns3d_diag_params *p, bo
     out->nonfinite = w[14] != 0ull;
 }
 
+// ---- ns3d_stats_* : running mean / Reynolds-stress fields (the state belongs to the caller) ----------------------------------
+static int stats_grid_check(int nx, int ny, int nz, const char *fn)
+{
+    if (nx < 3 || ny < 3 || nz < 3) return fail(NS3D_ERR_ARG, "%s: grid %dx%dx%d too small (need >= 3 per direction)", fn, nx, ny, nz);
+    return NS3D_OK;
+}
+extern "C" int ns3d_stats_reset(ns3d_ctx *c, double *S, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(S);
+    const int rc = stats_grid_check(nx, ny, nz, "ns3d_stats_reset");
+    if (rc) return rc;
+    return finish(c, hipMemsetAsync(S, 0, (size_t)NS3D_STATS_SLOTS * nx * ny * nz * sizeof(double), c->stream), "stats_reset");
+}
+extern "C" int ns3d_stats_finalize(ns3d_ctx *c, const double *S, double wsum, double *mean, double *rs, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(S, mean);
+    const int rc = stats_grid_check(nx, ny, nz, "ns3d_stats_finalize");
+    if (rc) return rc;
+    if (!std::isfinite(wsum) || !(wsum > 0.0)) return fail(NS3D_ERR_ARG, "ns3d_stats_finalize: wsum = %g (need a finite sum of weights > 0)", wsum);
+    return finish(c, DISPATCH(c, stats_finalize(c->stream, S, wsum, mean, rs, (long)nx * ny * nz)), "stats_finalize");
+}
+
 // After a synchronisation of the stream the persist launches ran on: did a bounded wait expire in any of them since the last check?
 // (k_pt_persist writes its ticket into pinned host memory when one does.)  A failure turns the cooperative form off for this context:
 // what made the workgroups non-resident — another context or process holding CUs — is unlikely to have gone away.
@@ -1111,6 +1133,16 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
         HIPCHK(c, hipStreamSynchronize(c->stream));                                                          \
         ns3d_diag_decode(c->diag_host, p, Pr != nullptr, C != nullptr, out_host);                            \
         return NS3D_OK;                                                                                      \
+    }                                                                                                        \
+    extern "C" int ns3d_stats_accumulate_##S(ns3d_ctx *c, double *St, const T *Vx, const T *Vy, const T *Vz, const T *Pr, \
+                                             double weight, int nx, int ny, int nz)                          \
+    {                                                                                                        \
+        CHECK_CTX(c); CHECK_PTRS(St, Vx, Vy, Vz);                                                            \
+        const int rc = stats_grid_check(nx, ny, nz, "ns3d_stats_accumulate");                                \
+        if (rc) return rc;                                                                                   \
+        if (!std::isfinite(weight)) return fail(NS3D_ERR_ARG, "ns3d_stats_accumulate: weight = %g is not finite", weight); \
+        return finish(c, DISPATCH(c, stats_accumulate<T>(c->stream, St, Vx, Vy, Vz, Pr, weight, nx, ny, nz)), \
+                      "stats_accumulate");                                                                   \
     }                                                                                                        \
     extern "C" int ns3d_correct_V_##S(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *Pr, double dt, double rho,  \
                                       double dx, double dy, double dz, int nx, int ny, int nz)               \

@@ -4179,6 +4179,81 @@ hipError_t diagnostics(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, con
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// ns3d_stats_accumulate: running sums of the cell-centred u, v, w, p and their products.  A pure streaming read-modify-write —
+// per cell 4 field reads (the i+1 / j+1 neighbours of Vx / Vy are loads of their own that L1 / L2 serve, the Vz plane just read
+// is kept for the next cell plane, as in k_diag), 11 accumulator loads and 11 stores: 208 B nominal in fp64, 192 B with fp32
+// fields.  No reduction, no LDS, no atomics: thread (i, j) marches kz cell planes, all loads of a plane are issued before its
+// stores.  One x-cell per thread and plain accesses to S: what was measured against two cells per thread with 16-byte accesses
+// and against non-temporal accesses is in DESIGN §4.9.
+// S = S + weight·term with the term's own parentheses; nothing here may be contracted in STRICT (the unit's -ffp-contract=off).
+// ---------------------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(256) void k_stats(double *__restrict__ S, const T *__restrict__ Vx, const T *__restrict__ Vy,
+                                               const T *__restrict__ Vz, const T *__restrict__ Pr, double wgt, int nx, int ny,
+                                               int nz, int kz)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y;
+    if (i >= nx || j >= ny) return;
+    const int kb = blockIdx.z * kz, ke = min(kb + kz, nz);
+    const idx_t pVx = (idx_t)(nx + 1) * ny, pVy = (idx_t)nx * (ny + 1), pC = (idx_t)nx * ny, N = pC * nz;
+    const idx_t oVx = (idx_t)i + (idx_t)(nx + 1) * j, oVy = (idx_t)i + (idx_t)nx * j, oC = oVy;
+    const bool has_p = Pr != nullptr;
+    double vz = (double)Vz[oC + pC * kb];
+    for (int k = kb; k < ke; ++k) {
+        const double vx0 = (double)Vx[oVx + pVx * k], vx1 = (double)Vx[oVx + 1 + pVx * k];
+        const double vy0 = (double)Vy[oVy + pVy * k], vy1 = (double)Vy[oVy + nx + pVy * k];
+        const double vz1 = (double)Vz[oC + pC * (k + 1)];
+        const double u = 0.5 * (vx0 + vx1), v = 0.5 * (vy0 + vy1), w = 0.5 * (vz + vz1);
+        const double p = has_p ? (double)Pr[oC + pC * k] : 0.0;
+        vz = vz1;
+        double *s = S + (oC + pC * k);
+        const double t[NS3D_STATS_SLOTS] = {u, v, w, p, u * u, v * v, w * w, u * v, u * w, v * w, p * p};
+        double a[NS3D_STATS_SLOTS];
+#pragma unroll
+        for (int q = 0; q < NS3D_STATS_SLOTS; ++q)
+            if (has_p || (q != NS3D_STATS_P && q != NS3D_STATS_PP)) a[q] = s[N * q];
+#pragma unroll
+        for (int q = 0; q < NS3D_STATS_SLOTS; ++q)
+            if (has_p || (q != NS3D_STATS_P && q != NS3D_STATS_PP)) s[N * q] = a[q] + wgt * t[q];
+    }
+}
+template <class T>
+hipError_t stats_accumulate(hipStream_t s, double *S, const T *Vx, const T *Vy, const T *Vz, const T *Pr, double weight, int nx,
+                            int ny, int nz)
+{
+    const int kz = NS3D_STATS_KZ;
+    const dim3 blk(64, 4, 1);
+    const dim3 grd((unsigned)((nx + 63) / 64), (unsigned)((ny + 3) / 4), (unsigned)((nz + kz - 1) / kz));
+    hipLaunchKernelGGL(k_stats<T>, grd, blk, 0, s, S, Vx, Vy, Vz, Pr, weight, nx, ny, nz, kz);
+    return hipGetLastError();
+}
+// ns3d_stats_finalize: mean = S/wsum (4 blocks), rs = S/wsum − ā·b̄ (7 blocks, optional); n cells, one per thread
+__global__ __launch_bounds__(256) void k_stats_finalize(const double *__restrict__ S, double wsum, double *__restrict__ mean,
+                                                        double *__restrict__ rs, idx_t n)
+{
+    const idx_t c = (idx_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    double m[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        m[q] = S[n * q + c] / wsum;
+        mean[n * q + c] = m[q];
+    }
+    if (!rs) return;
+    const int A[7] = {0, 1, 2, 0, 0, 1, 3}, B[7] = {0, 1, 2, 1, 2, 2, 3};     // uu vv ww uv uw vw pp
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        const double e = S[n * (4 + q) + c] / wsum, mm = m[A[q]] * m[B[q]];
+        rs[n * q + c] = e - mm;
+    }
+}
+hipError_t stats_finalize(hipStream_t s, const double *S, double wsum, double *mean, double *rs, long n_cells)
+{
+    hipLaunchKernelGGL(k_stats_finalize, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, s, S, wsum, mean, rs, (idx_t)n_cells);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Self-test of div_by_known against the hardware's IEEE division: n pseudo-random dividends per launch (random
 // significands over 120 binades — one in four over the whole guarded range and beyond it —, plus quotients planted next
 // to representable numbers and rounding midpoints).
@@ -4284,6 +4359,8 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
                                             unsigned long long *);                                           \
     template hipError_t diagnostics<T>(hipStream_t, const T *, const T *, const T *, const T *, const T *,   \
                                        const ns3d_diag_params &, unsigned long long *, unsigned long long *); \
+    template hipError_t stats_accumulate<T>(hipStream_t, double *, const T *, const T *, const T *, const T *, double, int, \
+                                            int, int);                                                       \
     template hipError_t divtest<T>(hipStream_t, double, long, unsigned long long, unsigned long long *);   \
     template hipError_t strip_inner<T>(hipStream_t, const T *, T *, int, int, int);                          \
     template hipError_t face_copy<T>(hipStream_t, T *, T *, int, int, int, int, int, int);                  \

@@ -72,6 +72,11 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
     return gx * gy * ((unsigned)(nz + 1 + kz - 1) / kz);
 }
 
+// ns3d_stats_accumulate (k_stats): 64×4 columns per workgroup over the nx×ny cell columns, NS3D_STATS_KZ planes of the nz cell planes
+// per workgroup.  4 was the fastest of 4 / 8 / 16 / 32 at 512³ and at 255×153×153 alike (profiles/stats_variants_ab.log): short
+// chunks keep every CU busy on small grids (a rank of the 255×153×153 case: 6 240 workgroups) and cost one extra Vz plane in four.
+#define NS3D_STATS_KZ 4
+
 #define NS3D_LAUNCHER_DECLS(NS)                                                                              \
     namespace NS {                                                                                           \
     template <class T>                                                                                       \
@@ -138,6 +143,11 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
     template <class T>                                                                                       \
     hipError_t diagnostics(hipStream_t, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C,     \
                            const ns3d_diag_params &, unsigned long long *part, unsigned long long *result); \
+    /* S: NS3D_STATS_SLOTS blocks of nx·ny·nz doubles; Pr may be null */                                     \
+    template <class T>                                                                                       \
+    hipError_t stats_accumulate(hipStream_t, double *S, const T *Vx, const T *Vy, const T *Vz, const T *Pr, \
+                                double weight, int nx, int ny, int nz);                                      \
+    hipError_t stats_finalize(hipStream_t, const double *S, double wsum, double *mean, double *rs, long n_cells); \
     template <class T>                                                                                       \
     hipError_t divtest(hipStream_t, double d, long n, unsigned long long seed, unsigned long long *bad_dev); \
     template <class T>                                                                                       \

@@ -23,6 +23,7 @@ from . import kernels as K
 from . import lib as L
 from .halo import ZSlabGrid
 from .slab import SlabPTSolver
+from .stats import RunningStats
 from .params import gpu_params, multi_params
 from .vis import save_frame_gpu, save_frame_multi
 
@@ -163,7 +164,8 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
-                       return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False):
+                       return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
+                       statistics=None, stats_every=1):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -185,11 +187,17 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     Fields, iteration counts and errs are those of the run without it, bit for bit.  With wide_advect_halo a step whose
     courant[2] is not below 2 raises Ns3dError instead of advecting outside ns3d_advect_wide's precondition (|δz| < 2 cells; on
     more than one rank only — on one rank wide_advect_halo has no effect and nothing is checked).
-    One rank or the C-ABI grid (mgpu.MgpuGrid), any topology."""
+    One rank or the C-ABI grid (mgpu.MgpuGrid), any topology.
+    statistics=s (default None: not one extra call): running statistics of the flow (ns3d_stats_accumulate, on the device, on every
+    local rank's context) sampled with weight 1.0 at the end of the steps s, s+stats_every, … — after the step's last halo update
+    :477, whichever way the step ran (`one_call` stays in use).  info.stats gets n, mean (U, V, W, P: cell-centred means) and rs
+    (uu, vv, ww, uv, uw, vw: Reynolds stresses, pp: pressure variance) as halo-stripped global host arrays on the root, gathered
+    like the fields.  Read-only: every other result keeps its bits."""
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
         device = torch.cuda.current_device()
+    _check_stats_options(statistics, stats_every)
     shape = dict(shape or {})
     if grid is None:
         p0 = multi_params(nx, **shape)
@@ -269,6 +277,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             if mg is not None:
                 return grid.diagnostics(col("Vx"), col("Vy"), col("Vz"), pr, cf, dps)[0]
             return K.diagnostics(fs[0].Vx, fs[0].Vy, fs[0].Vz, pr and pr[0], cf and cf[0], dps[0], ctx=ctxs[0])
+    running = RunningStats((nx, ny, nz), ctxs) if statistics is not None else None
     nsave = nvis = 10                                                                         # :330,332
     root = _is_root(grid)
     # :450's halo update of the normal stresses may only go with the stress arrays where the interior planes two ranks both compute
@@ -308,6 +317,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                 for q_, e in enumerate(errs):
                     print("  #iter = %d, err = %1.3e" % ((q_ + 1) * p.nchk, e))
             info.iters.append(done); info.errs.append(errs)
+            if running is not None and _stats_due(it, statistics, stats_every):
+                running.sample(fs)                          # ns3d_time_step has swapped the names: fs holds the new fields
             frames(it)
             continue
         if fuse_predictor:
@@ -400,16 +411,31 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=c)  # :476
         if not (wide_advect_halo and P > 1):
             grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                 # :477 (not C)
+        if running is not None and _stats_due(it, statistics, stats_every):
+            running.sample(fs)
         frames(it)
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
             K.copy(f.Vz_o, f.Vz, ctx=c)     # the one copy of :475 the swaps skipped (Vz is never advected): same final state
     sync()
     out = _gather_all(grid, fs)                                                               # :528-532
+    if running is not None:
+        info.stats = running.gathered(grid) if running.n else SimpleNamespace(n=0, wsum=0.0, mean=None, rs=None)
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
     return out + ((info,) if return_info else ())                                             # :535
+
+
+def _check_stats_options(statistics, stats_every):
+    if statistics is not None and (int(statistics) != statistics or statistics < 1):
+        raise L.Ns3dError("statistics = %r (None, or the first step to sample: an integer >= 1)" % (statistics,))
+    if int(stats_every) != stats_every or stats_every < 1:
+        raise L.Ns3dError("stats_every = %r (an integer >= 1)" % (stats_every,))
+
+
+def _stats_due(it, first, every):
+    return it >= first and (it - first) % every == 0
 
 
 def _predict_swap(f, p, ctx):
@@ -464,16 +490,19 @@ def _save_mat(path, f, p, step0):
 
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
-          diagnostics=False):
+          diagnostics=False, statistics=None, stats_every=1):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
     every nvis = 10 steps).
     diagnostics=True: as in run_navierstokes3D — the monitor before the set_cylinder! calls :123 and :139 and after :140, one
     record per step in info.diag (gpu.jl's form of the cylinder test, its dx-for-dy quirk included), a line per step with
-    do_print; the step runs call by call (`one_call` is not used) and returns the same bits."""
+    do_print; the step runs call by call (`one_call` is not used) and returns the same bits.
+    statistics / stats_every: as in run_navierstokes3D, sampled after :142; info.stats holds the FULL local arrays (boundary cells
+    included)."""
     if device is None:
         device = torch.cuda.current_device()
+    _check_stats_options(statistics, stats_every)
     dev = torch.device("cuda", device)
     ctx = K.Context(device, mode, async_=True)
     p = gpu_params(nx)
@@ -499,6 +528,7 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         iframe += 1
     step_params = None
     monitor = None
+    running = RunningStats((nx, ny, nz), [ctx]) if statistics is not None else None
     if diagnostics:
         info.diag = []
         dp = K.diag_params(nx, ny, nz, p.dx, p.dy, p.dz, p.rho, cylinder=cyl)
@@ -518,6 +548,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
                 for q_, e in enumerate(errs):
                     print("  #iter = %d, err = %1.3e" % ((q_ + 1) * p.nchk, e))                # :134
             info.iters.append(done); info.errs.append(errs)
+            if running is not None and _stats_due(it, statistics, stats_every):
+                running.sample([f])                         # ns3d_time_step has swapped the names: f holds the new fields
             if do_vis and it % nvis == 0:                                                     # :143-167
                 ctx.sync()
                 save_frame_gpu(host(), ny, nz, iframe)
@@ -577,6 +609,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             K.copy(f.Vx_o, f.Vx, ctx=ctx); K.copy(f.Vy_o, f.Vy, ctx=ctx)                      # :141
             K.copy(f.Vz_o, f.Vz, ctx=ctx); K.copy(f.C_o, f.C, ctx=ctx)
             K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=ctx)  # :142
+        if running is not None and _stats_due(it, statistics, stats_every):
+            running.sample([f])
         if do_vis and it % nvis == 0:                                                         # :143-167
             ctx.sync()
             save_frame_gpu(host(), ny, nz, iframe)
@@ -588,4 +622,6 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()
     info.ctx = ctx
+    if running is not None:
+        info.stats = running.local(0) if running.n else SimpleNamespace(n=0, wsum=0.0, mean=None, rs=None)
     return f, info

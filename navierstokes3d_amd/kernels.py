@@ -337,6 +337,52 @@ def diagnostics(Vx, Vy, Vz, Pr, Cf, dp, ctx=None):
     return diag_record(out)
 
 
+def _chk_blocks(t, nblocks, cells, name):
+    """a float64 device array of `nblocks` consecutive column-major (nx,ny,nz) blocks: kernels.zeros((nx, ny, nz·nblocks)) or any
+    contiguous float64 tensor of that many elements"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+        raise L.Ns3dError("%s must be a float64 CUDA/HIP tensor" % name)
+    if t.numel() != nblocks * cells:
+        raise L.Ns3dError("%s has %d elements, expected %d blocks of %d" % (name, t.numel(), nblocks, cells))
+    if t.dim() == 3:
+        return _chk(t, None, name)
+    if not t.is_contiguous():
+        raise L.Ns3dError("%s must be contiguous" % name)
+    return C.c_void_p(t.data_ptr())
+
+
+def stats_accumulate(S, Vx, Vy, Vz, Pr, weight=1.0, ctx=None):
+    """ns3d_stats_accumulate: one sample into the running sums S (lib.NS3D_STATS_SLOTS blocks of (nx,ny,nz) float64, slot order
+    stats.SLOTS): S += weight·(u, v, w, p, uu, vv, ww, uv, uw, vw, pp) of the cell-centred values, one fused pass on the device.
+    Pr may be None (slots p and pp are left alone).  Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    c = _ctx(ctx, Vx)
+    c.call("stats_accumulate", Vx, _chk_blocks(S, L.NS3D_STATS_SLOTS, nx * ny * nz, "S"), _chk(Vx, (nx + 1, ny, nz), "Vx"),
+           _chk(Vy, (nx, ny + 1, nz), "Vy"), _chk(Vz, (nx, ny, nz + 1), "Vz"),
+           None if Pr is None else _chk(Pr, (nx, ny, nz), "Pr"), C.c_double(float(weight)), nx, ny, nz)
+
+
+def _untyped(ctx, ref, name, *args):
+    c = _ctx(ctx, ref)
+    if not getattr(c, "_pinned", False) and torch.cuda.current_stream(c.device).cuda_stream != c._stream:
+        c.use_torch_stream()
+    L.check(getattr(c.lib, name)(c.handle, *args))
+
+
+def stats_reset(S, shape, ctx=None):
+    """ns3d_stats_reset: S = 0 on the context's stream; shape = (nx, ny, nz) of one block."""
+    nx, ny, nz = (int(q) for q in shape)
+    _untyped(ctx, S, "ns3d_stats_reset", _chk_blocks(S, L.NS3D_STATS_SLOTS, nx * ny * nz, "S"), nx, ny, nz)
+
+
+def stats_finalize(S, wsum, mean, rs, shape, ctx=None):
+    """ns3d_stats_finalize: mean (4 blocks) = S[u,v,w,p]/wsum; rs (7 blocks, or None) = S[uu…vw,pp]/wsum − ā·b̄."""
+    nx, ny, nz = (int(q) for q in shape)
+    n = nx * ny * nz
+    _untyped(ctx, S, "ns3d_stats_finalize", _chk_blocks(S, L.NS3D_STATS_SLOTS, n, "S"), C.c_double(float(wsum)),
+             _chk_blocks(mean, 4, n, "mean"), None if rs is None else _chk_blocks(rs, 7, n, "rs"), nx, ny, nz)
+
+
 def correct_V(Vx, Vy, Vz, Pr, dt, rho, dx, dy, dz, ctx=None):
     """correct_V!  multi.jl:97-102 / gpu.jl:214-219"""
     nx, ny, nz = Pr.shape

@@ -76,6 +76,7 @@ SIGNATURES = {
     "max_abs": [_P, _L, C.POINTER(_D)],
     "correct_V": [_P] * 4 + [_D] * 5 + [_I] * 3,
     "diagnostics": [_P] * 5 + [C.POINTER(DiagParams), C.POINTER(Diag)],
+    "stats_accumulate": [_P] * 5 + [_D] + [_I] * 3,
     "bc_x": [_P] + [_I] * 3,
     "bc_y": [_P] + [_I] * 3,
     "bc_z": [_P] + [_I] * 3,
@@ -102,7 +103,9 @@ SIGNATURES = {
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
                    "ns3d_set_pt2_variant", "ns3d_set_ptn_variant", "ns3d_set_pt_depth", "ns3d_set_graph_mode", "ns3d_set_autotune", "ns3d_last_pt2_variant", "ns3d_last_ptn_variant", "ns3d_last_pt_depth",
-                   "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults"]
+                   "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
+                   "ns3d_stats_reset", "ns3d_stats_finalize"]
+NS3D_STATS_SLOTS = 11
 
 
 _PP = C.POINTER(C.c_void_p)      # T *const *  — one device pointer per local rank (field-major for field lists)
@@ -204,6 +207,10 @@ def load():
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
     lib.ns3d_arith_build.restype = _I
+    lib.ns3d_stats_reset.argtypes = [_P, _P] + [_I] * 3
+    lib.ns3d_stats_reset.restype = _I
+    lib.ns3d_stats_finalize.argtypes = [_P, _P, _D, _P, _P] + [_I] * 3
+    lib.ns3d_stats_finalize.restype = _I
     for name, args in SIGNATURES.items():
         for suf in ("f64", "f32"):
             fn = getattr(lib, "ns3d_%s_%s" % (name, suf))
