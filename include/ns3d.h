@@ -30,7 +30,8 @@
  *    (≤1e-6 relative L2 at equal iteration counts).  In STRICT mode x/dx is evaluated as the correctly rounded
  *    quotient by the divisor-known-in-advance sequence q=RN(x·r), e=x−q·dx (FMA), RN(q+e·r) with r=RN(1/dx)
  *    whenever dx,dy,dz are eligible (same bits as the division instruction sequence, ≈⅓ of the instructions;
- *    ns3d_selftest_exact_div compares the two on the device); NS3D_IEEE_DIV forces the plain sequence.
+ *    ns3d_selftest_exact_div compares the two on the device, with quotients drawn across the whole range in which
+ *    the sequence runs, both of its bounds and the plain-division range beyond them); NS3D_IEEE_DIV forces the plain sequence.
  */
 #ifndef NS3D_H
 #define NS3D_H
@@ -375,7 +376,9 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
     int ns3d_residual_max_##S(ns3d_ctx *, const T *Pr, const T *divV, const ns3d_pt_params *p,               \
                               double *out_host);                                                             \
     /* Compares the divisor-known-in-advance division with the plain IEEE division for n pseudo-random dividends  \
-     * (bitwise); *mismatches must come back 0. */                                                           \
+     * (bitwise); *mismatches must come back 0.  The dividends are x = RN(q*d) with the QUOTIENT's binade drawn: half \
+     * within 2^+-60 (f32: 2^+-20), the rest over the guard's whole range, eight binades beyond each end, within six    \
+     * binades of each bound of the one- and two-division guards; every other one planted next to a rounding midpoint. */ \
     int ns3d_selftest_exact_div_##S(ns3d_ctx *, double d, long n, unsigned long long seed, long *mismatches);\
     /* The whole inner loop multi.jl:458-471 / gpu.jl:126-137 on one rank: at most niter iterations, every   \
      * nchk-th computes err = max|Rp|*err_mul/err_div (= maximum(abs.(Rp))*ly^2/psc, multi.jl:466), stops  \

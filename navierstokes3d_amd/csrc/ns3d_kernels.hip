@@ -70,15 +70,29 @@ static Geo<T> make_geo(double dx, double dy, double dz)
 // Muller & Raina, IEEE TC 2004: "the advanced computation of 1/y allows performing correctly rounded division in one
 // multiplication plus two FMACs"):
 //        q = RN(x·r);   e = x − q·d  (exact, one FMA);   q' = RN(q + e·r)  =  RN(x/d)
-// valid while no intermediate over/underflows, i.e. for 2^-900 < |q| < 2^900 with 2^-100 < d < 2^100 (checked on the
-// host, which also refuses divisors whose significand is all ones); everything else — zeros (sign preserved), huge,
+// The result is RN(x/d) only while e is EXACT.  q·d is an integer multiple of ulp(q)·ulp(d) = 2^(eq+ed−2(p−1)) (eq, ed the
+// exponents of q and d, p = 24 / 53 significand bits) and |e| < ulp(q)·d, so e is representable — to its last bit — exactly
+// when that quantum is no finer than the format's smallest subnormal 2^(emin−p+1):
+//        eq + ed ≥ (emin − p + 1) + 2(p − 1)      fp32: eq + ed ≥ −149 + 46 = −103      fp64: eq + ed ≥ −1074 + 104 = −970
+// (x, q and q' are then normal as well: |x| ≈ |q|·d ≥ 2^−104 / 2^−971).  The guard tests |q| alone, so its lower bound has to hold
+// for the SMALLEST divisor the host admits.  recip_ok (ns3d_api.cpp) admits 2^−20 < (float)d < 2^20 for BOTH element types
+// (a spacing must suit the f32 kernels too; its double range 2^±100 never binds) and refuses significands of all ones in
+// either type (Markstein's proof needs them excluded), hence ed ≥ −20 and
+//        fp32: |q| > 2^−83   (eq ≥ −83:  eq + ed ≥ −103)          fp64: |q| > 2^−900   (eq + ed ≥ −920 ≥ −970)
+// (fp32 used to say 2^−100: with d = float(1.3·2^−19), x = 7.336370446077286e−36 the residual lost its low bits and the
+// quotient came out one ulp low.)  Upwards nothing can go wrong before q itself overflows: |q| < 2^100 / 2^900 keeps
+// |x| ≈ |q|·d < 2^120 / 2^920 and |e·r| ≈ ulp(q) finite.  tests/test_div_guard_host.py proves both bounds with an exact integer
+// model of this sequence over the admitted divisors, reading the constants from this file and from recip_ok.
+// Everything else — zeros (sign preserved), huge,
 // tiny, Inf, NaN — takes the plain division, behind two branches so that a wave whose only outliers are ZEROS (fields at rest:
 // the cylinder case starts with Vy = Vz = 0 and a uniform Vx) does not run it: the predictor of the 255×153×153 case was three
 // times slower per plane than the power-of-two build before (round 4).  `ns3d_selftest_exact_div` compares the two on the
-// GPU bit for bit.
+// GPU bit for bit, with quotients drawn across both guard bounds.
+__device__ __forceinline__ double abs_div(double a) { return __builtin_fabs(a); }
+__device__ __forceinline__ float abs_div(float a) { return __builtin_fabsf(a); }
 template <class T> struct DivLim;
 template <> struct DivLim<double> { static constexpr double lo = 0x1p-900, hi = 0x1p900; };
-template <> struct DivLim<float> { static constexpr float lo = 0x1p-100f, hi = 0x1p100f; };
+template <> struct DivLim<float> { static constexpr float lo = 0x1p-83f, hi = 0x1p100f; };
 template <class T>
 __device__ __forceinline__ T div_by_known(T x, T d, T r)
 {
@@ -4254,9 +4268,12 @@ hipError_t stats_finalize(hipStream_t s, const double *S, double wsum, double *m
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Self-test of div_by_known against the hardware's IEEE division: n pseudo-random dividends per launch (random
-// significands over 120 binades — one in four over the whole guarded range and beyond it —, plus quotients planted next
-// to representable numbers and rounding midpoints).
+// Self-test of div_by_known against the hardware's IEEE division: n pseudo-random dividends per launch.  The QUOTIENT's
+// binade is drawn, x = RN(q·d), so that every admitted divisor — small or large — meets the fast path, the plain division
+// and the boundary between them: half of the quotients within 2^±60 (fp32: 2^±20), one in eight over the guard's whole
+// range and eight binades beyond each end, one in eight within six binades of DivLim's lower or upper bound, and a quarter with
+// the DIVIDEND within six binades of Div2Lim's bounds (the guard of the two-division forms tests |x|).  Every other dividend
+// is moved by −3…+3 representable steps, which plants the quotient next to a representable number or a rounding midpoint.
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned long long splitmix(unsigned long long &st)
 {
@@ -4265,45 +4282,55 @@ __device__ __forceinline__ unsigned long long splitmix(unsigned long long &st)
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+// 2^k (k inside the normal range), ±[1,2) from random bits, a number `k` representable steps away, bitwise equality
+__device__ __forceinline__ double dt_pow2(int k, double) { return __longlong_as_double((long long)(1023 + k) << 52); }
+__device__ __forceinline__ float dt_pow2(int k, float) { return __uint_as_float((unsigned int)(127 + k) << 23); }
+__device__ __forceinline__ double dt_unit(unsigned long long u, double)
+{
+    return __longlong_as_double((long long)((u & 0x8000000000000000ull) | (1023ull << 52) | (u & 0x000FFFFFFFFFFFFFull)));
+}
+__device__ __forceinline__ float dt_unit(unsigned long long u, float)
+{
+    const unsigned int w = (unsigned int)u;
+    return __uint_as_float((w & 0x80000000u) | (127u << 23) | (w & 0x007FFFFFu));
+}
+__device__ __forceinline__ double dt_step(double x, int k) { return __longlong_as_double(__double_as_longlong(x) + (long long)k); }
+__device__ __forceinline__ float dt_step(float x, int k) { return __uint_as_float(__float_as_uint(x) + (unsigned int)k); }
+__device__ __forceinline__ bool dt_same(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+__device__ __forceinline__ bool dt_same(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ int dt_ilogb(double a) { return ilogb(a); }
+__device__ __forceinline__ int dt_ilogb(float a) { return ilogbf(a); }
 template <class T>
 __global__ __launch_bounds__(256) void k_divtest(T d, T r, long n, unsigned long long seed, unsigned long long *bad)
 {
     unsigned long long st = seed + 0x632BE59BD9B4E019ull * ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x + 1);
     unsigned long long nb = 0;
+    const int near = sizeof(T) == 8 ? 60 : 20;
+    const int elo = dt_ilogb(DivLim<T>::lo), ehi = dt_ilogb(DivLim<T>::hi);
+    const T tmax = dt_pow2(sizeof(T) == 8 ? 1022 : 126, (T)0), tmin = dt_pow2(sizeof(T) == 8 ? -1020 : -124, (T)0);
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
         const unsigned long long u = splitmix(st), v = splitmix(st);
-        T x;
-        if (sizeof(T) == 8) {
-            const unsigned long long mant = u & 0x000FFFFFFFFFFFFFull, sign = u & 0x8000000000000000ull;
-            const unsigned long long expo = ((v >> 32) & 3) ? 1023 - 60 + (v % 120) : 1023 - 720 + (v % 1440);  // 1 in 4 over the guard's whole range and beyond
-            double xd = __longlong_as_double((long long)(sign | (expo << 52) | mant));
-            if ((v >> 60) & 1) { // plant the quotient next to a representable number / midpoint: x ≈ qc·d
-                double qc = xd, prod = qc * (double)d;
-                long long pb = __double_as_longlong(prod) + (long long)((v >> 56) & 7) - 3;
-                xd = __longlong_as_double(pb);
-            }
-            x = (T)xd;
-        } else {
-            const unsigned int w = (unsigned int)u;
-            const unsigned int mant = w & 0x007FFFFFu, sign = w & 0x80000000u,
-                               expo = ((v >> 32) & 3) ? 127 - 20 + (unsigned int)(v % 40) : 127 - 80 + (unsigned int)(v % 160);
-            float xf = __uint_as_float(sign | (expo << 23) | mant);
-            if ((v >> 60) & 1) xf = __uint_as_float(__float_as_uint(xf * (float)d) + (unsigned int)((v >> 56) & 7) - 3u);
-            x = (T)xf;
-        }
+        const unsigned int cat = (unsigned int)(v >> 32) & 7u;
+        const T m = dt_unit(u, (T)0);
+        T qc;
+        if (cat == 4) qc = m * dt_pow2(elo - 8 + (int)(v % (unsigned long long)(ehi - elo + 16)), (T)0);
+        else if (cat == 5) qc = m * dt_pow2(((v >> 40) & 1 ? ehi : elo) - 6 + (int)(v % 12), (T)0);
+#if defined(NS3D_EXACT_RECIP)
+        else if (cat >= 6) qc = (m * (((v >> 40) & 1 ? Div2Lim<T>::hi : Div2Lim<T>::lo) * dt_pow2(-6 + (int)(v % 12), (T)0))) * r;
+#endif
+        else qc = m * dt_pow2(-near + (int)(v % (unsigned long long)(2 * near)), (T)0);
+        T x = qc * d;
+        const T ax = abs_div(x);
+        if (((v >> 60) & 1) && ax > tmin && ax < tmax) x = dt_step(x, (int)((v >> 56) & 7) - 3);   // plant: x/d next to qc or a midpoint
         const T a = div_by_known(x, d, r), b = x / d;
-        bool same;
-        if (sizeof(T) == 8) same = __double_as_longlong((double)a) == __double_as_longlong((double)b);
-        else same = __float_as_uint((float)a) == __float_as_uint((float)b);
+        bool same = dt_same(a, b);
 #if defined(NS3D_EXACT_RECIP)
         bool ok = true;                       // the branch-free double division of the hot kernels: x/d/d
         const T a2 = div2_known<T>(x, d, r, ok), b2 = x / d / d;
         if (ok) {
-            if (sizeof(T) == 8) same = same && (__double_as_longlong((double)a2) == __double_as_longlong((double)b2));
-            else same = same && (__float_as_uint((float)a2) == __float_as_uint((float)b2));
+            same = same && dt_same(a2, b2);
             const T a3 = div2_known_nochk<T>(x, d, r);   // k_pt_sweep2's form (guarded per value, same dividend range)
-            if (sizeof(T) == 8) same = same && (__double_as_longlong((double)a3) == __double_as_longlong((double)b2));
-            else same = same && (__float_as_uint((float)a3) == __float_as_uint((float)b2));
+            same = same && dt_same(a3, b2);
         }
 #endif
         nb += same ? 0 : 1;

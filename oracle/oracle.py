@@ -10,6 +10,7 @@ kernels (multi.jl:36-281); the cell grid (nx,ny,nz) is derived from the array sh
 ParallelStencil derives the launch range from its arguments.
 """
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -24,8 +25,18 @@ def build(force=False):
         return os.environ["NS3D_ORACLE_LIB"]
     so = os.path.join(_HERE, "libns3d_oracle.so")
     src = os.path.join(_HERE, "ns3d_oracle.c")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-C", _HERE, "-s"], stdout=subprocess.DEVNULL)
+    stale = lambda: not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src)
+    if force or stale():
+        # several processes may get here at once (the spawned ranks of tests/test_halo_gloo.py): one builds, the
+        # others wait on the directory's lock and find the library fresh.  The Makefile moves the finished library
+        # into place, so a process that did not wait never loads a half-written file either.
+        fd = os.open(_HERE, os.O_RDONLY)
+        try:
+            fcntl.flock(fd, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.check_call(["make", "-C", _HERE, "-s"], stdout=subprocess.DEVNULL)
+        finally:
+            os.close(fd)
     return so
 
 

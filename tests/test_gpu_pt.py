@@ -7,7 +7,7 @@ the outlet plane, on ragged grids.  FAST: ≤1e-9 relative L2 after 40 sweeps (f
 import numpy as np
 import pytest
 
-from util import fields, geometry, rel_l2, rnd
+from util import bits_equal as _bits_equal, fields, geometry, rel_l2, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -273,14 +273,6 @@ def test_pt_solve_hip_graph_replay(hip, oracle, two):
 
 
 # ---- the exact-division guard: values far outside the range in which the reciprocal sequence is proven exact -----------
-def _bits_equal(a, b):
-    """Bit-for-bit (signed zeros included); NaNs compare equal to NaNs whatever their payload."""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    u = np.uint64 if a.dtype == np.float64 else np.uint32
-    nan = np.isnan(a) & np.isnan(b)
-    return bool(np.all((a.view(u) == b.view(u)) | nan))
-
-
 def _extreme_fields(nx, ny, nz, dtype, seed, mode):
     """Pressure fields that exercise the guard of STRICT's division-by-known-divisor (the cases it must hand to the plain
     IEEE division; an unguarded reciprocal sequence mis-rounds ≈30 % of the dividends near 1e-308 / 1e-38):
