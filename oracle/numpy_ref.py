@@ -114,10 +114,14 @@ def bc_x_Pr(A, val):                                                # multi.jl:1
     A[-1, :, :] = val
 
 
-def _mask(xq, yq, ox, oy, sinb, cosb, a2, b2, thr):
+def _q(xq, yq, ox, oy, sinb, cosb, a2, b2):                         # the ellipse's quadratic form (also run on value/bound pairs)
     xr = (xq - ox) * cosb - (yq - oy) * sinb
     yr = (xq - ox) * sinb + (yq - oy) * cosb
-    return xr * xr / a2 + yr * yr / b2 < thr
+    return xr * xr / a2 + yr * yr / b2
+
+
+def _mask(xq, yq, ox, oy, sinb, cosb, a2, b2, thr):
+    return _q(xq, yq, ox, oy, sinb, cosb, a2, b2) < thr
 
 
 def _apply_cyl(C, Vx, Vy, Vz, xc, yc, xv, yv, a2, b2, ox, oy, sinb, cosb):
