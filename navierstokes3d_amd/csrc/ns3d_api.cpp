@@ -511,7 +511,7 @@ static Plan tune_plan(ns3d_ctx *c, hipStream_t s, int mode, const T *src, T *dst
         bool ok = true;
         for (int rep = 0; rep <= timed && ok; ++rep) {     // one untimed launch, then `timed` timed ones
             if (rep == 1) ok = hipEventRecord(c->tune_ev[0], s) == hipSuccess;
-            const int tf = (c->reserved_cus / 8) << 8;      // compute units the launch must not count on
+            const int tf = ns3d_pass_flags_cus(c->reserved_cus);      // compute units the launch must not count on
             hipError_t e = depth == 2 ? DISPATCHM(mode, pt_sweep2<T>(s, v, src, dst, dsrc, ddst, divV, *p, k0, k1, tf))
                                       : DISPATCHM(mode, pt_sweepn<T>(s, depth, v, src, dst, dsrc, ddst, divV, *p, k0, k1, tf));
             ok = ok && e == hipSuccess;
@@ -653,7 +653,7 @@ static hipError_t launch_pass(ns3d_ctx *c, hipStream_t s, int depth, const Plan 
 {
     const int mode = mode_of(c, p->dx, p->dy, p->dz);
     c->last_depth = depth;
-    const int flags = more_flags | ((c->reserved_cus / 8) << 8);   // bits 8…: compute units the launch must not count on (in eights)
+    const int flags = more_flags | ns3d_pass_flags_cus(c->reserved_cus);   // bits 8…: compute units the launch must not count on (in eights)
     if (depth == 2) {
         c->last_pt2 = pl.v2;
         return DISPATCHM(mode, pt_sweep2<T>(s, pl.v2, src, dst, dsrc, ddst, divV, *p, k0, k1, flags, win));
@@ -829,7 +829,7 @@ static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, T *
         // next (persist_failed below) redoes the block by launches
         T *dout = ddst;
         if (!dout && ensure_pingpong_d<T>(c, p, &dout) != NS3D_OK) return hipErrorOutOfMemory;
-        e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, n, &c->persist, (c->reserved_cus / 8) << 8));
+        e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, n, &c->persist, ns3d_pass_flags_cus(c->reserved_cus)));
         if (e == hipSuccess) {
             T *t = src; src = dst; dst = t;
             if (ddst) { t = dsrc; dsrc = ddst; ddst = t; }
@@ -914,7 +914,7 @@ static bool use_persist(const ns3d_ctx *c, const ns3d_pt_params *p)
         if ((long long)p->nx * p->ny * p->nz > 170ll * 1000 || p->nx > 66) return false;
     }
     const hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, *p, 2, nullptr,
-                                                                      (c->reserved_cus / 8) << 8));
+                                                                      ns3d_pass_flags_cus(c->reserved_cus)));
     if (e != hipSuccess) (void)hipGetLastError();
     return e == hipSuccess;                                         // the CUs this context launches on hold the whole grid at once
 }
@@ -963,7 +963,7 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
         T *dout = ddst;
         if (!dout && (rc = ensure_pingpong_d<T>(c, p, &dout))) return rc;
         hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz,
-                                 pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, niter, &c->persist, (c->reserved_cus / 8) << 8, nchk, eps,
+                                 pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, niter, &c->persist, ns3d_pass_flags_cus(c->reserved_cus), nchk, eps,
                                                err_mul, err_div));
         if (e == hipSuccess) {
             HIPCHK(c, hipStreamSynchronize(s));

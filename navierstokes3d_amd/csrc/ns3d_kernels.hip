@@ -39,12 +39,6 @@
 namespace NS3D_NS {
 
 typedef long long idx_t;
-#ifndef NS3D_STEP_UNROLL
-#define NS3D_STEP_UNROLL 0      // 0: chosen per tile shape (k_pt_sweepN); 1, 2, 4: forced, for A/B builds
-#endif
-#ifndef NS3D_SHAPE24_F64
-#define NS3D_SHAPE24_F64 0      // A/B: the 1024-thread 64×32 shape for fp64 as well (it spills: 128 registers per lane)
-#endif
 #define IX3(i, j, k, sx, sy) ((idx_t)(i) + (idx_t)(sx) * ((idx_t)(j) + (idx_t)(sy) * (idx_t)(k)))
 
 // Grid spacings.  STRICT divides (x/dx, x/dx/dx) exactly like the Julia expressions; FAST multiplies by
@@ -1561,6 +1555,22 @@ struct SweepArgs {
     int cus_off;  // host side only: compute units the stream's CU mask leaves out (ns3d_reserve_cus) — the z-chunking counts the rest
     int no_faces; // NS3D_PASS_SKIP_FACES: no k_pt_faces launch behind the sweep (a split pass completes the boundary cells itself: box_pass_overlapped)
 };
+// Every field of SweepArgs from the PT parameters, for the output planes [k0,k1), with the single-rank defaults: the whole tile grid,
+// the faces completed behind the sweep, no compute unit left out, z halos as `p` says.  Callers state only what differs.
+template <class T>
+static SweepArgs<T> make_sweep_args(const ns3d_pt_params &p, const T *Pin, T *Pout, const T *Din, T *Dout, const T *RHS, int k0, int k1)
+{
+    SweepArgs<T> a;
+    a.Pin = Pin; a.Pout = Pout; a.D = Dout; a.Din = Din; a.RHS = RHS;
+    a.g = make_geo<T>(p.dx, p.dy, p.dz);
+    a.rho_dt = (T)p.rho / (T)p.dt; a.dtau = (T)p.dtau; a.one_m_damp = (T)1.0 - (T)p.damp;
+    a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
+    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
+    a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = p.z_lo_is_halo; a.zhi_halo = p.z_hi_is_halo;
+    a.k0 = k0; a.k1 = k1; a.kz = 1;
+    a.tx0 = a.ty0 = 0; a.win = nullptr; a.cus_off = 0; a.no_faces = 0;
+    return a;
+}
 
 // value stored on the x planes for target plane kk (0-based)
 template <class T>
@@ -1737,6 +1747,7 @@ static hipError_t launch_zmarch(hipStream_t s, SweepArgs<T> &a, int kz)
 // 6–11 % on MI355X (512³ strict 220 000 → 235 000 Mcells·iter/s, 255×153×153 177 000 → 197 000 with plain accesses; HBM
 // traffic 6.07 → 5.65 GB per pass): the rows that neighbouring tiles share are then re-fetched from HBM instead of hitting
 // the L2, and the next launch finds less of its input in the Infinity Cache.  -DNS3D_NONTEMPORAL restores the hints (A/B).
+// (Left switchable on purpose: resolving it would leave the sweep kernels' NT parameter without meaning, and run-time variants with it.)
 template <class T, bool NT> __device__ __forceinline__ T ld_stream(const T *p)
 {
 #ifdef NS3D_NONTEMPORAL
@@ -2290,7 +2301,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweep2(SweepArgs<T> a
     };
     // the step body written out four times per trip for the two-rows-per-thread shapes (see k_pt_sweepN: the ring rotations
     // inside a trip are renamed away); the four- and six-row shapes have no registers to spare for it
-    constexpr int UNR = NS3D_STEP_UNROLL > 0 ? NS3D_STEP_UNROLL : (CPT <= 2 ? 4 : 1);
+    constexpr int UNR = CPT <= 2 ? 4 : 1;
     int s = 0;
     if constexpr (UNR > 1) {
         const int hot_lo = max(2, 4 - kb), hot_hi = min(nsteps, nz - kb);       // bulk: s ≥ 2 and plane k2 = kb−2+s in [2, nz−3]
@@ -2389,14 +2400,7 @@ __global__ __launch_bounds__(256) void k_pt_faces_region(SweepArgs<T> a, int cx0
 template <class T>
 hipError_t pt_faces_region(hipStream_t s, T *Pout, const ns3d_pt_params &p, const int c0[3], const int c1[3], int want_core)
 {
-    SweepArgs<T> a;
-    a.Pin = Pout; a.Pout = Pout; a.D = nullptr; a.Din = nullptr; a.RHS = nullptr;
-    a.g = make_geo<T>(p.dx, p.dy, p.dz);
-    a.rho_dt = (T)p.rho / (T)p.dt; a.dtau = (T)p.dtau; a.one_m_damp = (T)1.0 - (T)p.damp;
-    a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
-    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
-    a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = p.z_lo_is_halo; a.zhi_halo = p.z_hi_is_halo;
-    a.k0 = 1; a.k1 = p.nz - 1; a.kz = 1; a.no_faces = 0; a.cus_off = 0; a.win = nullptr; a.tx0 = a.ty0 = 0;
+    SweepArgs<T> a = make_sweep_args<T>(p, Pout, Pout, nullptr, nullptr, nullptr, 1, p.nz - 1);
     if (p.nx < 3 || p.ny < 3 || p.nz < 3) return hipErrorInvalidValue;
     const long cells = 2l * p.nx * (p.nz - 2) + 2l * p.nx * p.ny;
     hipLaunchKernelGGL(k_pt_faces_region<T>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, a, c0[0], c0[1], c0[2], c1[0], c1[1], c1[2],
@@ -2523,16 +2527,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
     const int nb = gridDim.x, b = blockIdx.x;
     const int q = nb >> 3, rem = nb & 7, xcd = b & 7, loc = b >> 3;
     const int tile = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + loc;
-#if defined(NS3D_TILE_ORDER) && NS3D_TILE_ORDER == 1     // A/B: y-neighbouring tiles next to each other in an XCD's range
-    const int ty_t = tile % nty, tx_t = (tile / nty) % ntx, tz_t = tile / (ntx * nty);
-#elif defined(NS3D_TILE_ORDER) && NS3D_TILE_ORDER >= 2   // A/B: strips NS3D_TILE_ORDER tiles wide in x, y-fastest inside a strip
-    const int tz_t = tile / (ntx * nty), t2 = tile % (ntx * nty);
-    const int strip = t2 / (NS3D_TILE_ORDER * nty), ins = t2 % (NS3D_TILE_ORDER * nty);
-    const int sw = min(NS3D_TILE_ORDER, ntx - strip * NS3D_TILE_ORDER);
-    const int tx_t = strip * NS3D_TILE_ORDER + ins % sw, ty_t = ins / sw;
-#else
     const int tx_t = a.tx0 + tile % ntx, ty_t = a.ty0 + (tile / ntx) % nty, tz_t = tile / (ntx * nty);     // ntx × nty: the launch's tile window
-#endif
     const int ox = 1 + tx_t * (TX - OV), oy = 1 + ty_t * (TY - OV);
     const int kb = a.k0 + tz_t * a.kz;
     const int ke = min(kb + a.kz, a.k1);
@@ -2564,31 +2559,12 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
         doff[r] = (cjj - 1) * (nx - 2) + (cii - 1);
         outc[r] = x_out && (gj <= ny - 2) && (lr >= NL - 1 || tile_y_lo) && (lr <= TY - NL || tile_y_hi);
     }
-    // Wave-uniform level skipping (round 4, VERDICT r3 #1a; -DNS3D_LEVEL_SKIP=1).  Level ℓ is exact on the rows ℓ−1 … TY−ℓ of a tile
-    // (all rows on a side that is a face of the domain); a wave none of whose CPT rows lies in that range computes nothing any
-    // valid row ever reads, so it may skip level ℓ's arithmetic and the publish of its Pˡ: with 12 waves × 2 rows, waves 0 and 11
-    // skip levels 3 and 4 of an interior tile, 4 of 48 wave-levels.  Same bits (138 sweepN tests) — and the same time: the pass
-    // is not bound by the instructions it issues (profiles/r4_levelskip_dma_ab.log), so the default build leaves it out.
-// DIAGNOSTIC builds only (WRONG results; tools/ab/ablate.sh): what part of a pass is whose — bit 1: the step's global loads replaced by
-// register values, bit 2: its stores behind a condition that never holds, bit 4: no LDS publishes, neighbours read from registers,
-// bit 8: no barrier per z-step
-#ifndef NS3D_ABL
-#define NS3D_ABL 0
-#endif
-#ifndef NS3D_PACK_F32
-#define NS3D_PACK_F32 1      /* fp32 two-row shapes of k_pt_sweepN: both rows through v_pk_* (A/B: -DNS3D_PACK_F32=0) */
-#endif
-#ifndef NS3D_LEVEL_SKIP
-#define NS3D_LEVEL_SKIP 0
-#endif
+    // every wave computes every level: skipping the levels none of a wave's rows needs (k_pt_sweepD's act[]) saved no time here
+    // (profiles/r4_levelskip_dma_ab.log (a)).  The array stays because the compiled kernels are not the same without it.
     bool act[NL + 1];
-    {
-        const int wyu = __builtin_amdgcn_readfirstlane(wy);
-        act[0] = act[1] = true;
+    act[0] = act[1] = true;
 #pragma unroll
-        for (int l = 2; l <= NL; ++l)
-            act[l] = !NS3D_LEVEL_SKIP || ((wyu * CPT + CPT - 1 >= l - 1 || tile_y_lo) && (wyu * CPT <= TY - l || tile_y_hi));
-    }
+    for (int l = 2; l <= NL; ++l) act[l] = true;
     // halo ring duties (P⁰ only): A = row below the tile, B = row above, C = the two columns beside it
     const bool hasA = (wy == 0), hasB = (wy == WY - 1), hasC = (tid < 2 * TY);
     const int offA = (oy - 1) * nx + ci;
@@ -2679,15 +2655,6 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
             const int kp = min(max(k1 + 2 + (AHEAD2 ? 1 : 0), 0), nz - 1);
             const int ka = min(max(k1 + 1 + (AHEAD2 ? 1 : 0), 1), nz - 2);
             const T *__restrict__ Pn = P + (idx_t)kp * sz;
-#ifdef NS3D_LOAD_PRIO       // A/B: the waves that are about to issue the next step's loads go first
-            __builtin_amdgcn_s_setprio(3);
-#endif
-#if NS3D_ABL & 1
-            (void)Pn; (void)ka;
-#pragma unroll
-            for (int r = 0; r < CPT; ++r) { p0n[r] = p0m[r]; d0n[r] = d0[r]; r0n[r] = rr[0][r]; }
-            hAn = hA; hBn = hB; hCn = hC;
-#else
 #pragma unroll
             for (int r = 0; r < CPT; ++r) {
                 p0n[r] = Pn[poff[r]];
@@ -2697,10 +2664,6 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
             if (hasA) hAn = Pn[offA];
             if (hasB) hBn = Pn[offB];
             if (hasC) hCn = Pn[offC];
-#endif
-#ifdef NS3D_LOAD_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         };
         if constexpr (EARLY) issue_next();
         // ---------------- level 1 at plane k1 ----------------
@@ -2716,7 +2679,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
             const T *__restrict__ l0 = L0[cur];
             auto level1 = [&](auto slow_tag) {
 #if NS3D_VEC2
-                if constexpr (NS3D_PACK_F32 && sizeof(T) == 4 && CPT == 2 && !decltype(slow_tag)::value) {
+                if constexpr (sizeof(T) == 4 && CPT == 2 && !decltype(slow_tag)::value) {
                     // fp32, two rows per thread: both rows through the packed instructions (same operations, same order per lane)
                     const int lr = wy * CPT;
                     const f32x2 c = mk2(p0c[0], p0c[1]);
@@ -2733,14 +2696,9 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
                 for (int r = 0; r < CPT; ++r) {
                     const int lr = wy * CPT + r;
                     const T c = p0c[r];
-#if NS3D_ABL & 4
-                    (void)lr; (void)l0;
-                    const T w = c * (T)0.5, e = c * (T)0.25, sv = p0m[r] * (T)0.5, nv = p0p[r] * (T)0.5;
-#else
                     const T w = l0[(lr + 1) * PX + lx], e = l0[(lr + 1) * PX + lx + 2];
                     const T sv = r == 0 ? l0[lr * PX + lx + 1] : p0c[r - 1 < 0 ? 0 : r - 1];
                     const T nv = r == CPT - 1 ? l0[(lr + 2) * PX + lx + 1] : p0c[r + 1 > CPT - 1 ? CPT - 1 : r + 1];
-#endif
                     const T res = decltype(slow_tag)::value
                                       ? poisson_rhs_slow<T>(c, w, e, sv, nv, p0m[r], p0p[r], rr[0][r], a.rho_dt, g)
                                       : poisson_rhs_nochk<T>(c, w, e, sv, nv, p0m[r], p0p[r], rr[0][r], a.rho_dt, g);
@@ -2758,7 +2716,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
             const int kl = k1 - (l - 1);
             T *__restrict__ npub = LN[l - 2][cur ^ 1];
             // publish Pˡ⁻¹ of the plane just produced (x/y neighbours of level l in the NEXT step)
-            if (act[l - 1] && (!(NS3D_ABL & 4) || a.nx < 0)) {
+            if (act[l - 1]) {
 #pragma unroll
                 for (int r = 0; r < CPT; ++r) npub[(wy * CPT + r) * TX + lx] = fresh[r];
             }
@@ -2773,7 +2731,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
                 const bool zlo = EDGE && (kl == 1), zhi = EDGE && (kl == nz - 2);
                 auto level = [&](auto slow_tag) {
 #if NS3D_VEC2
-                    if constexpr (NS3D_PACK_F32 && sizeof(T) == 4 && CPT == 2 && !decltype(slow_tag)::value) {
+                    if constexpr (sizeof(T) == 4 && CPT == 2 && !decltype(slow_tag)::value) {
                         // fp32, two rows per thread: operands gathered per row (boundary rule included), arithmetic on both rows at once
                         T cs[2], ws[2], es[2], ss[2], ns[2], bs[2], ts[2];
 #pragma unroll
@@ -2810,14 +2768,9 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
                     for (int r = 0; r < CPT; ++r) {
                         const int lr = wy * CPT + r;
                         const T c = pc[l - 2][r];
-#if NS3D_ABL & 4
-                        (void)ll;
-                        T w = c * (T)0.5, e = c * (T)0.25, sv = pm[l - 2][r] * (T)0.5, nv = fresh[r] * (T)0.5;
-#else
                         T w = ll[lr * TX + max(lx - 1, 0)], e = ll[lr * TX + min(lx + 1, TX - 1)];
                         T sv = r == 0 ? ll[max(lr - 1, 0) * TX + lx] : pc[l - 2][r - 1 < 0 ? 0 : r - 1];
                         T nv = r == CPT - 1 ? ll[min(lr + 1, TY - 1) * TX + lx] : pc[l - 2][r + 1 > CPT - 1 ? CPT - 1 : r + 1];
-#endif
                         T bv = pm[l - 2][r], tv = fresh[r];
                         if (tile_on_xy_face) {      // boundary rule substituted where the stencil touches a face of Pˡ⁻¹
                             const int gjf = oy + lr;
@@ -2843,7 +2796,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
                     T *__restrict__ Dk = D + (idx_t)(kl - 1) * dsz;
 #pragma unroll
                     for (int r = 0; r < CPT; ++r) {
-                        if (outc[r] && (!(NS3D_ABL & 2) || a.nx < 0)) {
+                        if (outc[r]) {
                             st_stream<T, true>(Dk + doff[r], out_d[r]);
                             const int gj = oy + wy * CPT + r;
                             T *__restrict__ po = a.Pout + (idx_t)kl * sz + gj * nx + gi;
@@ -2882,24 +2835,18 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
                     rr[0][r] = r0n[r];
                 } else {
                     (void)d0n; (void)r0n;
-#if NS3D_ABL & 1
-                    (void)ka; d0[r] = dnew[r]; rr[0][r] = rr[1][r];
-#else
                     d0[r] = ld_stream<T, true>(Din + (idx_t)(ka - 1) * dsz + doff[r]);
                     rr[0][r] = ld_stream<T, true>(RHS + (idx_t)ka * sz + roff[r]);
-#endif
                 }
             }
         }
         // ---------------- publish plane k1+1 of P⁰ ----------------
         T *__restrict__ n0 = L0[cur ^ 1];
-        if (!(NS3D_ABL & 4) || a.nx < 0) {
 #pragma unroll
         for (int r = 0; r < CPT; ++r) n0[(wy * CPT + r + 1) * PX + lx + 1] = p0p[r];
         if (hasA) n0[ldsA] = hA;
         if (hasB) n0[ldsB] = hB;
         if (hasC) n0[ldsC] = hC;
-        }
 #if NS3D_HAS_SLOW_PATH
         if (hasA) bad |= !val_ok<T>(hA);
         if (hasB) bad |= !val_ok<T>(hB);
@@ -2916,11 +2863,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
         for (int r = 0; r < CPT; ++r) { p0m[r] = p0c[r]; p0c[r] = p0p[r]; p0p[r] = p0n[r]; }
         hA = hAn; hB = hBn; hC = hCn;
         }
-#if defined(NS3D_NO_STEP_BARRIER) || (NS3D_ABL & 8)     // A/B (WRONG results): what the one barrier per z-step costs a CU that holds a single workgroup
-        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the wave's own LDS traffic only
-#else
         __syncthreads();
-#endif
         cur ^= 1;
     };
     // The z rings rotate every step (≈ 16 register-pair moves per row, a quarter of a step's vector instructions); with the
@@ -2930,7 +2873,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
     // the four-row 512-thread ones, none where three or more rows per thread already fill the register budget of a 768- or
     // 1024-thread workgroup (fp32 64×48: 34 registers would spill).
     // (4 is as good as 6 or 12; an ODD count is 15–35 % slower: the LDS double-buffer parity stops being a compile-time fact)
-    constexpr int UNR = NS3D_STEP_UNROLL > 0 ? NS3D_STEP_UNROLL : ((WX * WY >= 12 && CPT >= 3) ? 1 : (CPT <= 2 ? 4 : 2));
+    constexpr int UNR = (WX * WY >= 12 && CPT >= 3) ? 1 : (CPT <= 2 ? 4 : 2);
     int s = 0;
     if constexpr (UNR > 1) {
         // bulk steps [hot_lo, hot_hi): every level active, planes 2 … nz−3 for the levels that substitute z faces (ℓ ≥ 2)
@@ -2943,11 +2886,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
         if (s == h0)
             for (; s + UNR <= hot_hi; s += UNR) {
 #pragma unroll
-#ifdef NS3D_NO_EDGE_SPLIT      // A/B: the general step form in the bulk loop as well
-                for (int u = 0; u < UNR; ++u) step(s + u, std::true_type{});
-#else
                 for (int u = 0; u < UNR; ++u) step(s + u, std::false_type{});
-#endif
             }
     }
     for (; s < nsteps; ++s) step(s, std::true_type{});
@@ -3102,7 +3041,10 @@ __global__ __launch_bounds__(64 * WY) void k_pt_sweepD(SweepArgs<T> a, int ntx, 
         doff[r] = (cjj - 1) * (nx - 2) - 1;
         outr[r] = (gj <= ny - 2) && (lr >= NL - 1 || tile_y_lo) && (lr <= TY - NL || tile_y_hi);
     }
-    bool act[NL + 1];                        // wave-uniform level skipping, as in k_pt_sweepN
+    // Wave-uniform level skipping: level ℓ is exact on the rows ℓ−1 … TY−ℓ of a tile (all rows on a side that is a face of the
+    // domain); a wave none of whose CPT rows lies in that range computes nothing any valid row ever reads, so it skips level ℓ's
+    // arithmetic and the publish of its Pˡ (profiles/r4_levelskip_dma_ab.log)
+    bool act[NL + 1];
     act[0] = act[1] = true;
 #pragma unroll
     for (int l = 2; l <= NL; ++l) act[l] = (wyu * CPT + CPT - 1 >= l - 1 || tile_y_lo) && (wyu * CPT <= TY - l || tile_y_hi);
@@ -3227,9 +3169,6 @@ __global__ __launch_bounds__(64 * WY) void k_pt_sweepD(SweepArgs<T> a, int ntx, 
             for (int l = 2; l <= NL; ++l) {
                 const int kl = k1 - (l - 1);
                 T *__restrict__ npub = LN[l - 2][cur ^ 1];
-#ifdef NS3D_SCHED_FENCE      // keep the scheduler from interleaving the levels of the branch-free bulk step (register pressure)
-                __builtin_amdgcn_sched_barrier(0);
-#endif
                 if (act[l - 1]) {
 #pragma unroll
                     for (int r = 0; r < CPT; ++r) npub[lnb + r * TX + lx] = fresh[r];
@@ -3354,12 +3293,7 @@ __global__ __launch_bounds__(64 * WY) void k_pt_sweepD(SweepArgs<T> a, int ntx, 
         if (s == h0)
             for (; s + UNR <= hot_hi; s += UNR) {
 #pragma unroll
-                for (int u = 0; u < UNR; ++u)
-#ifdef NS3D_D_BULK_EDGE
-                    step(s + u, std::true_type{});
-#else
-                    step(s + u, std::false_type{});
-#endif
+                for (int u = 0; u < UNR; ++u) step(s + u, std::false_type{});
             }
     }
     for (; s < nsteps; ++s) step(s, std::true_type{});
@@ -3416,17 +3350,11 @@ template <class T>
 hipError_t pt_sweepn(hipStream_t s, int nlev, int variant, const T *Pin, T *Pout, const T *Din, T *Dout, const T *RHS,
                      const ns3d_pt_params &p, int k0, int k1, int pass_flags, const ns3d_tile_window *win)
 {
-    SweepArgs<T> a;
-    a.win = win; a.tx0 = a.ty0 = 0;
-    a.Pin = Pin; a.Pout = Pout; a.D = Dout; a.Din = Din; a.RHS = RHS;
-    a.g = make_geo<T>(p.dx, p.dy, p.dz);
-    a.rho_dt = (T)p.rho / (T)p.dt; a.dtau = (T)p.dtau; a.one_m_damp = (T)1.0 - (T)p.damp;
-    a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
-    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
-    a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = 0; a.zhi_halo = 0;
-    a.k0 = k0; a.k1 = k1; a.kz = 1;
+    SweepArgs<T> a = make_sweep_args<T>(p, Pin, Pout, Din, Dout, RHS, k0, k1);
+    a.zlo_halo = a.zhi_halo = 0;
+    a.win = win;
     a.no_faces = (pass_flags & NS3D_PASS_SKIP_FACES) ? 1 : 0;
-    a.cus_off = ((pass_flags >> 8) & 0xff) * 8;
+    a.cus_off = ns3d_pass_cus_off(pass_flags);
     if (k1 <= k0) return hipSuccess;
     int shape = variant / 100, kz = variant % 100;
     // built-in: 64×32 columns, next step's loads issued before level 1 (measured best at 512³ for three levels); four levels
@@ -3442,7 +3370,7 @@ hipError_t pt_sweepn(hipStream_t s, int nlev, int variant, const T *Pin, T *Pout
     case 16: NS3D_SWN(NLV, 1, 4, 4, true);                                                                  \
     case 22: if constexpr (sizeof(T) == 4) { NS3D_SWN(NLV, 1, 12, 4, true); } else return hipErrorInvalidValue; /* fp32: 64×48, 768 threads = three waves per SIMD */ \
     case 23: NS3D_SWN(NLV, 1, 12, 2, true);  /* 64×24, 768 threads, two rows per thread: three waves per SIMD */ \
-    case 24: if constexpr (sizeof(T) == 4 || NS3D_SHAPE24_F64) { NS3D_SWN(NLV, 1, 16, 2, true); } else return hipErrorInvalidValue; /* fp32: 64×32, 1024 threads = four waves per SIMD (fp64 spills: A/B with -DNS3D_SHAPE24_F64=1) */ \
+    case 24: if constexpr (sizeof(T) == 4) { NS3D_SWN(NLV, 1, 16, 2, true); } else return hipErrorInvalidValue; /* fp32: 64×32, 1024 threads = four waves per SIMD (fp64 spills at 128 registers per lane: profiles/r3_pace_order_ab.log §7) */ \
     case 25: if constexpr (sizeof(T) == 4) { NS3D_SWN(NLV, 1, 16, 2, 2); } else return hipErrorInvalidValue;   /* fp32 A/B: shape 24 with the loads two steps ahead */ \
     case 28: if (fold_wanted<T>(a)) return launch_sweepN<T, NLV, 1, 12, 2, false, 1, true>(s, a, kz);       /* small grids: boundary cells folded in */ \
              NS3D_SWN(NLV, 1, 12, 2, false);                                                                \
@@ -3490,17 +3418,11 @@ template <class T>
 hipError_t pt_sweep2(hipStream_t s, int variant, const T *Pin, T *Pout, const T *Din, T *Dout, const T *RHS,
                      const ns3d_pt_params &p, int k0, int k1, int pass_flags, const ns3d_tile_window *win)
 {
-    SweepArgs<T> a;
-    a.win = win; a.tx0 = a.ty0 = 0;
-    a.Pin = Pin; a.Pout = Pout; a.D = Dout; a.Din = Din; a.RHS = RHS;
-    a.g = make_geo<T>(p.dx, p.dy, p.dz);
-    a.rho_dt = (T)p.rho / (T)p.dt; a.dtau = (T)p.dtau; a.one_m_damp = (T)1.0 - (T)p.damp;
-    a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
-    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
-    a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = 0; a.zhi_halo = 0;
-    a.k0 = k0; a.k1 = k1; a.kz = 1;
+    SweepArgs<T> a = make_sweep_args<T>(p, Pin, Pout, Din, Dout, RHS, k0, k1);
+    a.zlo_halo = a.zhi_halo = 0;
+    a.win = win;
     a.no_faces = (pass_flags & NS3D_PASS_SKIP_FACES) ? 1 : 0;
-    a.cus_off = ((pass_flags >> 8) & 0xff) * 8;
+    a.cus_off = ns3d_pass_cus_off(pass_flags);
     if (k1 <= k0) return hipSuccess;
     int shape = variant / 100;
     int kz = variant % 100;
@@ -3890,15 +3812,9 @@ hipError_t pt_persist(hipStream_t s, const T *Pin, T *Pout, const T *Din, T *Dou
                       ns3d_persist_state *st, int pass_flags, int nchk, double eps, double err_mul, double err_div)
 {
     if (n_iters < 1 || n_iters > 60000 || p.z_lo_is_halo || p.z_hi_is_halo) return hipErrorInvalidValue;
-    SweepArgs<T> a;
-    a.Pin = Pin; a.Pout = Pout; a.D = Dout; a.Din = Din; a.RHS = RHS;
-    a.g = make_geo<T>(p.dx, p.dy, p.dz);
-    a.rho_dt = (T)p.rho / (T)p.dt; a.dtau = (T)p.dtau; a.one_m_damp = (T)1.0 - (T)p.damp;
-    a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
-    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
-    a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = 0; a.zhi_halo = 0;
-    a.k0 = 1; a.k1 = p.nz - 1; a.kz = 1; a.no_faces = 0; a.win = nullptr; a.tx0 = a.ty0 = 0;
-    a.cus_off = ((pass_flags >> 8) & 0xff) * 8;
+    SweepArgs<T> a = make_sweep_args<T>(p, Pin, Pout, Din, Dout, RHS, 1, p.nz - 1);
+    a.zlo_halo = a.zhi_halo = 0;        // refused above when `p` has either
+    a.cus_off = ns3d_pass_cus_off(pass_flags);
     // the iteration is arithmetic on the CUs the grid occupies plus one hand-over: the smallest workgroup the chip still holds
     // all at once spreads the cells over the most CUs.  NS3D_PERSIST_SHAPE=22|42|44 pins a shape (A/B).
     static const int pin = std::getenv("NS3D_PERSIST_SHAPE") ? std::atoi(std::getenv("NS3D_PERSIST_SHAPE")) : 0;
@@ -3915,14 +3831,7 @@ template <class T>
 hipError_t pt_sweep(hipStream_t s, int variant, const T *Pin, T *Pout, T *D, const T *RHS, const ns3d_pt_params &p,
                     int k0, int k1)
 {
-    SweepArgs<T> a;
-    a.Pin = Pin; a.Pout = Pout; a.D = D; a.Din = D; a.RHS = RHS;
-    a.g = make_geo<T>(p.dx, p.dy, p.dz);
-    a.rho_dt = (T)p.rho / (T)p.dt; a.dtau = (T)p.dtau; a.one_m_damp = (T)1.0 - (T)p.damp;
-    a.outlet_val = (T)p.outlet_val; a.rho_g = (T)p.rho * (T)p.g;
-    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
-    a.bc_kind = p.bc_kind; a.owns_outlet = p.owns_outlet; a.zlo_halo = p.z_lo_is_halo; a.zhi_halo = p.z_hi_is_halo;
-    a.k0 = k0; a.k1 = k1; a.kz = 1; a.no_faces = 0; a.cus_off = 0; a.win = nullptr; a.tx0 = a.ty0 = 0;
+    SweepArgs<T> a = make_sweep_args<T>(p, Pin, Pout, D, D, RHS, k0, k1);      // dPrdτ updated in place
     if (k1 <= k0) return hipSuccess;
     // variant = family*100 + kz  (kz = planes marched per block; 0 → default); variant 0 = choose by grid size:
     // grids whose four PT arrays stay resident in L2 / Infinity Cache run best with one thread per cell (neighbours are

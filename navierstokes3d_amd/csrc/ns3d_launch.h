@@ -12,6 +12,8 @@
 // pass_flags of pt_sweep2 / pt_sweepn: bit 1 — no boundary-cell launch behind the sweep; bits 8… — compute units (in eights) the stream's
 // CU mask leaves out (ns3d_reserve_cus), which the z-chunking must not count on
 #define NS3D_PASS_SKIP_FACES 2
+static inline int ns3d_pass_flags_cus(int reserved_cus) { return (reserved_cus / 8) << 8; }    // the CU field of pass_flags, and back:
+static inline int ns3d_pass_cus_off(int pass_flags) { return ((pass_flags >> 8) & 0xff) * 8; } // compute units to leave out
 #define NS3D_FACES_FOLDED 2             /* SweepArgs::no_faces: the sweep kernel forms the boundary cells itself (fold_faces) */
 #define NS3D_FOLD_MAX_CELLS 20000000L   /* … by default on grids up to this many cells */
 struct ns3d_tile_geom { int TX, TY, OV, ntx, nty; };      // columns × rows per tile, overlap 2(NL−1), tiles per plane

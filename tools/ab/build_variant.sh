@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B library with extra -D flags in the power-of-two STRICT kernel unit only (what bench.py's 512^3 default runs):
-#   tools/ab/build_variant.sh NAME "-DNS3D_COOP_EXP=1"   ->  tools/ab/libns3d_NAME.so   (use with NS3D_LIB=… or tools/ab/ab.sh)
+#   tools/ab/build_variant.sh NAME "-DNS3D_NONTEMPORAL"   ->  tools/ab/libns3d_NAME.so   (use with NS3D_LIB=… or tools/ab/ab.sh)
 set -e
 cd "$(dirname "$0")/../.."
 B=navierstokes3d_amd/build
