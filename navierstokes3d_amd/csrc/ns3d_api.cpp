@@ -1,7 +1,8 @@
 // ns3d_api.cpp — the extern "C" boundary of libns3d.so (see include/ns3d.h for the contract and the
 // reference file:line each entry point replaces).  Host-only logic: argument checks, mode dispatch
 // (strict / fast kernels), the context (stream, reduction scratch, ping-pong buffer) and the
-// pseudo-transient loop of multi.jl:458-471 / gpu.jl:126-137.
+// pseudo-transient loop of multi.jl:458-471 / gpu.jl:126-137.  The typed entry points (ns3d_<name>_f64 / _f32) are
+// ns3d_api_typed.h, included once per element type at the end of this file.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -414,44 +415,36 @@ static bool use_two(const ns3d_ctx *c, const ns3d_pt_params *p)
     return (long long)p->nx * p->ny * p->nz >= NS3D_TWO_MIN_CELLS;
 }
 
+// a scratch buffer of the context, grown to `need` bytes; whatever may still use the old one (either stream, a captured block) goes first
+static int ensure_scratch(ns3d_ctx *c, void *&buf, size_t &bytes, size_t need)
+{
+    if (bytes >= need) return NS3D_OK;
+    if (buf) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->own_stream));
+        c->clear_graphs();
+        HIPCHK(c, hipFree(buf));
+        buf = nullptr;
+        bytes = 0;
+    }
+    HIPCHK(c, hipMalloc(&buf, need));
+    bytes = need;
+    return NS3D_OK;
+}
+// its two uses: the second Pr buffer (every cell) and the second dPrdτ buffer (interior cells) of the PT loop
 template <class T>
 static int ensure_pingpong(ns3d_ctx *c, const ns3d_pt_params *p, T **buf)
 {
-    const size_t need = (size_t)p->nx * p->ny * p->nz * sizeof(T);
-    if (c->pingpong_bytes < need) {
-        if (c->pingpong) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->own_stream));
-            c->clear_graphs();
-            HIPCHK(c, hipFree(c->pingpong));
-            c->pingpong = nullptr;
-            c->pingpong_bytes = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->pingpong, need));
-        c->pingpong_bytes = need;
-    }
-    *buf = (T *)c->pingpong;
-    return NS3D_OK;
+    const int rc = ensure_scratch(c, c->pingpong, c->pingpong_bytes, (size_t)p->nx * p->ny * p->nz * sizeof(T));
+    if (!rc) *buf = (T *)c->pingpong;
+    return rc;
 }
-
 template <class T>
 static int ensure_pingpong_d(ns3d_ctx *c, const ns3d_pt_params *p, T **buf)
 {
-    const size_t need = (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T);
-    if (c->pingpong_d_bytes < need) {
-        if (c->pingpong_d) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->own_stream));
-            c->clear_graphs();
-            HIPCHK(c, hipFree(c->pingpong_d));
-            c->pingpong_d = nullptr;
-            c->pingpong_d_bytes = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->pingpong_d, need));
-        c->pingpong_d_bytes = need;
-    }
-    *buf = (T *)c->pingpong_d;
-    return NS3D_OK;
+    const int rc = ensure_scratch(c, c->pingpong_d, c->pingpong_d_bytes, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T));
+    if (!rc) *buf = (T *)c->pingpong_d;
+    return rc;
 }
 
 // ---- tile shape of the two-iteration sweep ------------------------------------------------------------------
@@ -761,11 +754,26 @@ NS3D_INST_INTERNAL(double)
 NS3D_INST_INTERNAL(float)
 #undef NS3D_INST_INTERNAL
 
+// The PT loop's buffers: Pr and dPrdτ as the next sweep reads them (src, dsrc) and where it writes them (dst, ddst).  ddst may be
+// null: the one-iteration sweep updates dPrdτ in place.
+template <class T>
+struct PtBufs {
+    T *src, *dst, *dsrc, *ddst;
+    void swap_p() { std::swap(src, dst); }
+    void swap_d() { std::swap(dsrc, ddst); }
+};
 template <class T>
 static bool use_persist(const ns3d_ctx *c, const ns3d_pt_params *p);
 template <class T>
-static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, T *&src, T *&dst, T *&dsrc, T *&ddst,
-                                const T *divV, const ns3d_pt_params *p, bool may_tune);
+static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, PtBufs<T> &b, const T *divV, const ns3d_pt_params *p,
+                                bool may_tune);
+// the same as a status: what both loops below do with a block, the first time and when they redo one
+template <class T>
+static int enqueue_block(ns3d_ctx *c, hipStream_t s, int n, bool two, PtBufs<T> &b, const T *divV, const ns3d_pt_params *p)
+{
+    const hipError_t e = enqueue_iters<T>(c, s, n, two, b, divV, p, true);
+    return e == hipSuccess ? NS3D_OK : fail(NS3D_ERR_HIP, "pt_sweep launch: %s", hipGetErrorString(e));
+}
 
 // n_iters fused sweeps, result left in Pr (one D2D copy when n_iters is odd).  With z halos the scratch
 // buffer's halo planes are seeded from Pr first (a sweep never writes them).
@@ -781,30 +789,27 @@ static int pt_iterate_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_p
     if (p->z_hi_is_halo)
         HIPCHK(c, hipMemcpyAsync(other + plane * (p->nz - 1), Pr + plane * (p->nz - 1), plane * sizeof(T),
                                  hipMemcpyDeviceToDevice, c->stream));
-    T *src = Pr, *dst = other;
-    T *dsrc = D, *ddst = nullptr;
+    PtBufs<T> b{Pr, other, D, nullptr};
     const bool two = use_two(c, p) && !p->z_lo_is_halo && !p->z_hi_is_halo && n_iters >= 2;
-    if (two && (rc = ensure_pingpong_d<T>(c, p, &ddst))) return rc;
+    if (two && (rc = ensure_pingpong_d<T>(c, p, &b.ddst))) return rc;
+    const PtBufs<T> in = b;                 // the block's inputs
     const unsigned ticket0 = c->persist.ticket;
-    hipError_t e = enqueue_iters<T>(c, c->stream, n_iters, two, src, dst, dsrc, ddst, divV, p, true);
-    if (e != hipSuccess) return fail(NS3D_ERR_HIP, "pt_sweep launch: %s", hipGetErrorString(e));
+    if ((rc = enqueue_block<T>(c, c->stream, n_iters, two, b, divV, p))) return rc;
     if (c->persist.ticket != ticket0) {
         // the block ran as ONE cooperative launch: before its result replaces the caller's arrays, make sure no hand-over timed out
         // (a stream synchronisation: these are launch-bound grids, the wait is the block itself); if one did, the inputs are
         // untouched — redo the block by launches (the cooperative form is off for this context from here on)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (persist_failed(c)) {
-            src = Pr; dst = other; dsrc = D; ddst = nullptr;
-            if (two && (rc = ensure_pingpong_d<T>(c, p, &ddst))) return rc;
-            e = enqueue_iters<T>(c, c->stream, n_iters, two, src, dst, dsrc, ddst, divV, p, true);
-            if (e != hipSuccess) return fail(NS3D_ERR_HIP, "pt_sweep launch: %s", hipGetErrorString(e));
+            b = in;
+            if ((rc = enqueue_block<T>(c, c->stream, n_iters, two, b, divV, p))) return rc;
         }
     }
-    if (dsrc != D)
-        HIPCHK(c, hipMemcpyAsync(D, dsrc, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T),
+    if (b.dsrc != D)
+        HIPCHK(c, hipMemcpyAsync(D, b.dsrc, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T),
                                  hipMemcpyDeviceToDevice, c->stream));
-    if (src != Pr)
-        HIPCHK(c, hipMemcpyAsync(Pr, src, plane * p->nz * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    if (b.src != Pr)
+        HIPCHK(c, hipMemcpyAsync(Pr, b.src, plane * p->nz * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
     return NS3D_OK;
 }
 
@@ -816,10 +821,10 @@ static bool bc_fused_enabled()
 }
 
 // ---- the PT loop of multi.jl:458-471 ----------------------------------------------------------------------
-// enqueue exactly n iterations on stream s (two per pass where allowed) and leave the result pointers in src/dsrc
+// enqueue exactly n iterations on stream s (two per pass where allowed) and leave the result pointers in b.src / b.dsrc
 template <class T>
-static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, T *&src, T *&dst, T *&dsrc, T *&ddst,
-                                const T *divV, const ns3d_pt_params *p, bool may_tune)
+static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, PtBufs<T> &b, const T *divV, const ns3d_pt_params *p,
+                                bool may_tune)
 {
     hipError_t e = hipSuccess;
     // small grids: the whole block of n iterations in one cooperative launch (k_pt_persist), where it applies
@@ -827,13 +832,13 @@ static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, T *
         // outputs in buffers of their own (dPrdτ too): a launch whose bounded waits expire — its workgroups were not all resident at
         // once: another context or process on the device — leaves the block's inputs intact, and whoever synchronises the stream
         // next (persist_failed below) redoes the block by launches
-        T *dout = ddst;
+        T *dout = b.ddst;
         if (!dout && ensure_pingpong_d<T>(c, p, &dout) != NS3D_OK) return hipErrorOutOfMemory;
-        e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, n, &c->persist, ns3d_pass_flags_cus(c->reserved_cus)));
+        e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_persist<T>(s, b.src, b.dst, b.dsrc, dout, divV, *p, n, &c->persist, ns3d_pass_flags_cus(c->reserved_cus)));
         if (e == hipSuccess) {
-            T *t = src; src = dst; dst = t;
-            if (ddst) { t = dsrc; dsrc = ddst; ddst = t; }
-            else { ddst = dsrc; dsrc = dout; }       // the caller had no second dPrdτ buffer: it has one now (copied back at the end)
+            b.swap_p();
+            if (b.ddst) b.swap_d();
+            else { b.ddst = b.dsrc; b.dsrc = dout; } // the caller had no second dPrdτ buffer: it has one now (copied back at the end)
             return e;
         }
         if (e != hipErrorInvalidValue) return e;     // invalid value: the form does not apply here → the ordinary path
@@ -842,16 +847,16 @@ static hipError_t enqueue_iters(ns3d_ctx *c, hipStream_t s, int n, bool two, T *
     }
     Plan pl{2, 0, 0, true};
     if (two && n >= 2)
-        pl = pick_plan<T>(c, s, mode_of(c, p->dx, p->dy, p->dz), src, dst, dsrc, ddst, divV, p, 1, p->nz - 1, may_tune);
+        pl = pick_plan<T>(c, s, mode_of(c, p->dx, p->dy, p->dz), b.src, b.dst, b.dsrc, b.ddst, divV, p, 1, p->nz - 1, may_tune);
     for (int it = 0; it < n && e == hipSuccess;) {
         const int d = next_depth(pl, two, n - it);
         if (d >= 2) {
-            e = launch_pass<T>(c, s, d, pl, src, dst, dsrc, ddst, divV, p, 1, p->nz - 1);
-            T *t = dsrc; dsrc = ddst; ddst = t;
+            e = launch_pass<T>(c, s, d, pl, b.src, b.dst, b.dsrc, b.ddst, divV, p, 1, p->nz - 1);
+            b.swap_d();
         } else
-            e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_sweep<T>(s, c->pt_variant, src, dst, dsrc, divV, *p, 1, p->nz - 1));
+            e = DISPATCHG(c, p->dx, p->dy, p->dz, pt_sweep<T>(s, c->pt_variant, b.src, b.dst, b.dsrc, divV, *p, 1, p->nz - 1));
         it += d;
-        T *t = src; src = dst; dst = t;
+        b.swap_p();
     }
     return e;
 }
@@ -864,30 +869,33 @@ static bool same_pt_params(const ns3d_pt_params &a, const ns3d_pt_params &b)
            a.nx == b.nx && a.ny == b.ny && a.nz == b.nz && a.bc_kind == b.bc_kind && a.owns_outlet == b.owns_outlet &&
            a.outlet_val == b.outlet_val && a.g == b.g && a.z_lo_is_halo == b.z_lo_is_halo && a.z_hi_is_halo == b.z_hi_is_halo;
 }
+template <class T>
+static bool same_bufs(const ns3d_ctx::BlockGraph::Bufs &a, const PtBufs<T> &b)
+{
+    return a.src == b.src && a.dst == b.dst && a.dsrc == b.dsrc && a.ddst == b.ddst;
+}
 
 // One residual-check block (nchk iterations) as a HIP graph: launch-bound grids (63×38×38: ≈2 µs of kernel per ≈5 µs
 // launch) replay the whole block with one host call.  Graphs are cached per buffer state in the context.
 template <class T>
-static int run_block_graph(ns3d_ctx *c, hipStream_t s, int n, bool two, T *&src, T *&dst, T *&dsrc, T *&ddst,
-                           const T *divV, const ns3d_pt_params *p)
+static int run_block_graph(ns3d_ctx *c, hipStream_t s, int n, bool two, PtBufs<T> &b, const T *divV, const ns3d_pt_params *p)
 {
     const int mode = mode_of(c, p->dx, p->dy, p->dz);
     for (auto &g : c->graphs)
-        if (g.src == src && g.dst == dst && g.dsrc == dsrc && g.ddst == ddst && g.rhs == divV && g.n == n && g.two == two &&
-            g.mode == mode && g.v1 == c->pt_variant && g.v2 == c->pt2_variant && g.vn == c->ptn_variant && g.depth == c->pt_depth &&
-            g.esize == (int)sizeof(T) &&
+        if (same_bufs(g.in, b) && g.rhs == divV && g.n == n && g.two == two && g.mode == mode && g.v1 == c->pt_variant &&
+            g.v2 == c->pt2_variant && g.vn == c->ptn_variant && g.depth == c->pt_depth && g.esize == (int)sizeof(T) &&
             same_pt_params(g.p, *p)) {
             HIPCHK(c, hipGraphLaunch(g.exec, s));
-            src = (T *)g.src_out; dst = (T *)g.dst_out; dsrc = (T *)g.dsrc_out; ddst = (T *)g.ddst_out;
+            b = {(T *)g.out.src, (T *)g.out.dst, (T *)g.out.dsrc, (T *)g.out.ddst};
             return NS3D_OK;
         }
     if (c->graphs.size() >= 16) c->clear_graphs();
     ns3d_ctx::BlockGraph g;
-    g.src = src; g.dst = dst; g.dsrc = dsrc; g.ddst = ddst; g.rhs = divV; g.n = n; g.two = two; g.mode = mode;
+    g.in = {b.src, b.dst, b.dsrc, b.ddst}; g.rhs = divV; g.n = n; g.two = two; g.mode = mode;
     g.v1 = c->pt_variant; g.v2 = c->pt2_variant; g.vn = c->ptn_variant; g.depth = c->pt_depth; g.esize = (int)sizeof(T); g.p = *p;
     hipGraph_t graph = nullptr;
     HIPCHK(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hipError_t e = enqueue_iters<T>(c, s, n, two, src, dst, dsrc, ddst, divV, p, false);
+    hipError_t e = enqueue_iters<T>(c, s, n, two, b, divV, p, false);
     hipError_t e2 = hipStreamEndCapture(s, &graph);
     if (e != hipSuccess || e2 != hipSuccess) {
         if (graph) (void)hipGraphDestroy(graph);
@@ -896,7 +904,7 @@ static int run_block_graph(ns3d_ctx *c, hipStream_t s, int n, bool two, T *&src,
     e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(NS3D_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-    g.src_out = src; g.dst_out = dst; g.dsrc_out = dsrc; g.ddst_out = ddst;
+    g.out = {b.src, b.dst, b.dsrc, b.ddst};
     c->graphs.push_back(g);
     HIPCHK(c, hipGraphLaunch(g.exec, s));
     return NS3D_OK;
@@ -936,12 +944,11 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
     int rc = ensure_pingpong<T>(c, p, &other);
     if (rc) return rc;
     const size_t plane = (size_t)p->nx * p->ny;
-    T *src = Pr, *dst = other;
+    PtBufs<T> b{Pr, other, D, nullptr};
     int checks = 0, iter = 0, done = niter;
     bool converged = false;
     const bool two = use_two(c, p) && niter >= 2;
-    T *dsrc = D, *ddst = nullptr;
-    if (two && (rc = ensure_pingpong_d<T>(c, p, &ddst))) return rc;
+    if (two && (rc = ensure_pingpong_d<T>(c, p, &b.ddst))) return rc;
     // graphs cannot be captured on HIP's null stream: run the loop on the context's own stream, fenced by events
     const bool graphs = use_graphs<T>(c, p, nchk);
     hipStream_t s = c->stream;
@@ -953,17 +960,17 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
     }
     // settle the tile choice of the two-iteration sweep now (eagerly, into the scratch buffers): inside a stream capture
     // it could only be looked up
-    if (two) (void)pick_plan<T>(c, s, mode_of(c, p->dx, p->dy, p->dz), src, dst, dsrc, ddst, divV, p, 1, p->nz - 1, true);
+    if (two) (void)pick_plan<T>(c, s, mode_of(c, p->dx, p->dy, p->dz), b.src, b.dst, b.dsrc, b.ddst, divV, p, 1, p->nz - 1, true);
     // Small grids (round 4): the WHOLE loop — iterations, residual checks, the decision of :467-469 — as one launch of k_pt_persist.  The
     // checks' maxima come back through pinned host memory behind one synchronisation; a launch whose bounded waits expired left its
     // inputs intact and the loop below redoes the solve by launches.  NS3D_PERSIST_SOLVE=0: a launch per residual-check block (A/B).
     const char *wv = std::getenv("NS3D_PERSIST_SOLVE");         // read per solve: tests flip it
     const bool whole = !(wv && *wv == '0');
     if (whole && nchk > 0 && niter >= nchk && niter / nchk <= NS3D_PERSIST_MAXCHK && use_persist<T>(c, p)) {
-        T *dout = ddst;
+        T *dout = b.ddst;
         if (!dout && (rc = ensure_pingpong_d<T>(c, p, &dout))) return rc;
         hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz,
-                                 pt_persist<T>(s, src, dst, dsrc, dout, divV, *p, niter, &c->persist, ns3d_pass_flags_cus(c->reserved_cus), nchk, eps,
+                                 pt_persist<T>(s, b.src, b.dst, b.dsrc, dout, divV, *p, niter, &c->persist, ns3d_pass_flags_cus(c->reserved_cus), nchk, eps,
                                                err_mul, err_div));
         if (e == hipSuccess) {
             HIPCHK(c, hipStreamSynchronize(s));
@@ -976,7 +983,7 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
                     std::memcpy(&mx, &res[2 + q], sizeof mx);
                     err_hist[q] = mx * err_mul / err_div;
                 }
-                src = dst; dsrc = dout;
+                b.src = b.dst; b.dsrc = dout;
                 iter = niter;                   // nothing left for the loop below
             }
         } else if (e != hipErrorInvalidValue)
@@ -987,30 +994,24 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
     while (iter < niter) {
         // iterations until the next residual check (multi.jl:464) or the end of the budget
         const int n = nchk > 0 ? std::min(nchk - iter % nchk, niter - iter) : niter - iter;
-        T *const in_src = src, *const in_dst = dst, *const in_dsrc = dsrc, *const in_ddst = ddst;     // the block's inputs
+        const PtBufs<T> in = b;                 // the block's inputs
         const unsigned ticket0 = c->persist.ticket;
-        if (graphs && n == nchk) {
-            if ((rc = run_block_graph<T>(c, s, n, two, src, dst, dsrc, ddst, divV, p))) return rc;
-        } else {
-            hipError_t e = enqueue_iters<T>(c, s, n, two, src, dst, dsrc, ddst, divV, p, true);
-            if (e != hipSuccess) return fail(NS3D_ERR_HIP, "pt_sweep launch: %s", hipGetErrorString(e));
-        }
+        if ((rc = graphs && n == nchk ? run_block_graph<T>(c, s, n, two, b, divV, p) : enqueue_block<T>(c, s, n, two, b, divV, p))) return rc;
         iter += n;
         const bool check_now = nchk > 0 && iter % nchk == 0;
         if (c->persist.ticket != ticket0 && !check_now) HIPCHK(c, hipStreamSynchronize(s));     // a last, partial block: no read-back follows
         for (int attempt = 0; attempt < 2; ++attempt) {
             double mx = 0.0;
             if (check_now) { // multi.jl:464-469
-                hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, residual_max_key<T>(s, src, divV, *p, c->key_dev));
+                hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, residual_max_key<T>(s, b.src, divV, *p, c->key_dev));
                 if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));
                 if ((rc = fetch_key(c, s, &mx))) return rc;
             }
             // the read-back synchronised the stream: if the block ran as one cooperative launch and a hand-over in it timed out, its
             // inputs are still there — redo it by launches (once; the cooperative form is off for this context afterwards)
             if (attempt == 0 && c->persist.ticket != ticket0 && persist_failed(c)) {
-                src = in_src; dst = in_dst; dsrc = in_dsrc; ddst = in_ddst;
-                hipError_t e = enqueue_iters<T>(c, s, n, two, src, dst, dsrc, ddst, divV, p, true);
-                if (e != hipSuccess) return fail(NS3D_ERR_HIP, "pt_sweep launch: %s", hipGetErrorString(e));
+                b = in;
+                if ((rc = enqueue_block<T>(c, s, n, two, b, divV, p))) return rc;
                 continue;
             }
             if (!check_now) break;
@@ -1022,10 +1023,10 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
         }
         if (converged) break;
     }
-    if (src != Pr)
-        HIPCHK(c, hipMemcpyAsync(Pr, src, plane * p->nz * sizeof(T), hipMemcpyDeviceToDevice, s));
-    if (dsrc != D)
-        HIPCHK(c, hipMemcpyAsync(D, dsrc, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T),
+    if (b.src != Pr)
+        HIPCHK(c, hipMemcpyAsync(Pr, b.src, plane * p->nz * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (b.dsrc != D)
+        HIPCHK(c, hipMemcpyAsync(D, b.dsrc, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T),
                                  hipMemcpyDeviceToDevice, s));
     if (fenced) {
         HIPCHK(c, hipEventRecord(c->fence, s));
@@ -1036,407 +1037,31 @@ static int pt_solve_impl(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_
     return NS3D_OK;
 }
 
-#define NS3D_DEFINE(T, S)                                                                                    \
-    extern "C" int ns3d_update_tau_##S(ns3d_ctx *c, T *txx, T *tyy, T *tzz, T *txy, T *txz, T *tyz,          \
-                                       const T *Vx, const T *Vy, const T *Vz, double mu, double dx,          \
-                                       double dy, double dz, int nx, int ny, int nz)                         \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 2);       \
-        return finish(c, DISPATCHG(c, dx, dy, dz, update_tau<T>(c->stream, txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu,  \
-                                                   dx, dy, dz, nx, ny, nz)), "update_tau");                  \
-    }                                                                                                        \
-    extern "C" int ns3d_predict_V_##S(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *txx, const T *tyy,          \
-                                      const T *tzz, const T *txy, const T *txz, const T *tyz, double rho,    \
-                                      double g, double dt, double dx, double dy, double dz, int nx, int ny,  \
-                                      int nz)                                                                \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, txx, tyy, tzz, txy, txz, tyz); CHECK_GRID(nx, ny, nz, 2);       \
-        return finish(c, DISPATCHG(c, dx, dy, dz, predict_V<T>(c->stream, Vx, Vy, Vz, txx, tyy, tzz, txy, txz, tyz, rho,  \
-                                                  g, dt, dx, dy, dz, nx, ny, nz)), "predict_V");             \
-    }                                                                                                        \
-    extern "C" int ns3d_predict_fused_##S(ns3d_ctx *c, T *Vx_new, T *Vy_new, T *Vz_new, const T *Vx, const T *Vy, \
-                                          const T *Vz, double mu, double rho, double g, double dt, double dx, \
-                                          double dy, double dz, int nx, int ny, int nz)                      \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx_new, Vy_new, Vz_new, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 2);             \
-        if (Vx_new == Vx || Vy_new == Vy || Vz_new == Vz)                                                    \
-            return fail(NS3D_ERR_ARG, "ns3d_predict_fused: the predicted velocities need buffers of their own"); \
-        return finish(c, DISPATCHG(c, dx, dy, dz, predict_fused<T>(c->stream, Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu, rho, \
-                                                  g, dt, dx, dy, dz, nx, ny, nz)), "predict_fused");         \
-    }                                                                                                        \
-    extern "C" int ns3d_set_cylinder_##S(ns3d_ctx *c, T *C, T *Vx, T *Vy, T *Vz, double a2, double b2,       \
-                                         double ox, double oy, double sinb, double cosb, double xco_g,       \
-                                         double yco_g, double zco_g, double lx, double ly, double lz,        \
-                                         double dx, double dy, double dz, int nx, int ny, int nz)            \
-    {                                                                                                        \
-        (void)zco_g; (void)lz; (void)dz;                                                                     \
-        CHECK_CTX(c); CHECK_PTRS(C, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 1);                                  \
-        return finish(c, DISPATCH(c, set_cylinder<T>(c->stream, C, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb,   \
-                                                     0, xco_g, yco_g, lx, ly, dx, dy, nx, ny, nz)),          \
-                      "set_cylinder");                                                                       \
-    }                                                                                                        \
-    extern "C" int ns3d_set_cylinder_local_##S(ns3d_ctx *c, T *C, T *Vx, T *Vy, T *Vz, double a2, double b2, \
-                                               double ox, double oy, double sinb, double cosb, double lx,    \
-                                               double ly, double lz, double dx, double dy, double dz,        \
-                                               int nx, int ny, int nz)                                       \
-    {                                                                                                        \
-        (void)lz; (void)dz;                                                                                  \
-        CHECK_CTX(c); CHECK_PTRS(C, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 1);                                  \
-        return finish(c, DISPATCH(c, set_cylinder<T>(c->stream, C, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb,   \
-                                                     1, 0.0, 0.0, lx, ly, dx, dy, nx, ny, nz)),              \
-                      "set_cylinder_local");                                                                 \
-    }                                                                                                        \
-    extern "C" int ns3d_update_divV_##S(ns3d_ctx *c, T *divV, const T *Vx, const T *Vy, const T *Vz,         \
-                                        double dx, double dy, double dz, int nx, int ny, int nz)             \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(divV, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 1);                               \
-        return finish(c, DISPATCHG(c, dx, dy, dz, update_divV<T>(c->stream, divV, Vx, Vy, Vz, dx, dy, dz, nx, ny, nz)),   \
-                      "update_divV");                                                                        \
-    }                                                                                                        \
-    extern "C" int ns3d_update_dPrdtau_##S(ns3d_ctx *c, const T *Pr, T *dPrdtau, const T *divV, double rho,  \
-                                           double dt, double dtau, double damp, double dx, double dy,        \
-                                           double dz, int nx, int ny, int nz)                                \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr, dPrdtau, divV); CHECK_GRID(nx, ny, nz, 3);                              \
-        return finish(c, DISPATCHG(c, dx, dy, dz, update_dPrdtau<T>(c->stream, Pr, dPrdtau, divV, rho, dt, dtau, damp,    \
-                                                       dx, dy, dz, nx, ny, nz)), "update_dPrdtau");          \
-    }                                                                                                        \
-    extern "C" int ns3d_update_Pr_##S(ns3d_ctx *c, T *Pr, const T *dPrdtau, double dtau, int nx, int ny,     \
-                                      int nz)                                                                \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr, dPrdtau); CHECK_GRID(nx, ny, nz, 3);                                    \
-        return finish(c, DISPATCH(c, update_Pr<T>(c->stream, Pr, dPrdtau, dtau, nx, ny, nz)), "update_Pr");  \
-    }                                                                                                        \
-    extern "C" int ns3d_compute_res_##S(ns3d_ctx *c, T *Rp, const T *Pr, const T *divV, double rho,          \
-                                        double dt, double dx, double dy, double dz, int nx, int ny, int nz)  \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Rp, Pr, divV); CHECK_GRID(nx, ny, nz, 3);                                   \
-        return finish(c, DISPATCHG(c, dx, dy, dz, compute_res<T>(c->stream, Rp, Pr, divV, rho, dt, dx, dy, dz, nx, ny,    \
-                                                    nz)), "compute_res");                                    \
-    }                                                                                                        \
-    extern "C" int ns3d_max_abs_##S(ns3d_ctx *c, const T *A, long n, double *out_host)                       \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(A, out_host);                                                               \
-        if (n < 0) return fail(NS3D_ERR_ARG, "ns3d_max_abs: negative length");                               \
-        hipError_t e = DISPATCH(c, max_abs_key<T>(c->stream, A, n, c->key_dev));                             \
-        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "max_abs launch: %s", hipGetErrorString(e));          \
-        return fetch_key(c, c->stream, out_host);                                                                       \
-    }                                                                                                        \
-    extern "C" int ns3d_diagnostics_##S(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const T *Pr, const T *C, \
-                                        const ns3d_diag_params *p, ns3d_diag *out_host)                      \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, out_host);                                                      \
-        int rc = ns3d_diag_check(p, "ns3d_diagnostics");                                                     \
-        if (rc) return rc;                                                                                   \
-        rc = ns3d_diag_enqueue<T>(c, Vx, Vy, Vz, Pr, C, p);                                                  \
-        if (rc) return rc;                                                                                   \
-        HIPCHK(c, hipStreamSynchronize(c->stream));                                                          \
-        ns3d_diag_decode(c->diag_host, p, Pr != nullptr, C != nullptr, out_host);                            \
-        return NS3D_OK;                                                                                      \
-    }                                                                                                        \
-    extern "C" int ns3d_stats_accumulate_##S(ns3d_ctx *c, double *St, const T *Vx, const T *Vy, const T *Vz, const T *Pr, \
-                                             double weight, int nx, int ny, int nz)                          \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(St, Vx, Vy, Vz);                                                            \
-        const int rc = stats_grid_check(nx, ny, nz, "ns3d_stats_accumulate");                                \
-        if (rc) return rc;                                                                                   \
-        if (!std::isfinite(weight)) return fail(NS3D_ERR_ARG, "ns3d_stats_accumulate: weight = %g is not finite", weight); \
-        return finish(c, DISPATCH(c, stats_accumulate<T>(c->stream, St, Vx, Vy, Vz, Pr, weight, nx, ny, nz)), \
-                      "stats_accumulate");                                                                   \
-    }                                                                                                        \
-    extern "C" int ns3d_correct_V_##S(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *Pr, double dt, double rho,  \
-                                      double dx, double dy, double dz, int nx, int ny, int nz)               \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, Pr); CHECK_GRID(nx, ny, nz, 2);                                 \
-        return finish(c, DISPATCHG(c, dx, dy, dz, correct_V<T>(c->stream, Vx, Vy, Vz, Pr, dt, rho, dx, dy, dz, nx, ny,    \
-                                                  nz)), "correct_V");                                        \
-    }                                                                                                        \
-    static int bc_##S(ns3d_ctx *c, int which, T *A, int sx, int sy, int sz, double a, double b, int nz_arg,  \
-                      const char *name)                                                                      \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(A);                                                                         \
-        if (sx < 2 || sy < 2 || sz < 2) return fail(NS3D_ERR_ARG, "%s: extents %dx%dx%d too small", name,    \
-                                                    sx, sy, sz);                                             \
-        return finish(c, DISPATCH(c, bc_plane<T>(c->stream, which, A, sx, sy, sz, a, b, 0.0, nz_arg)), name);\
-    }                                                                                                        \
-    extern "C" int ns3d_bc_x_##S(ns3d_ctx *c, T *A, int sx, int sy, int sz) { return bc_##S(c, 0, A, sx, sy, sz, 0, 0, 0, "bc_x"); } \
-    extern "C" int ns3d_bc_y_##S(ns3d_ctx *c, T *A, int sx, int sy, int sz) { return bc_##S(c, 1, A, sx, sy, sz, 0, 0, 0, "bc_y"); } \
-    extern "C" int ns3d_bc_z_##S(ns3d_ctx *c, T *A, int sx, int sy, int sz) { return bc_##S(c, 2, A, sx, sy, sz, 0, 0, 0, "bc_z"); } \
-    extern "C" int ns3d_bc_zV_##S(ns3d_ctx *c, T *A, int sx, int sy, int sz) { return bc_##S(c, 3, A, sx, sy, sz, 0, 0, 0, "bc_zV"); } \
-    extern "C" int ns3d_bc_xhydstatic_##S(ns3d_ctx *c, T *A, double dz, int nz, double g, double rho,        \
-                                          int sx, int sy, int sz)                                            \
-    {                                                                                                        \
-        return bc_##S(c, 4, A, sx, sy, sz, (double)((T)rho * (T)g), dz, nz, "bc_xhydstatic");                \
-    }                                                                                                        \
-    extern "C" int ns3d_bc_x_Vx_##S(ns3d_ctx *c, T *A, double V, int sx, int sy, int sz) { return bc_##S(c, 5, A, sx, sy, sz, V, 0, 0, "bc_x_Vx"); } \
-    extern "C" int ns3d_bc_x_Pr_##S(ns3d_ctx *c, T *A, double v, int sx, int sy, int sz) { return bc_##S(c, 6, A, sx, sy, sz, v, 0, 0, "bc_x_Pr"); } \
-    extern "C" int ns3d_copy_##S(ns3d_ctx *c, T *dst, const T *src, long n)                                  \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(dst, src);                                                                  \
-        if (n < 0) return fail(NS3D_ERR_ARG, "ns3d_copy: negative length");                                  \
-        return finish(c, hipMemcpyAsync(dst, src, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, c->stream),\
-                      "copy");                                                                               \
-    }                                                                                                        \
-    extern "C" int ns3d_advect_##S(ns3d_ctx *c, T *Vx, const T *Vx_o, T *Vy, const T *Vy_o, T *Vz,           \
-                                   const T *Vz_o, T *C, const T *C_o, double dt, double dx, double dy,       \
-                                   double dz, int nx, int ny, int nz, int faithful)                          \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx, Vx_o, Vy, Vy_o, Vz, Vz_o, C, C_o); CHECK_GRID(nx, ny, nz, 1);           \
-        return finish(c, DISPATCHG(c, dx, dy, dz, advect<T>(c->stream, Vx, Vx_o, Vy, Vy_o, Vz, Vz_o, C, C_o, dt, dx, dy,  \
-                                               dz, nx, ny, nz, faithful ? 1 : 0, 0, 0)), "advect");                        \
-    }                                                                                                        \
-    extern "C" int ns3d_copy_advect_##S(ns3d_ctx *c, T *Vx_new, const T *Vx, T *Vy_new, const T *Vy, T *Vz_new, \
-                                        const T *Vz, T *C_new, const T *C, double dt, double dx, double dy,  \
-                                        double dz, int nx, int ny, int nz, int faithful)                     \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx_new, Vx, Vy_new, Vy, Vz_new, Vz, C_new, C); CHECK_GRID(nx, ny, nz, 1);   \
-        if (Vx_new == Vx || Vy_new == Vy || C_new == C || (!faithful && Vz_new == Vz))                       \
-            return fail(NS3D_ERR_ARG, "ns3d_copy_advect: outputs must be buffers of their own (only Vz_new may be Vz, and only " \
-                                      "in faithful mode, where Vz is never advected)");                      \
-        return finish(c, DISPATCHG(c, dx, dy, dz, advect<T>(c->stream, Vx_new, Vx, Vy_new, Vy, Vz_new, Vz, C_new, C, dt, dx, dy, \
-                                               dz, nx, ny, nz, (faithful ? 1 : 0) | 2, 0, 0)), "copy_advect");     \
-    }                                                                                                        \
-    extern "C" int ns3d_set_bc_Pr_##S(ns3d_ctx *c, T *Pr, int bc_kind, int owns_outlet, double outlet_val,   \
-                                      double dz, int nz_arg, double g, double rho, int nx, int ny, int nz)   \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr); CHECK_GRID(nx, ny, nz, 2);                                             \
-        hipError_t e = hipSuccess;                                                                           \
-        hipStream_t s = c->stream;                                                                           \
-        if (bc_kind != NS3D_BC_MULTI && bc_kind != NS3D_BC_GPU) return fail(NS3D_ERR_ARG, "ns3d_set_bc_Pr: bad bc_kind %d", bc_kind); \
-        if (bc_fused_enabled()) {       /* the whole sequence as one gather launch (k_bc_fused) */          \
-            e = DISPATCH(c, bc_fused<T>(s, 1, bc_kind, Pr, (T *)nullptr, (T *)nullptr, nx, ny, nz, owns_outlet, outlet_val, \
-                                        (double)((T)rho * (T)g), dz, nz_arg));                               \
-            if (e != hipErrorInvalidValue) return finish(c, e, "set_bc_Pr");                                 \
-            (void)hipGetLastError();                                                                         \
-            e = hipSuccess;                                                                                  \
-        }                                                                                                    \
-        if (bc_kind == NS3D_BC_MULTI) { /* multi.jl:176-181 */                                               \
-            e = DISPATCH(c, bc_plane<T>(s, 0, Pr, nx, ny, nz, 0, 0, 0, 0));                                  \
-            if (e == hipSuccess) e = DISPATCH(c, bc_plane<T>(s, 1, Pr, nx, ny, nz, 0, 0, 0, 0));             \
-            if (e == hipSuccess) e = DISPATCH(c, bc_plane<T>(s, 2, Pr, nx, ny, nz, 0, 0, 0, 0));             \
-            if (e == hipSuccess && owns_outlet) e = DISPATCH(c, bc_plane<T>(s, 6, Pr, nx, ny, nz, outlet_val, 0, 0, 0)); \
-        } else if (bc_kind == NS3D_BC_GPU) { /* gpu.jl:282-284 */                                            \
-            e = DISPATCH(c, bc_plane<T>(s, 1, Pr, nx, ny, nz, 0, 0, 0, 0));                                  \
-            if (e == hipSuccess) e = DISPATCH(c, bc_plane<T>(s, 2, Pr, nx, ny, nz, 0, 0, 0, 0));             \
-            if (e == hipSuccess) e = DISPATCH(c, bc_plane<T>(s, 4, Pr, nx, ny, nz, (double)((T)rho * (T)g), dz, 0, nz_arg)); \
-        } else return fail(NS3D_ERR_ARG, "ns3d_set_bc_Pr: bad bc_kind %d", bc_kind);                         \
-        return finish(c, e, "set_bc_Pr");                                                                    \
-    }                                                                                                        \
-    extern "C" int ns3d_set_bc_Vel_##S(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, int bc_kind, int owns_inlet,        \
-                                       double vin, int nx, int ny, int nz)                                   \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 2);                                     \
-        hipStream_t s = c->stream;                                                                           \
-        hipError_t e = hipSuccess;                                                                           \
-        if (bc_kind != NS3D_BC_MULTI && bc_kind != NS3D_BC_GPU) return fail(NS3D_ERR_ARG, "ns3d_set_bc_Vel: bad bc_kind %d", bc_kind); \
-        if (bc_fused_enabled()) {       /* the whole sequence as one gather launch (k_bc_fused) */          \
-            e = DISPATCH(c, bc_fused<T>(s, 0, bc_kind, Vx, Vy, Vz, nx, ny, nz, bc_kind == NS3D_BC_MULTI && owns_inlet, vin, 0.0, 0.0, 0)); \
-            if (e != hipErrorInvalidValue) return finish(c, e, "set_bc_Vel");                                \
-            (void)hipGetLastError();                                                                         \
-            e = hipSuccess;                                                                                  \
-        }                                                                                                    \
-        struct { int which; T *A; int sx, sy, sz; } seq[9];                                                  \
-        int n = 0;                                                                                           \
-        if (bc_kind == NS3D_BC_MULTI) { /* multi.jl:157-163 */                                               \
-            seq[n++] = {0, Vx, nx + 1, ny, nz}; seq[n++] = {1, Vx, nx + 1, ny, nz}; seq[n++] = {2, Vx, nx + 1, ny, nz}; \
-            seq[n++] = {0, Vy, nx, ny + 1, nz}; seq[n++] = {2, Vy, nx, ny + 1, nz};                          \
-            seq[n++] = {0, Vz, nx, ny, nz + 1}; seq[n++] = {1, Vz, nx, ny, nz + 1};                          \
-        } else if (bc_kind == NS3D_BC_GPU) { /* gpu.jl:265-276 */                                            \
-            seq[n++] = {0, Vx, nx + 1, ny, nz}; seq[n++] = {1, Vx, nx + 1, ny, nz}; seq[n++] = {3, Vx, nx + 1, ny, nz}; \
-            seq[n++] = {0, Vy, nx, ny + 1, nz}; seq[n++] = {1, Vy, nx, ny + 1, nz}; seq[n++] = {3, Vy, nx, ny + 1, nz}; \
-            seq[n++] = {0, Vz, nx, ny, nz + 1}; seq[n++] = {1, Vz, nx, ny, nz + 1}; seq[n++] = {3, Vz, nx, ny, nz + 1}; \
-        } else return fail(NS3D_ERR_ARG, "ns3d_set_bc_Vel: bad bc_kind %d", bc_kind);                        \
-        for (int q = 0; q < n && e == hipSuccess; ++q)                                                       \
-            e = DISPATCH(c, bc_plane<T>(s, seq[q].which, seq[q].A, seq[q].sx, seq[q].sy, seq[q].sz, 0, 0, 0, 0)); \
-        if (e == hipSuccess && bc_kind == NS3D_BC_MULTI && owns_inlet) /* multi.jl:164-166 */                \
-            e = DISPATCH(c, bc_plane<T>(s, 5, Vx, nx + 1, ny, nz, vin, 0, 0, 0));                            \
-        return finish(c, e, "set_bc_Vel");                                                                   \
-    }                                                                                                        \
-    extern "C" int ns3d_pt_iterate_##S(ns3d_ctx *c, T *Pr, T *dPrdtau, const T *divV,                        \
-                                       const ns3d_pt_params *p, int n_iters)                                 \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr, dPrdtau, divV);                                                         \
-        int rc = ns3d_check_pt_params(p, "ns3d_pt_iterate");                                                      \
-        if (rc) return rc;                                                                                   \
-        if ((rc = pt_iterate_impl<T>(c, Pr, dPrdtau, divV, p, n_iters))) return rc;                          \
-        return finish(c, hipSuccess, "pt_iterate");                                                          \
-    }                                                                                                        \
-    extern "C" int ns3d_pt_sweep_##S(ns3d_ctx *c, const T *Pr_in, T *Pr_out, T *dPrdtau, const T *divV,      \
-                                     const ns3d_pt_params *p, int k0, int k1)                                \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr_in, Pr_out, dPrdtau, divV);                                              \
-        int rc = ns3d_check_pt_params(p, "ns3d_pt_sweep");                                                        \
-        if (rc) return rc;                                                                                   \
-        if (Pr_in == Pr_out) return fail(NS3D_ERR_ARG, "ns3d_pt_sweep: Pr_in and Pr_out must differ");       \
-        if (k0 < 1 || k1 > p->nz - 1 || k0 > k1)                                                             \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweep: plane range [%d,%d) outside [1,%d)", k0, k1, p->nz - 1);\
-        return finish(c, DISPATCHG(c, p->dx, p->dy, p->dz, pt_sweep<T>(c->stream, c->pt_variant, Pr_in, Pr_out, dPrdtau, divV, *p, \
-                                                 k0, k1)), "pt_sweep");                                      \
-    }                                                                                                        \
-    extern "C" int ns3d_pt_sweep2_##S(ns3d_ctx *c, const T *Pr_in, T *Pr_out, const T *dPrdtau, T *dPrdtau_out,\
-                                      const T *divV, const ns3d_pt_params *p, int k0, int k1)               \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr_in, Pr_out, dPrdtau, dPrdtau_out, divV);                                 \
-        if (dPrdtau == dPrdtau_out) return fail(NS3D_ERR_ARG, "ns3d_pt_sweep2: dPrdtau_in and dPrdtau_out must differ"); \
-        int rc = ns3d_check_pt_params(p, "ns3d_pt_sweep2");                                                       \
-        if (rc) return rc;                                                                                   \
-        if (Pr_in == Pr_out) return fail(NS3D_ERR_ARG, "ns3d_pt_sweep2: Pr_in and Pr_out must differ");      \
-        if (p->z_lo_is_halo || p->z_hi_is_halo)                                                              \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweep2: z-slab ranks pass ghost-extended buffers, not halo flags"); \
-        if (k0 < 1 || k1 > p->nz - 1 || k0 > k1)                                                             \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweep2: plane range [%d,%d) outside [1,%d)", k0, k1, p->nz - 1); \
-        return finish(c, launch_pt2<T>(c, c->stream, Pr_in, Pr_out, dPrdtau, dPrdtau_out, divV, p, k0, k1, false), "pt_sweep2"); \
-    }                                                                                                        \
-    extern "C" int ns3d_pt_sweepn_##S(ns3d_ctx *c, int nlev, const T *Pr_in, T *Pr_out, const T *dPrdtau,  \
-                                      T *dPrdtau_out, const T *divV, const ns3d_pt_params *p, int k0, int k1)\
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr_in, Pr_out, dPrdtau, dPrdtau_out, divV);                                 \
-        int rc = ns3d_check_pt_params(p, "ns3d_pt_sweepn");                                                  \
-        if (rc) return rc;                                                                                   \
-        if (nlev < 2 || nlev > (sizeof(T) == 4 ? 5 : 4))                                                     \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweepn: %d levels (2…4; 5 with float32 fields)", nlev);       \
-        if (Pr_in == Pr_out || dPrdtau == dPrdtau_out)                                                       \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweepn: input and output buffers must differ");               \
-        if (p->z_lo_is_halo || p->z_hi_is_halo)                                                              \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweepn: z-slab ranks pass ghost-extended buffers, not halo flags"); \
-        if (k0 < 1 || k1 > p->nz - 1 || k0 > k1)                                                             \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweepn: plane range [%d,%d) outside [1,%d)", k0, k1, p->nz - 1); \
-        hipError_t e = ns3d_enqueue_pass<T>(c, c->stream, nlev, Pr_in, Pr_out, dPrdtau, dPrdtau_out, divV, p, k0, k1); \
-        if (e == hipErrorInvalidValue)                                                                       \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_sweepn: tile variant %d cannot run %d levels", c->ptn_variant, nlev); \
-        return finish(c, e, "pt_sweepn");                                                                    \
-    }                                                                                                        \
-    extern "C" int ns3d_plan_pt_##S(ns3d_ctx *c, const T *Pr_in, T *Pr_out, const T *dPrdtau, T *dPrdtau_out, \
-                                    const T *divV, const ns3d_pt_params *p, int k0, int k1)                  \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr_in, Pr_out, dPrdtau, dPrdtau_out, divV);                                 \
-        int rc = ns3d_check_pt_params(p, "ns3d_plan_pt");                                                    \
-        if (rc) return rc;                                                                                   \
-        if (Pr_in == Pr_out || dPrdtau == dPrdtau_out)                                                       \
-            return fail(NS3D_ERR_ARG, "ns3d_plan_pt: input and output buffers must differ");                 \
-        if (k0 < 1 || k1 > p->nz - 1 || k0 > k1)                                                             \
-            return fail(NS3D_ERR_ARG, "ns3d_plan_pt: plane range [%d,%d) outside [1,%d)", k0, k1, p->nz - 1);\
-        (void)ns3d_plan_pt_internal<T>(c, Pr_in, Pr_out, dPrdtau, dPrdtau_out, divV, p, k0, k1);             \
-        return finish(c, hipSuccess, "plan_pt");                                                             \
-    }                                                                                                        \
-    extern "C" int ns3d_residual_max_##S(ns3d_ctx *c, const T *Pr, const T *divV, const ns3d_pt_params *p,   \
-                                         double *out_host)                                                   \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr, divV, out_host);                                                        \
-        int rc = ns3d_check_pt_params(p, "ns3d_residual_max");                                                    \
-        if (rc) return rc;                                                                                   \
-        hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, residual_max_key<T>(c->stream, Pr, divV, *p, c->key_dev));                \
-        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "residual launch: %s", hipGetErrorString(e));         \
-        return fetch_key(c, c->stream, out_host);                                                                       \
-    }                                                                                                        \
-    extern "C" int ns3d_selftest_exact_div_##S(ns3d_ctx *c, double d, long n, unsigned long long seed,        \
-                                               long *mismatches)                                             \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(mismatches);                                                                \
-        if (!recip_ok(d)) return fail(NS3D_ERR_ARG, "ns3d_selftest_exact_div: divisor %g is not eligible", d);\
-        hipError_t e = ns3d_strictx::divtest<T>(c->stream, d, n, seed, c->key_dev);                          \
-        if (e != hipSuccess) return fail(NS3D_ERR_HIP, "divtest launch: %s", hipGetErrorString(e));          \
-        HIPCHK(c, hipMemcpyAsync(c->key_host, c->key_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, \
-                                 c->stream));                                                                \
-        HIPCHK(c, hipStreamSynchronize(c->stream));                                                          \
-        *mismatches = (long)*c->key_host;                                                                    \
-        return NS3D_OK;                                                                                      \
-    }                                                                                                        \
-    extern "C" int ns3d_pt_solve_##S(ns3d_ctx *c, T *Pr, T *dPrdtau, const T *divV, const ns3d_pt_params *p, \
-                                     double eps, int niter, int nchk, double err_mul, double err_div,        \
-                                     int *iters_done, double *err_hist, int max_checks, int *n_checks)       \
-    {                                                                                                        \
-        CHECK_CTX(c); CHECK_PTRS(Pr, dPrdtau, divV);                                                         \
-        int rc = ns3d_check_pt_params(p, "ns3d_pt_solve");                                                        \
-        if (rc) return rc;                                                                                   \
-        if (p->z_lo_is_halo || p->z_hi_is_halo)                                                              \
-            return fail(NS3D_ERR_ARG, "ns3d_pt_solve: single-rank loop; drive z-slab ranks with ns3d_pt_sweep + halo exchange"); \
-        if (niter < 0 || nchk < 0) return fail(NS3D_ERR_ARG, "ns3d_pt_solve: negative niter/nchk");          \
-        if ((rc = pt_solve_impl<T>(c, Pr, dPrdtau, divV, p, eps, niter, nchk, err_mul, err_div, iters_done,  \
-                                   err_hist, max_checks, n_checks))) return rc;                              \
-        return finish(c, hipSuccess, "pt_solve");                                                            \
-    }
-
-NS3D_DEFINE(double, f64)
-NS3D_DEFINE(float, f32)
-
-// ---- one whole time step per call (include/ns3d.h ns3d_time_step) -----------------------------------------------------------
-// multi.jl:449-477 on one rank / gpu.jl:121-142 as the fused sequence the Python driver issues call by call — through the SAME entry
-// points (argument checks, arithmetic builds and all), with the context switched to non-blocking for the duration so that the residual
-// read-backs inside ns3d_pt_solve are the only synchronisations; one synchronisation at the end restores a blocking context's
-// contract.  ≈40 host calls per step become one: with the direct pressure solve a step of the 255×153×153 case is otherwise mostly
-// the driver's calls.
-extern "C" int ns3d_poisson_direct_f64(ns3d_ctx *, double *, double *, const double *, const ns3d_pt_params *);
+// ---- the typed entry points: ns3d_api_typed.h, plain code, compiled once per element type ----------------------------------------
+// plane range of a sweep entry point: interior planes only
+static int check_planes(const ns3d_pt_params *p, int k0, int k1, const char *fn)
+{
+    if (k0 < 1 || k1 > p->nz - 1 || k0 > k1) return fail(NS3D_ERR_ARG, "%s: plane range [%d,%d) outside [1,%d)", fn, k0, k1, p->nz - 1);
+    return NS3D_OK;
+}
+static int check_no_halos(const ns3d_pt_params *p, const char *fn)
+{
+    if (p->z_lo_is_halo || p->z_hi_is_halo) return fail(NS3D_ERR_ARG, "%s: z-slab ranks pass ghost-extended buffers, not halo flags", fn);
+    return NS3D_OK;
+}
+extern "C" int ns3d_poisson_direct_f64(ns3d_ctx *, double *, double *, const double *, const ns3d_pt_params *);      // ns3d_direct.hip
 extern "C" int ns3d_poisson_direct_f32(ns3d_ctx *, float *, float *, const float *, const ns3d_pt_params *);
-#define NS3D_DEFINE_STEP(T, S)                                                                                \
-    extern "C" int ns3d_time_step_##S(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_step_params *p, int *iters_done, \
-                                      double *err_hist, int max_checks, int *n_checks)                       \
-    {                                                                                                        \
-        CHECK_CTX(c);                                                                                        \
-        if (!f || !p) return fail(NS3D_ERR_ARG, "ns3d_time_step: null argument");                            \
-        if (p->script != NS3D_BC_MULTI && p->script != NS3D_BC_GPU)                                          \
-            return fail(NS3D_ERR_ARG, "ns3d_time_step: script %d (NS3D_BC_MULTI: multi.jl, NS3D_BC_GPU: gpu.jl)", p->script); \
-        if (p->write_stress && !(f->txx && f->tyy && f->tzz && f->txy && f->txz && f->tyz))                  \
-            return fail(NS3D_ERR_ARG, "ns3d_time_step: write_stress needs the six stress arrays");           \
-        const int nx = p->nx, ny = p->ny, nz = p->nz;                                                        \
-        const int was = c->flags;                                                                            \
-        c->flags |= NS3D_ASYNC;                                                                              \
-        int rc = NS3D_OK;                                                                                    \
-        bool deferred_residual = false;                                                                      \
-        T *Vx = (T *)f->Vx, *Vy = (T *)f->Vy, *Vz = (T *)f->Vz, *Vxo = (T *)f->Vx_o, *Vyo = (T *)f->Vy_o, *Vzo = (T *)f->Vz_o; \
-        T *C = (T *)f->C, *Co = (T *)f->C_o, *Pr = (T *)f->Pr, *D = (T *)f->dPrdtau, *divV = (T *)f->divV;    \
-        auto cylinder = [&]() -> int {          /* multi.jl:249-281 (global coordinates) / gpu.jl:336-368 (local) */ \
-            return p->script == NS3D_BC_MULTI                                                                \
-                       ? ns3d_set_cylinder_##S(c, C, Vx, Vy, Vz, p->a2, p->b2, p->ox, p->oy, p->sinb, p->cosb, p->xco_g, p->yco_g, \
-                                               p->zco_g, p->lx, p->ly, p->lz, p->dx, p->dy, p->dz, nx, ny, nz)  \
-                       : ns3d_set_cylinder_local_##S(c, C, Vx, Vy, Vz, p->a2, p->b2, p->ox, p->oy, p->sinb, p->cosb, p->lx,    \
-                                                     p->ly, p->lz, p->dx, p->dy, p->dz, nx, ny, nz);            \
-        };                                                                                                   \
-        do {                                                                                                 \
-            if (p->write_stress &&                                                                           \
-                (rc = ns3d_update_tau_##S(c, (T *)f->txx, (T *)f->tyy, (T *)f->tzz, (T *)f->txy, (T *)f->txz, (T *)f->tyz, Vx, Vy, Vz, \
-                                          p->mu, p->dx, p->dy, p->dz, nx, ny, nz))) break;                   \
-            /* :449-451 / :121-122 in one pass; the predicted fields land in the *_o buffers and the names swap */ \
-            if ((rc = ns3d_predict_fused_##S(c, Vxo, Vyo, Vzo, Vx, Vy, Vz, p->mu, p->rho, p->g, p->dt, p->dx, p->dy, p->dz, nx, ny, nz))) break; \
-            std::swap(Vx, Vxo); std::swap(Vy, Vyo); std::swap(Vz, Vzo);                                      \
-            if ((rc = cylinder())) break;                                                   /* :452 / :123 */ \
-            if ((rc = ns3d_update_divV_##S(c, divV, Vx, Vy, Vz, p->dx, p->dy, p->dz, nx, ny, nz))) break;     /* :454 / :124 */ \
-            ns3d_pt_params pt;                                                                               \
-            pt.rho = p->rho; pt.dt = p->dt; pt.dtau = p->dtau; pt.damp = p->damp; pt.dx = p->dx; pt.dy = p->dy; pt.dz = p->dz; \
-            pt.nx = nx; pt.ny = ny; pt.nz = nz; pt.bc_kind = p->script; pt.owns_outlet = p->script == NS3D_BC_MULTI ? p->owns_outlet : 0; \
-            pt.outlet_val = 0.0; pt.g = p->g; pt.z_lo_is_halo = 0; pt.z_hi_is_halo = 0;                        \
-            if (p->pressure == 1) {             /* outside parity: the exact solution of what :458-471 iterates towards */ \
-                if ((rc = ns3d_poisson_direct_##S(c, Pr, D, divV, &pt))) break;                              \
-                /* its residual steers nothing: the 8 bytes come back behind the REST of the step (read after the final            \
-                 * synchronisation) instead of stalling the stream in the middle of it */                     \
-                hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, residual_max_key<T>(c->stream, Pr, divV, pt, c->key_dev)); \
-                if (e == hipSuccess) e = hipMemcpyAsync(c->key_host, c->key_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream); \
-                if (e != hipSuccess) { rc = fail(NS3D_ERR_HIP, "ns3d_time_step: residual launch: %s", hipGetErrorString(e)); break; } \
-                deferred_residual = true;                                                                    \
-            } else if ((rc = ns3d_pt_solve_##S(c, Pr, D, divV, &pt, p->eps, p->niter, p->nchk, p->err_mul, p->err_div, iters_done, \
-                                               err_hist, max_checks, n_checks))) break;     /* :458-471 / :126-137 */ \
-            if ((rc = ns3d_correct_V_##S(c, Vx, Vy, Vz, Pr, p->dt, p->rho, p->dx, p->dy, p->dz, nx, ny, nz))) break;   /* :472 / :138 */ \
-            if ((rc = cylinder())) break;                                                   /* :473 / :139 */ \
-            if ((rc = ns3d_set_bc_Vel_##S(c, Vx, Vy, Vz, p->script, p->script == NS3D_BC_MULTI ? p->owns_inlet : 0, p->vin, nx, ny, nz))) break; \
-            /* :475-476 / :141-142 in one pass: complete new fields into the *_o buffers, then the roles swap */ \
-            if ((rc = ns3d_copy_advect_##S(c, Vxo, Vx, Vyo, Vy, p->faithful ? Vz : Vzo, Vz, Co, C, p->dt, p->dx, p->dy, p->dz, nx, ny, nz, \
-                                           p->faithful ? 1 : 0))) break;                                     \
-            std::swap(Vx, Vxo); std::swap(Vy, Vyo); std::swap(C, Co);                                        \
-            if (!p->faithful) std::swap(Vz, Vzo);                                                            \
-        } while (0);                                                                                         \
-        c->flags = was;                                                                                      \
-        f->Vx = Vx; f->Vy = Vy; f->Vz = Vz; f->Vx_o = Vxo; f->Vy_o = Vyo; f->Vz_o = Vzo; f->C = C; f->C_o = Co; \
-        if (rc) return rc;                                                                                   \
-        if (deferred_residual) {                                                                             \
-            HIPCHK(c, hipStreamSynchronize(c->stream));                                                      \
-            double mx;                                                                                       \
-            std::memcpy(&mx, c->key_host, sizeof mx);                                                        \
-            if (iters_done) *iters_done = 0;                                                                 \
-            if (err_hist && max_checks > 0) err_hist[0] = mx * p->err_mul / p->err_div;                      \
-            if (n_checks) *n_checks = 1;                                                                     \
-            return NS3D_OK;                                                                                  \
-        }                                                                                                    \
-        return finish(c, hipSuccess, "time_step");                                                           \
-    }
-NS3D_DEFINE_STEP(double, f64)
-NS3D_DEFINE_STEP(float, f32)
+namespace ns3d_api_f64 { using T = double;
+#define NS3D_FN(name) ns3d_##name##_f64
+#define NS3D_BC_RULE bc_f64       // the name its messages carry (__func__)
+#include "ns3d_api_typed.h"
+#undef NS3D_BC_RULE
+#undef NS3D_FN
+}
+namespace ns3d_api_f32 { using T = float;
+#define NS3D_FN(name) ns3d_##name##_f32
+#define NS3D_BC_RULE bc_f32
+#include "ns3d_api_typed.h"
+#undef NS3D_BC_RULE
+#undef NS3D_FN
+}

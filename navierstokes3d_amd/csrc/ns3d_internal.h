@@ -1,5 +1,5 @@
-// ns3d_internal.h — what the host-side translation units of libns3d.so share (ns3d_api.cpp: single-device entry points
-// and the PT loop; ns3d_mgpu.cpp: the z-slab multi-GPU layer).  Internal; the public boundary is include/ns3d.h.
+// ns3d_internal.h — what the host-side translation units of libns3d.so share (ns3d_api.cpp with ns3d_api_typed.h: single-device
+// entry points and the PT loop; ns3d_mgpu.cpp: the z-slab multi-GPU layer).  Internal; the public boundary is include/ns3d.h.
 #pragma once
 #include <cstring>
 #include <vector>
@@ -36,8 +36,8 @@ struct ns3d_ctx {
     hipEvent_t tune_ev[2];
     hipEvent_t fence;
     struct BlockGraph {
-        const void *src, *dst, *dsrc, *ddst, *rhs;
-        void *src_out, *dst_out, *dsrc_out, *ddst_out;
+        struct Bufs { void *src, *dst, *dsrc, *ddst; } in, out;   // PtBufs<T> (ns3d_api.cpp) the block was captured on / leaves behind
+        const void *rhs;
         int n, mode, v1, v2, vn, depth, esize;
         bool two;
         ns3d_pt_params p;

@@ -74,6 +74,21 @@ def test_null_context_is_an_error_not_a_crash(L):
     assert lib.ns3d_pt_iterate_f64(None, None, None, None, ctypes.byref(p), 1) == 1
 
 
+def test_every_typed_entry_point_reports_a_null_context_under_its_own_name(L):
+    """Every name of lib.SIGNATURES with both suffixes, called with a NULL context and zeroed / NULL arguments: NS3D_ERR_ARG and
+    "<function>: null context" — the symbol exists, the context is tested before anything else, and __func__ names the entry
+    point.  The seven ns3d_bc_* rules share one body per element type and report under ITS name, bc_f64 / bc_f32."""
+    lib = L.load()
+    shared = {"bc_x", "bc_y", "bc_z", "bc_zV", "bc_xhydstatic", "bc_x_Vx", "bc_x_Pr"}
+    assert shared < set(L.SIGNATURES) and len(L.SIGNATURES) == 35
+    for name, args in L.SIGNATURES.items():
+        for suf in ("f64", "f32"):
+            fn = getattr(lib, "ns3d_%s_%s" % (name, suf))
+            assert fn(None, *[a() for a in args]) == L.NS3D_ERR_ARG, (name, suf)
+            who = "bc_" + suf if name in shared else "ns3d_%s_%s" % (name, suf)
+            assert L.last_error() == who + ": null context", (name, suf)
+
+
 def test_product_never_imports_the_oracle():
     """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/."""
     pkg = os.path.join(ROOT, "navierstokes3d_amd")
