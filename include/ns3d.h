@@ -249,6 +249,40 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
      * without NS3D_ASYNC).  NS3D_ERR_ARG: null context / S / velocity, a grid below 3×3×3, a weight that is not finite. */    \
     int ns3d_stats_accumulate_##S(ns3d_ctx *, double *S_, const T *Vx, const T *Vy, const T *Vz, const T *Pr,  \
                                   double weight, int nx, int ny, int nz);                                    \
+    /* Vorticity and Q-criterion: the third observer — what one looks at in a cylinder wake.  Four cell-centred (nx,ny,nz)    \
+     * fields of the element type T, formed in ONE pass over Vx, Vy, Vz.  All arithmetic is in T, like ns3d_update_divV and   \
+     * unlike the statistics: h = (T)0.5, and dx, dy, dz are converted to T on entry.                                         \
+     *   cell-centred velocities   u = h·(Vx[i,j,k] + Vx[i+1,j,k])   v = h·(Vy[i,j,k] + Vy[i,j+1,k])   w = h·(Vz[i,j,k] + Vz[i,j,k+1]) \
+     *   diagonal of ∇V (update_∇V!'s terms)   gxx = (Vx[i+1,j,k] − Vx[i,j,k])/dx   gyy = (Vy[i,j+1,k] − Vy[i,j,k])/dy      \
+     *                                         gzz = (Vz[i,j,k+1] − Vz[i,j,k])/dz                                              \
+     *   off-diagonal entries, central differences of the cell-centred values                                                 \
+     *     uy = h·((u[i,j+1,k] − u[i,j−1,k])/dy)   uz = h·((u[i,j,k+1] − u[i,j,k−1])/dz)   vx = h·((v[i+1,j,k] − v[i−1,j,k])/dx) \
+     *     vz = h·((v[i,j,k+1] − v[i,j,k−1])/dz)   wx = h·((w[i+1,j,k] − w[i−1,j,k])/dx)   wy = h·((w[i,j+1,k] − w[i,j−1,k])/dy) \
+     *   Wx = wy − vz     Wy = uz − wx     Wz = vx − uy                                                                        \
+     *   Q  = ((−h)·((gxx·gxx + gyy·gyy) + gzz·gzz)) − ((uy·vx + uz·wx) + vz·wy)                                              \
+     * (Q = −½·G_ij·G_ji = ½(‖Ω‖² − ‖S‖²) whatever ∇·V is; the parentheses are as written.)  As NumPy, on arrays of dtype T   \
+     * with h, dx, dy, dz scalars of that dtype, I = [1:-1,1:-1,1:-1]:                                                         \
+     *   u = h*(Vx[:-1] + Vx[1:]);  v = h*(Vy[:,:-1] + Vy[:,1:]);  w = h*(Vz[:,:,:-1] + Vz[:,:,1:])                           \
+     *   gxx = ((Vx[1:] − Vx[:-1])/dx)[I];  gyy = ((Vy[:,1:] − Vy[:,:-1])/dy)[I];  gzz = ((Vz[:,:,1:] − Vz[:,:,:-1])/dz)[I]   \
+     *   uy = h*((u[1:-1,2:,1:-1] − u[1:-1,:-2,1:-1])/dy);  uz = h*((u[1:-1,1:-1,2:] − u[1:-1,1:-1,:-2])/dz)                  \
+     *   vx = h*((v[2:,1:-1,1:-1] − v[:-2,1:-1,1:-1])/dx);  vz = h*((v[1:-1,1:-1,2:] − v[1:-1,1:-1,:-2])/dz)                  \
+     *   wx = h*((w[2:,1:-1,1:-1] − w[:-2,1:-1,1:-1])/dx);  wy = h*((w[1:-1,2:,1:-1] − w[1:-1,:-2,1:-1])/dy)                  \
+     *   Wx[I] = wy − vz;  Wy[I] = uz − wx;  Wz[I] = vx − uy                                                                   \
+     *   Q[I] = ((−h)*((gxx*gxx + gyy*gyy) + gzz*gzz)) − ((uy*vx + uz*wx) + vz*wy)                                            \
+     * Interior cells (1 ≤ i ≤ nx−2, the same in y and z) receive these values, EVERY other entry +0.0: one call writes an    \
+     * output completely.  STRICT returns the bits of that expression (float64 and float32, no contraction, whichever of the  \
+     * three division builds the spacings select; NS3D_IEEE_DIV is honoured); FAST multiplies by reciprocals and may contract. \
+     * Any of Wx, Wy, Wz, Q may be NULL — it is then neither computed nor stored — but not all four.  Outputs must not alias   \
+     * the inputs or each other.  Enqueued on the context's stream, no read-back (blocks only as every call does without       \
+     * NS3D_ASYNC).  The interior of a rank needs only that rank's own arrays with their one-cell halo, so there is no        \
+     * ns3d_mgpu form: a multi-rank caller makes this call on each local rank's context (ns3d_mgpu_ctx) after the step's last \
+     * halo update, and ns3d_gather_* assembles the halo-stripped global fields.  The gathered result equals the one-rank      \
+     * result wherever the ranks' duplicated velocity entries agree — they do after update_halo! unless several ranks run the \
+     * corrected advection (faithful = 0) without the wide halo.                                                   \
+     * NS3D_ERR_ARG: null context / velocity pointer, all four outputs NULL, a grid below 3×3×3, a spacing that is not finite  \
+     * or not greater than 0; the outputs are then untouched. */                                                              \
+    int ns3d_vortex_##S(ns3d_ctx *, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T *Vy, const T *Vz,       \
+                        double dx, double dy, double dz, int nx, int ny, int nz);                            \
     /* The monitor above on one rank.  Pr or C may be NULL: pr_min / pr_max resp. c_vol then come back as NaN (and take no    \
      * part in `nonfinite`).  Blocks for its read-back like ns3d_max_abs.  NS3D_ERR_ARG: null context / velocity / params /   \
      * output, a grid below 3×3×3, a cylinder form other than 0, 1, 2. */                                    \

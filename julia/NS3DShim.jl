@@ -42,6 +42,7 @@ export bc_x!, bc_y!, bc_z!, bc_zV!, bc_xhydstatic!, bc_x_Vx!, bc_x_Pr!, bc_xVx!,
 export init_global_grid, finalize_global_grid, nx_g, ny_g, nz_g, x_g, y_g, z_g, update_halo!, gather!
 export diagnostics, Diag, DiagParams
 export stats_zeros, stats_reset!, stats_accumulate!, stats_finalize
+export vortex
 export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
 
 const libns3d = get(ENV, "NS3D_LIB", joinpath(@__DIR__, "..", "navierstokes3d_amd", "libns3d.so"))
@@ -383,6 +384,22 @@ function stats_finalize(S, wsum, Pr)
     check(ccall((:ns3d_stats_finalize, libns3d), Cint, (Ptr{Cvoid}, PF, Cdouble, PF, PF, Cint, Cint, Cint),
                 _ctx(), ptr(S), wsum, ptr(mean), ptr(rs), nx, ny, nz))
     return mean, rs
+end
+"""
+    vortex(Vx, Vy, Vz, dx, dy, dz; Wx = true, Wy = true, Wz = true, Q = true)
+
+Vorticity components and Q-criterion of the staggered velocity field as cell-centred `(nx,ny,nz)` arrays, one fused pass on the
+device (`ns3d_vortex_f64`; include/ns3d.h has the expression).  Interior cells receive the values, every other entry 0.  Returns
+`(Wx, Wy, Wz, Q)` with `nothing` for the outputs switched off (at least one must stay on).  After `init_global_grid` call it on
+every rank after the step's last `update_halo!`; `gather!` assembles the halo-stripped global fields.
+"""
+function vortex(Vx, Vy, Vz, dx, dy, dz; Wx = true, Wy = true, Wz = true, Q = true)
+    nx, ny, nz = Cint(size(Vx, 1) - 1), Cint(size(Vx, 2)), Cint(size(Vx, 3))
+    out = map(on -> on ? AMDGPU.zeros(Float64, Int(nx), Int(ny), Int(nz)) : nothing, (Wx, Wy, Wz, Q)); _sync()
+    p = map(a -> a === nothing ? PF(C_NULL) : ptr(a), out)
+    check(ccall((:ns3d_vortex_f64, libns3d), Cint, (Ptr{Cvoid}, PF, PF, PF, PF, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint),
+                _ctx(), p[1], p[2], p[3], p[4], ptr(Vx), ptr(Vy), ptr(Vz), dx, dy, dz, nx, ny, nz))
+    return out
 end
 mutable struct StepFields          # struct ns3d_step_fields (include/ns3d.h): device pointers, IN/OUT (the fused step swaps X and X_o)
     Pr::PF; dPrdtau::PF; divV::PF

@@ -96,6 +96,16 @@ extern "C" int NS3D_FN(stats_accumulate)(ns3d_ctx *c, double *St, const T *Vx, c
     if (!std::isfinite(weight)) return fail(NS3D_ERR_ARG, "ns3d_stats_accumulate: weight = %g is not finite", weight);
     return finish(c, DISPATCH(c, stats_accumulate<T>(c->stream, St, Vx, Vy, Vz, Pr, weight, nx, ny, nz)), "stats_accumulate");
 }
+extern "C" int NS3D_FN(vortex)(ns3d_ctx *c, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T *Vy, const T *Vz, double dx, double dy, double dz,
+                               int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz);
+    if (!Wx && !Wy && !Wz && !Q) return fail(NS3D_ERR_ARG, "%s: all four outputs are NULL", __func__);
+    CHECK_GRID(nx, ny, nz, 3);
+    if (!(std::isfinite(dx) && std::isfinite(dy) && std::isfinite(dz) && dx > 0.0 && dy > 0.0 && dz > 0.0))
+        return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (need finite values > 0)", __func__, dx, dy, dz);
+    return finish(c, DISPATCHG(c, dx, dy, dz, vortex<T>(c->stream, Wx, Wy, Wz, Q, Vx, Vy, Vz, dx, dy, dz, nx, ny, nz)), "vortex");
+}
 extern "C" int NS3D_FN(correct_V)(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *Pr, double dt, double rho, double dx, double dy, double dz,
                                   int nx, int ny, int nz)
 {

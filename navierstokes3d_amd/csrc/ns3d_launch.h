@@ -79,6 +79,11 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
 // chunks keep every CU busy on small grids (a rank of the 255×153×153 case: 6 240 workgroups) and cost one extra Vz plane in four.
 #define NS3D_STATS_KZ 4
 
+// ns3d_vortex (k_vortex): 64×4 cell columns per workgroup over the nx×ny columns, NS3D_VORTEX_KZ of the nz planes per workgroup (two
+// further planes of Vx and Vy are read per chunk for the z ring).  64×4 with 16 planes was the fastest of 64×4 / 64×8 / 64×16 with
+// 8 / 16 / 32 planes at 512³ in fp64 and within 7 % of the best elsewhere (profiles/vortex_variants_ab.log).
+#define NS3D_VORTEX_KZ 16
+
 #define NS3D_LAUNCHER_DECLS(NS)                                                                              \
     namespace NS {                                                                                           \
     template <class T>                                                                                       \
@@ -150,6 +155,10 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
     hipError_t stats_accumulate(hipStream_t, double *S, const T *Vx, const T *Vy, const T *Vz, const T *Pr, \
                                 double weight, int nx, int ny, int nz);                                      \
     hipError_t stats_finalize(hipStream_t, const double *S, double wsum, double *mean, double *rs, long n_cells); \
+    /* any of Wx, Wy, Wz, Q may be null (not all) */                                                          \
+    template <class T>                                                                                       \
+    hipError_t vortex(hipStream_t, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T *Vy, const T *Vz,        \
+                      double dx, double dy, double dz, int nx, int ny, int nz);                              \
     template <class T>                                                                                       \
     hipError_t divtest(hipStream_t, double d, long n, unsigned long long seed, unsigned long long *bad_dev); \
     template <class T>                                                                                       \

@@ -24,8 +24,9 @@ from . import lib as L
 from .halo import ZSlabGrid
 from .slab import SlabPTSolver
 from .stats import RunningStats
+from .vortex import VortexFields, save_bins as _save_vortex_bins
 from .params import gpu_params, multi_params
-from .vis import save_frame_gpu, save_frame_multi
+from .vis import save_frame_gpu, save_frame_multi, save_frame_vortex
 
 
 def _alloc(nx, ny, nz, dtype, device):
@@ -165,7 +166,7 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
-                       statistics=None, stats_every=1):
+                       statistics=None, stats_every=1, vortex=False):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -192,7 +193,13 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     local rank's context) sampled with weight 1.0 at the end of the steps s, s+stats_every, … — after the step's last halo update
     :477, whichever way the step ran (`one_call` stays in use).  info.stats gets n, mean (U, V, W, P: cell-centred means) and rs
     (uu, vv, ww, uv, uw, vw: Reynolds stresses, pp: pressure variance) as halo-stripped global host arrays on the root, gathered
-    like the fields.  Read-only: every other result keeps its bits."""
+    like the fields.  Read-only: every other result keeps its bits.
+    vortex=True (default False: not one extra call, file or attribute): the vorticity components and the Q-criterion (ns3d_vortex, on
+    the device, on every local rank's context) of the final state, after the last step's halo update — and, with do_save / do_vis,
+    of every frame's state.  info.vortex gets Wx, Wy, Wz, Q as halo-stripped global host arrays on the root, gathered like the
+    fields; do_save adds out_Wx_v_%04d.bin, out_Wy_v_…, out_Wz_v_…, out_Q_v_… (Float32, same directory and counter), do_vis adds
+    3D_NavierStokes_xy_Wz_%04d.png, …_xy_Q_…, …_xz_Wy_…, …_xz_Q_… (colour range: the data's own).  `one_call` stays in use;
+    read-only: every other result keeps its bits."""
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -240,6 +247,18 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     iframe = 0
     nz_g_all = dims[2] * (nz - 2) + 2
     ny_g_all = dims[1] * (ny - 2) + 2
+    vort = VortexFields((nx, ny, nz), ctxs, (p.dx, p.dy, p.dz), dtype) if vortex else None
+
+    def vortex_frame(save, vis):
+        """the vortex fields of the state a frame shows: computed, gathered, written by the root"""
+        vort.compute(fs)
+        rec = vort.gathered(grid)
+        if _is_root(grid):
+            if save:
+                _save_vortex_bins(rec, iframe)
+            if vis:
+                save_frame_vortex(rec, ny_g_all, nz_g_all, iframe)
+
     if do_save or do_vis:                                                                     # :399-403
         sync()
         gathered = _gather_all(grid, fs)
@@ -247,6 +266,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             _save_frame(grid, gathered, iframe)
         if do_vis and _is_root(grid):                                                         # :416-443
             save_frame_multi(gathered, ny_g_all, nz_g_all, iframe)
+        if vort is not None:
+            vortex_frame(do_save, do_vis)
     iframe += 1
     pts = [K.pt_params(f.Pr, q.rho, q.dt, q.dtau, q.damp, q.dx, q.dy, q.dz, L.NS3D_BC_MULTI, q.owns_outlet, 0.0, q.g,
                        q.coords[2] > 0, q.coords[2] < dims[2] - 1) for f, q in zip(fs, ps)]
@@ -306,6 +327,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                 save_frame_multi(gathered, ny_g_all, nz_g_all, iframe)
             if do_save and it % nsave == 0:                                                   # :515-522
                 _save_frame(grid, gathered, iframe)
+            if vort is not None:
+                vortex_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
             iframe += 1
 
     for it in range(1, nt + 1):                                                               # :446
@@ -421,6 +444,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     out = _gather_all(grid, fs)                                                               # :528-532
     if running is not None:
         info.stats = running.gathered(grid) if running.n else SimpleNamespace(n=0, wsum=0.0, mean=None, rs=None)
+    if vort is not None:
+        vort.compute(fs)
+        info.vortex = vort.gathered(grid)
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
@@ -490,7 +516,7 @@ def _save_mat(path, f, p, step0):
 
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
-          diagnostics=False, statistics=None, stats_every=1):
+          diagnostics=False, statistics=None, stats_every=1, vortex=False):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -499,7 +525,10 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     record per step in info.diag (gpu.jl's form of the cylinder test, its dx-for-dy quirk included), a line per step with
     do_print; the step runs call by call (`one_call` is not used) and returns the same bits.
     statistics / stats_every: as in run_navierstokes3D, sampled after :142; info.stats holds the FULL local arrays (boundary cells
-    included)."""
+    included).
+    vortex=True: as in run_navierstokes3D, of the final state and — with do_vis — of every frame's; info.vortex holds the FULL
+    local arrays Wx, Wy, Wz, Q (their boundary entries are 0); do_vis adds 3D_NavierStokes_Wz_%04d.png, …_Q_…, …_long_Wy_…,
+    …_long_Q_… (do_save's MAT files are left as the reference writes them)."""
     if device is None:
         device = torch.cuda.current_device()
     _check_stats_options(statistics, stats_every)
@@ -522,9 +551,17 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         _save_mat("out_save/step_0.mat", f, p, True)
     iframe = 0
     host = lambda: {n: K.to_numpy(getattr(f, n)) for n in ("Pr", "C", "Vx", "Vy", "Vz")}
+    vort = VortexFields((nx, ny, nz), [ctx], (p.dx, p.dy, p.dz), dtype) if vortex else None
+
+    def vortex_frame():
+        vort.compute([f])
+        save_frame_vortex(vort.local(0), ny, nz, iframe, gpu_names=True)
+
     if do_vis:                                                                                # :90-117
         ctx.sync()
         save_frame_gpu(host(), ny, nz, iframe)
+        if vort is not None:
+            vortex_frame()
         iframe += 1
     step_params = None
     monitor = None
@@ -553,6 +590,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             if do_vis and it % nvis == 0:                                                     # :143-167
                 ctx.sync()
                 save_frame_gpu(host(), ny, nz, iframe)
+                if vort is not None:
+                    vortex_frame()
                 iframe += 1
             if do_save and it % nsave == 0:                                                   # :168-170
                 ctx.sync()
@@ -614,6 +653,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         if do_vis and it % nvis == 0:                                                         # :143-167
             ctx.sync()
             save_frame_gpu(host(), ny, nz, iframe)
+            if vort is not None:
+                vortex_frame()
             iframe += 1
         if do_save and it % nsave == 0:                                                       # :168-170
             ctx.sync()
@@ -624,4 +665,7 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     info.ctx = ctx
     if running is not None:
         info.stats = running.local(0) if running.n else SimpleNamespace(n=0, wsum=0.0, mean=None, rs=None)
+    if vort is not None:
+        vort.compute([f])
+        info.vortex = vort.local(0)
     return f, info

@@ -362,6 +362,29 @@ def stats_accumulate(S, Vx, Vy, Vz, Pr, weight=1.0, ctx=None):
            None if Pr is None else _chk(Pr, (nx, ny, nz), "Pr"), C.c_double(float(weight)), nx, ny, nz)
 
 
+def vortex(Vx, Vy, Vz, dx, dy, dz, *, Wx=None, Wy=None, Wz=None, Q=None, ctx=None):
+    """ns3d_vortex: the vorticity components Wx, Wy, Wz and the Q-criterion of the staggered velocity field, each a cell-centred
+    (nx,ny,nz) array of the fields' dtype, in one fused pass on the device (include/ns3d.h has the expression).  Interior cells
+    receive the values, every other entry +0.0.  Only the outputs that are given are computed; at least one is needed.
+    Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    outs = []
+    for name, t in (("Wx", Wx), ("Wy", Wy), ("Wz", Wz), ("Q", Q)):
+        if t is None:
+            outs.append(None)
+            continue
+        outs.append(_chk(t, (nx, ny, nz), name))
+        if t.dtype != Vx.dtype or t.device != Vx.device:
+            raise L.Ns3dError("%s is %s on %s, the velocities are %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    if all(o is None for o in outs):
+        raise L.Ns3dError("vortex: give at least one of Wx, Wy, Wz, Q")
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("vortex", Vx, *outs, _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
+                       _chk(Vz, (nx, ny, nz + 1), "Vz"), *_d(dx, dy, dz), nx, ny, nz)
+
+
 def _untyped(ctx, ref, name, *args):
     c = _ctx(ctx, ref)
     if not getattr(c, "_pinned", False) and torch.cuda.current_stream(c.device).cuda_stream != c._stream:

@@ -100,6 +100,10 @@ SIGNATURES = {
     "pt_solve": [_P] * 3 + [C.POINTER(PtParams), _D, _I, _I, _D, _D, C.POINTER(_I), C.POINTER(_D), _I, C.POINTER(_I)],
     "time_step": [C.POINTER(StepFields), C.POINTER(StepParams), C.POINTER(_I), C.POINTER(_D), _I, C.POINTER(_I)],
 }
+# typed entry points of the derived-field observers (same convention as SIGNATURES, a table of their own)
+DERIVED_SIGNATURES = {
+    "vortex": [_P] * 7 + [_D] * 3 + [_I] * 3,
+}
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
                    "ns3d_set_pt2_variant", "ns3d_set_ptn_variant", "ns3d_set_pt_depth", "ns3d_set_graph_mode", "ns3d_set_autotune", "ns3d_last_pt2_variant", "ns3d_last_ptn_variant", "ns3d_last_pt_depth",
@@ -155,7 +159,7 @@ MGPU_SIGNATURES = {   # typed (_f64/_f32), after the leading ns3d_mgpu*
 def exported_symbols():
     """Every symbol include/ns3d.h declares."""
     out = list(CONTEXT_SYMBOLS) + list(MGPU_SYMBOLS)
-    for n in list(SIGNATURES) + list(MGPU_SIGNATURES):
+    for n in list(SIGNATURES) + list(DERIVED_SIGNATURES) + list(MGPU_SIGNATURES):
         out += ["ns3d_%s_f64" % n, "ns3d_%s_f32" % n]
     return out
 
@@ -211,7 +215,7 @@ def load():
     lib.ns3d_stats_reset.restype = _I
     lib.ns3d_stats_finalize.argtypes = [_P, _P, _D, _P, _P] + [_I] * 3
     lib.ns3d_stats_finalize.restype = _I
-    for name, args in SIGNATURES.items():
+    for name, args in list(SIGNATURES.items()) + list(DERIVED_SIGNATURES.items()):
         for suf in ("f64", "f32"):
             fn = getattr(lib, "ns3d_%s_%s" % (name, suf))
             fn.restype = _I

@@ -101,3 +101,20 @@ def save_frame_gpu(fields, ny, nz, iframe, outdir="viz3D_out"):
             heatmap_png(path, S)
             out.append(path)
     return out
+
+
+def save_frame_vortex(rec, ny, nz, iframe, outdir="viz3D_out", gpu_names=False):
+    """The vortex fields of a frame (vortex.py: a record with Wx, Wy, Wz, Q): Wz and Q on the x-y mid-plane, Wy and Q on the x-z
+    mid-plane — the components normal to the planes drawn.  Files `3D_NavierStokes_xy_Wz_%04d.png`, `…_xy_Q_…`, `…_xz_Wy_…`,
+    `…_xz_Q_…` beside save_frame_multi's (gpu_names: `3D_NavierStokes_Wz_…`, `…_Q_…`, `…_long_Wy_…`, `…_long_Q_…` beside
+    save_frame_gpu's).  The reference draws none of them and so has no limits for them: the colour range is the data's own."""
+    os.makedirs(outdir, exist_ok=True)
+    tags = {"xy": "", "xz": "long_"} if gpu_names else {"xy": "xy_", "xz": "xz_"}
+    out = []
+    for plane, name in (("xy", "Wz"), ("xy", "Q"), ("xz", "Wy"), ("xz", "Q")):
+        A = getattr(rec, name)
+        kz, jy = min(_mid(nz), A.shape[2] - 1), min(_mid(ny), A.shape[1] - 1)
+        path = os.path.join(outdir, "3D_NavierStokes_%s%s_%04d.png" % (tags[plane], name, iframe))
+        heatmap_png(path, A[:, :, kz] if plane == "xy" else A[:, jy, :])
+        out.append(path)
+    return out
