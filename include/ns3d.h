@@ -283,6 +283,50 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
      * or not greater than 0; the outputs are then untouched. */                                                              \
     int ns3d_vortex_##S(ns3d_ctx *, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T *Vy, const T *Vz,       \
                         double dx, double dy, double dz, int nx, int ny, int nz);                            \
+    /* Point samples and Lagrangian tracers: the observers that do not live on the grid.  Both rest on ONE definition, the \
+     * trilinear interpolation of backtrack! (multi.jl:190-214: clamp, floor, lerp(a,b,t) = b*t + a*(1-t), x then y then z), evaluated \
+     * at points the caller chooses.  Positions are fp64 and in INDEX space whatever T is: X holds three consecutive blocks of n \
+     * doubles, xi | eta | zeta; the cell grid occupies the closed box [0,nx] x [0,ny] x [0,nz], cell centres sit at half-integers, \
+     * and a field staggered in a direction has its nodes at the integers of that direction.  `state` is one byte per point: 1 alive, \
+     * 0 dead.  Field values are converted to double on load; all arithmetic after that is fp64 and is NEVER contracted, in any \
+     * build: STRICT, NS3D_IEEE_DIV and FAST contexts return the same bits (the calls are bound by gather latency, an FMA would buy \
+     * nothing, and whether a particle is alive does not depend on the arithmetic mode).  The device performs no division. \
+     *   I(A, ext, stag, p), per direction q:   c = p_q - (stag_q ? 0.0 : 0.5);   c = c > 0.0 ? c : 0.0;   c = c < ext_q-1 ? c : ext_q-1 \
+     *                                          i0 = min((int)floor(c), ext_q-2);   t = c - i0                            \
+     *     (max and min written as comparisons: -0.0 becomes +0.0), then with a_ijk = A[i0+i, j0+j, k0+k]                 \
+     *     fy1z1 = lerp(a000,a100,tx)  fy1z2 = lerp(a001,a101,tx)  fy2z1 = lerp(a010,a110,tx)  fy2z2 = lerp(a011,a111,tx) \
+     *     fz1 = lerp(fy1z1,fy2z1,ty)  fz2 = lerp(fy1z2,fy2z2,ty)  I = lerp(fz1,fz2,tz)                                   \
+     *   velocity at p:   u = I(Vx,(nx+1,ny,nz),(1,0,0),p)   v = I(Vy,(nx,ny+1,nz),(0,1,0),p)   w = I(Vz,(nx,ny,nz+1),(0,0,1),p) \
+     * As NumPy, on the points m that are evaluated (X of shape (3,N), A column-major of extents e, s the stagger flags): \
+     *   c = [np.where(X[q,m] - (0.0 if s[q] else 0.5) > 0.0, X[q,m] - (0.0 if s[q] else 0.5), 0.0) for q in range(3)]    \
+     *   c = [np.where(c[q] < e[q]-1.0, c[q], e[q]-1.0) for q in range(3)]                                                \
+     *   i = [np.minimum(np.floor(c[q]).astype(np.int64), e[q]-2) for q in range(3)];  t = [c[q] - i[q] for q in range(3)] \
+     *   a = lambda di,dj,dk: A[i[0]+di, i[1]+dj, i[2]+dk].astype(np.float64);  lerp = lambda a,b,t: b*t + a*(1.0-t)      \
+     *   fz1 = lerp(lerp(a(0,0,0),a(1,0,0),t[0]), lerp(a(0,1,0),a(1,1,0),t[0]), t[1])                                     \
+     *   fz2 = lerp(lerp(a(0,0,1),a(1,0,1),t[0]), lerp(a(0,1,1),a(1,1,1),t[0]), t[1]);   I = lerp(fz1, fz2, t[2])         \
+     * ns3d_sample_*: out[p] = I(A, (ex,ey,ez), stag, X_p) for the points that are alive (state NULL: all of them), finite and inside the \
+     *   closed box [0, e_q - stag_q] per direction; every other point receives NaN.  One call writes `out` (n doubles) completely; \
+     *   X, state and A are read-only.                                                                                    \
+     * ns3d_tracers_advance_*: one explicit midpoint (RK2) step through the frozen field; cx, cy, cz are the Courant factors dt/dx, \
+     *   dt/dy, dt/dz, formed by the caller in double (backtrack!'s dt*vxc/dx with the division taken out).  A particle is ACTIVE if \
+     *   state == 1, its three coordinates are finite and it is inside the closed box.  An inactive particle keeps its coordinates \
+     *   bit for bit, its state becomes 0, its U entries NaN.  An active one:                                             \
+     *     v1 = V(X);   Xm_q = X_q + 0.5*(v1_q*c_q);   if any Xm_q is not finite: Xn = Xm;   else v2 = V(Xm) (the midpoint may lie \
+     *     outside the box: the clamp of I covers that) and Xn_q = X_q + v2_q*c_q.                                        \
+     *   Xn is stored even when it lies outside the box (it records where the particle left); state becomes 1 if Xn is finite and \
+     *   inside the closed box, else 0.  U may be NULL; otherwise it is three blocks of n doubles and receives v1.  The fields are \
+     *   read-only.  X, state and U must not overlap the fields.  Through a field at rest every position keeps its bits, but for a \
+     *   coordinate -0.0 of an active particle, which -0.0 + (+0.0) turns into +0.0.                                      \
+     * Both are enqueued on the context's stream without a read-back (they block only as every call does without NS3D_ASYNC). \
+     * NS3D_ERR_ARG, with every output untouched: a null context, X, field or `out`; a null `state` in the advance; n < 0 (n == 0 is \
+     * a successful no-op); a grid below 3x3x3 resp. extents below 2 in the sample; a stagger flag other than 0 or 1; a Courant \
+     * factor that is not finite.                                                                                         \
+     * There is NO ns3d_mgpu form: a particle that crosses a seam between ranks has to migrate to its neighbour, and that is a \
+     * design of its own.  Positions are local to the arrays passed in. */                                                \
+    int ns3d_sample_##S(ns3d_ctx *, double *out, const double *X, const unsigned char *state, long n, const T *A, \
+                        int ex, int ey, int ez, int stag_x, int stag_y, int stag_z);                          \
+    int ns3d_tracers_advance_##S(ns3d_ctx *, double *X, unsigned char *state, double *U, long n, const T *Vx, \
+                                 const T *Vy, const T *Vz, double cx, double cy, double cz, int nx, int ny, int nz); \
     /* The monitor above on one rank.  Pr or C may be NULL: pr_min / pr_max resp. c_vol then come back as NaN (and take no    \
      * part in `nonfinite`).  Blocks for its read-back like ns3d_max_abs.  NS3D_ERR_ARG: null context / velocity / params /   \
      * output, a grid below 3×3×3, a cylinder form other than 0, 1, 2. */                                    \

@@ -43,6 +43,7 @@ export init_global_grid, finalize_global_grid, nx_g, ny_g, nz_g, x_g, y_g, z_g, 
 export diagnostics, Diag, DiagParams
 export stats_zeros, stats_reset!, stats_accumulate!, stats_finalize
 export vortex
+export sample, tracers_advance!
 export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
 
 const libns3d = get(ENV, "NS3D_LIB", joinpath(@__DIR__, "..", "navierstokes3d_amd", "libns3d.so"))
@@ -400,6 +401,39 @@ function vortex(Vx, Vy, Vz, dx, dy, dz; Wx = true, Wy = true, Wz = true, Q = tru
     check(ccall((:ns3d_vortex_f64, libns3d), Cint, (Ptr{Cvoid}, PF, PF, PF, PF, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint),
                 _ctx(), p[1], p[2], p[3], p[4], ptr(Vx), ptr(Vy), ptr(Vz), dx, dy, dz, nx, ny, nz))
     return out
+end
+"""
+    sample(A, X; state = nothing, stagger = (0, 0, 0))
+
+The field `A` interpolated at the points `X` — a `3×N`-element Float64 device array holding the index-space coordinates as three
+blocks ξ | η | ζ (`reshape` of an `N×3` array) — trilinear as `backtrack!` (`ns3d_sample_f64`; include/ns3d.h has the
+definition).  `stagger` flags the directions in which `A`'s nodes sit at integers.  Returns `N` Float64 values on the device, NaN
+for points that are dead (`state`: `N` UInt8, 1 = alive), not finite or outside the closed box.
+"""
+function sample(A, X; state = nothing, stagger = (0, 0, 0))
+    n = length(X) ÷ 3
+    out = AMDGPU.zeros(Float64, n); _sync()
+    st = state === nothing ? Ptr{UInt8}(C_NULL) : convert(Ptr{UInt8}, pointer(state))
+    check(ccall((:ns3d_sample_f64, libns3d), Cint, (Ptr{Cvoid}, PF, PF, Ptr{UInt8}, Clong, PF, Cint, Cint, Cint, Cint, Cint, Cint),
+                _ctx(), ptr(out), ptr(X), st, n, ptr(A), Cint(size(A, 1)), Cint(size(A, 2)), Cint(size(A, 3)),
+                Cint(stagger[1]), Cint(stagger[2]), Cint(stagger[3])))
+    return out
+end
+"""
+    tracers_advance!(X, state, Vx, Vy, Vz, dt, dx, dy, dz; U = nothing)
+
+One explicit-midpoint step of the particles `X` (index space, blocks ξ | η | ζ) with `state` (UInt8, 1 = alive) through the frozen
+velocity field, in place (`ns3d_tracers_advance_f64`).  Particles that leave the closed box `[0,nx]×[0,ny]×[0,nz]` die where they
+are.  `U` (same shape as `X`) receives the velocity at the start points.  One rank only: there is no multi-rank form.
+"""
+function tracers_advance!(X, state, Vx, Vy, Vz, dt, dx, dy, dz; U = nothing)
+    nx, ny, nz = Cint(size(Vx, 1) - 1), Cint(size(Vx, 2)), Cint(size(Vx, 3)); _sync()
+    n = length(state)
+    u = U === nothing ? PF(C_NULL) : ptr(U)
+    check(ccall((:ns3d_tracers_advance_f64, libns3d), Cint,
+                (Ptr{Cvoid}, PF, Ptr{UInt8}, PF, Clong, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint),
+                _ctx(), ptr(X), convert(Ptr{UInt8}, pointer(state)), u, n, ptr(Vx), ptr(Vy), ptr(Vz), dt / dx, dt / dy, dt / dz, nx, ny, nz))
+    return X
 end
 mutable struct StepFields          # struct ns3d_step_fields (include/ns3d.h): device pointers, IN/OUT (the fused step swaps X and X_o)
     Pr::PF; dPrdtau::PF; divV::PF

@@ -106,6 +106,37 @@ extern "C" int NS3D_FN(vortex)(ns3d_ctx *c, T *Wx, T *Wy, T *Wz, T *Q, const T *
         return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (need finite values > 0)", __func__, dx, dy, dz);
     return finish(c, DISPATCHG(c, dx, dy, dz, vortex<T>(c->stream, Wx, Wy, Wz, Q, Vx, Vy, Vz, dx, dy, dz, nx, ny, nz)), "vortex");
 }
+// ns3d_sample / ns3d_tracers_advance: one kernel build for every arithmetic mode (ns3d_tracers.hip), hence no DISPATCH
+static int tracers_count_check(long n, const char *fn)
+{
+    if (n < 0) return fail(NS3D_ERR_ARG, "%s: n = %ld is negative", fn, n);
+    if (n > 256L * 0x7fffffffL) return fail(NS3D_ERR_ARG, "%s: n = %ld exceeds one launch (256 x 2^31 points)", fn, n);
+    return NS3D_OK;
+}
+extern "C" int NS3D_FN(sample)(ns3d_ctx *c, double *out, const double *X, const unsigned char *state, long n, const T *A, int ex, int ey,
+                               int ez, int stag_x, int stag_y, int stag_z)
+{
+    CHECK_CTX(c); CHECK_PTRS(out, X, A);
+    const int rc = tracers_count_check(n, __func__);
+    if (rc) return rc;
+    if (ex < 2 || ey < 2 || ez < 2) return fail(NS3D_ERR_ARG, "%s: extents %dx%dx%d too small (need >= 2 per direction)", __func__, ex, ey, ez);
+    if ((stag_x | stag_y | stag_z) & ~1)
+        return fail(NS3D_ERR_ARG, "%s: stagger flags %d, %d, %d (each 0 or 1)", __func__, stag_x, stag_y, stag_z);
+    if (n == 0) return NS3D_OK;
+    return finish(c, ns3d_tracers::sample<T>(c->stream, out, X, state, n, A, ex, ey, ez, stag_x, stag_y, stag_z), "sample");
+}
+extern "C" int NS3D_FN(tracers_advance)(ns3d_ctx *c, double *X, unsigned char *state, double *U, long n, const T *Vx, const T *Vy,
+                                        const T *Vz, double cx, double cy, double cz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(X, state, Vx, Vy, Vz);
+    const int rc = tracers_count_check(n, __func__);
+    if (rc) return rc;
+    CHECK_GRID(nx, ny, nz, 3);
+    if (!(std::isfinite(cx) && std::isfinite(cy) && std::isfinite(cz)))
+        return fail(NS3D_ERR_ARG, "%s: Courant factors %g, %g, %g (need finite values)", __func__, cx, cy, cz);
+    if (n == 0) return NS3D_OK;
+    return finish(c, ns3d_tracers::advance<T>(c->stream, X, state, U, n, Vx, Vy, Vz, cx, cy, cz, nx, ny, nz), "tracers_advance");
+}
 extern "C" int NS3D_FN(correct_V)(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *Pr, double dt, double rho, double dx, double dy, double dz,
                                   int nx, int ny, int nz)
 {

@@ -187,3 +187,14 @@ hipError_t ns3d_direct_inv_yx(hipStream_t s, double *U, double *tmp, const doubl
                               int nz);
 // chunk-major [c][k][i + mx·(ky − ky0_c)] (ns3d_direct_ychunk's P chunks, each over the mz planes) → plane-major dst
 hipError_t ns3d_direct_unpack(hipStream_t s, const double *src, double *dst, int mx, int my, int mz, int P);
+
+// ---- ns3d_tracers.hip: ns3d_sample / ns3d_tracers_advance.  One compilation without contraction serves every arithmetic mode (the
+// entry points' contract: the same bits from STRICT, NS3D_IEEE_DIV and FAST contexts).  n > 0; state (sample) and U (advance) may be null.
+namespace ns3d_tracers {
+template <class T>
+hipError_t sample(hipStream_t s, double *out, const double *X, const unsigned char *state, long n, const T *A, int ex, int ey, int ez,
+                  int stag_x, int stag_y, int stag_z);
+template <class T>
+hipError_t advance(hipStream_t s, double *X, unsigned char *state, double *U, long n, const T *Vx, const T *Vy, const T *Vz, double cx,
+                   double cy, double cz, int nx, int ny, int nz);
+}

@@ -25,8 +25,9 @@ from .halo import ZSlabGrid
 from .slab import SlabPTSolver
 from .stats import RunningStats
 from .vortex import VortexFields, save_bins as _save_vortex_bins
+from .tracers import Probes, Tracers
 from .params import gpu_params, multi_params
-from .vis import save_frame_gpu, save_frame_multi, save_frame_vortex
+from .vis import save_frame_gpu, save_frame_multi, save_frame_tracers, save_frame_vortex
 
 
 def _alloc(nx, ny, nz, dtype, device):
@@ -166,7 +167,7 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
-                       statistics=None, stats_every=1, vortex=False):
+                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -199,7 +200,19 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     of every frame's state.  info.vortex gets Wx, Wy, Wz, Q as halo-stripped global host arrays on the root, gathered like the
     fields; do_save adds out_Wx_v_%04d.bin, out_Wy_v_…, out_Wz_v_…, out_Q_v_… (Float32, same directory and counter), do_vis adds
     3D_NavierStokes_xy_Wz_%04d.png, …_xy_Q_…, …_xz_Wy_…, …_xz_Q_… (colour range: the data's own).  `one_call` stays in use;
-    read-only: every other result keeps its bits."""
+    read-only: every other result keeps its bits.
+    tracers=… (default None: not one extra call, file or attribute): Lagrangian tracer particles (tracers.Tracers,
+    ns3d_tracers_advance on the device).  An (N,3) array gives physical start points (the box is [−lx/2, lx/2] × [−ly/2, ly/2] ×
+    [−lz/2, lz/2]), an int N gives N points uniform in the box from a generator seeded with 0.  They are advanced once per time
+    step, after advect! and :477's halo update, with the step's dt through the current Vx, Vy, Vz.  info.tracers gets x, y, z
+    (physical), alive and steps; do_save adds out_tracers_%04d.bin per saved frame (Float32 (4,N): x, y, z, alive), do_vis
+    3D_NavierStokes_tracers_%04d.png per drawn frame (an x-y scatter).
+    probes=… (default None): an (M,3) array of physical points at which u, v, w, p are sampled at the end of every step (four
+    ns3d_sample calls; the series stay on the device and are read back ONCE, after the last step): info.probes gets u, v, w, p
+    of shape (nt, M), NaN for a point outside the box.
+    Both are read-only with respect to the flow — every other result keeps its bits — and leave `one_call` in use.  ONE RANK
+    only: on more than one rank either keyword raises Ns3dError, because a particle that crosses a seam has to migrate to the
+    neighbouring rank and there is no ns3d_mgpu form of these calls yet."""
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -210,6 +223,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         p0 = multi_params(nx, **shape)
         grid = ZSlabGrid(p0.nx, p0.ny, p0.nz)                                                  # :325
     P = grid.P
+    if P > 1 and (tracers is not None or probes is not None):
+        raise L.Ns3dError("tracers= / probes= run on one rank only (this grid has %d): particles that cross a seam between ranks "
+                          "would have to migrate, and ns3d_tracers_advance / ns3d_sample have no ns3d_mgpu form" % P)
     local_ranks = list(getattr(grid, "local_ranks", [grid.me]))
     if hasattr(grid, "contexts"):
         ctxs = list(grid.contexts)                         # contexts of the ns3d_mgpu's ranks (their devices)
@@ -248,6 +264,14 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     nz_g_all = dims[2] * (nz - 2) + 2
     ny_g_all = dims[1] * (ny - 2) + 2
     vort = VortexFields((nx, ny, nz), ctxs, (p.dx, p.dy, p.dz), dtype) if vortex else None
+    trc, prb = _observers(tracers, probes, (nx, ny, nz), ctxs[0], p, nt)
+
+    def tracers_frame(save, vis):
+        rec = trc.record()
+        if save:
+            Tracers.save_bins(rec, iframe)
+        if vis:
+            save_frame_tracers(rec, p.lx, p.ly, iframe)
 
     def vortex_frame(save, vis):
         """the vortex fields of the state a frame shows: computed, gathered, written by the root"""
@@ -268,6 +292,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             save_frame_multi(gathered, ny_g_all, nz_g_all, iframe)
         if vort is not None:
             vortex_frame(do_save, do_vis)
+        if trc is not None:
+            tracers_frame(do_save, do_vis)
     iframe += 1
     pts = [K.pt_params(f.Pr, q.rho, q.dt, q.dtau, q.damp, q.dx, q.dy, q.dz, L.NS3D_BC_MULTI, q.owns_outlet, 0.0, q.g,
                        q.coords[2] > 0, q.coords[2] < dims[2] - 1) for f, q in zip(fs, ps)]
@@ -329,6 +355,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                 _save_frame(grid, gathered, iframe)
             if vort is not None:
                 vortex_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
+            if trc is not None:
+                tracers_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
             iframe += 1
 
     for it in range(1, nt + 1):                                                               # :446
@@ -342,6 +370,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             info.iters.append(done); info.errs.append(errs)
             if running is not None and _stats_due(it, statistics, stats_every):
                 running.sample(fs)                          # ns3d_time_step has swapped the names: fs holds the new fields
+            _observe(trc, prb, fs[0], p.dt)
             frames(it)
             continue
         if fuse_predictor:
@@ -436,6 +465,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                 # :477 (not C)
         if running is not None and _stats_due(it, statistics, stats_every):
             running.sample(fs)
+        _observe(trc, prb, fs[0], p.dt)
         frames(it)
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
@@ -447,10 +477,40 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     if vort is not None:
         vort.compute(fs)
         info.vortex = vort.gathered(grid)
+    if trc is not None:
+        info.tracers = trc.record()
+    if prb is not None:
+        info.probes = prb.gathered()
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
     return out + ((info,) if return_info else ())                                             # :535
+
+
+def _observers(tracers, probes, shape, ctx, p, nt):
+    """(Tracers | None, Probes | None) of a one-rank run from the drivers' `tracers=` / `probes=` keywords; the box's low corner is
+    (−lx/2, −ly/2, −lz/2) in both scripts"""
+    spacings, origin = (p.dx, p.dy, p.dz), (-p.lx / 2, -p.ly / 2, -p.lz / 2)
+    trc = prb = None
+    if tracers is not None:
+        trc = Tracers(shape, ctx, spacings, origin)
+        if isinstance(tracers, (int, np.integer)) and not isinstance(tracers, bool):
+            if tracers < 0:
+                raise L.Ns3dError("tracers = %r (a number of particles >= 0, or an (N,3) array of start points)" % (tracers,))
+            trc.seed_random(int(tracers), 0)
+        else:
+            trc.seed_points(tracers)
+    if probes is not None:
+        prb = Probes(shape, ctx, spacings, origin, probes, nt)
+    return trc, prb
+
+
+def _observe(trc, prb, f, dt):
+    """end of a time step: the particles move through the step's final velocity field, the probes sample the final state"""
+    if trc is not None:
+        trc.advance(f, dt)
+    if prb is not None:
+        prb.record(f)
 
 
 def _check_stats_options(statistics, stats_every):
@@ -516,7 +576,7 @@ def _save_mat(path, f, p, step0):
 
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
-          diagnostics=False, statistics=None, stats_every=1, vortex=False):
+          diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -528,7 +588,9 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     included).
     vortex=True: as in run_navierstokes3D, of the final state and — with do_vis — of every frame's; info.vortex holds the FULL
     local arrays Wx, Wy, Wz, Q (their boundary entries are 0); do_vis adds 3D_NavierStokes_Wz_%04d.png, …_Q_…, …_long_Wy_…,
-    …_long_Q_… (do_save's MAT files are left as the reference writes them)."""
+    …_long_Q_… (do_save's MAT files are left as the reference writes them).
+    tracers / probes: as in run_navierstokes3D, advanced resp. sampled after :142; do_save adds out_save/out_tracers_%04d.bin beside
+    each MAT file (numbered 0, 1, … in the order the MAT files are written), do_vis 3D_NavierStokes_tracers_%04d.png per frame."""
     if device is None:
         device = torch.cuda.current_device()
     _check_stats_options(statistics, stats_every)
@@ -545,10 +607,13 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     pt = K.pt_params(f.Pr, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, L.NS3D_BC_GPU, False, 0.0, p.g)
     info = SimpleNamespace(iters=[], errs=[], params=p)
     nsave = nvis = 10                                                                         # :50,52
+    trc, prb = _observers(tracers, probes, (nx, ny, nz), ctx, p, nt)
     if do_save:                                                                               # :89
         os.makedirs("./out_save", exist_ok=True)
         ctx.sync()
         _save_mat("out_save/step_0.mat", f, p, True)
+        if trc is not None:
+            Tracers.save_bins(trc.record(), 0)
     iframe = 0
     host = lambda: {n: K.to_numpy(getattr(f, n)) for n in ("Pr", "C", "Vx", "Vy", "Vz")}
     vort = VortexFields((nx, ny, nz), [ctx], (p.dx, p.dy, p.dz), dtype) if vortex else None
@@ -562,6 +627,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         save_frame_gpu(host(), ny, nz, iframe)
         if vort is not None:
             vortex_frame()
+        if trc is not None:
+            save_frame_tracers(trc.record(), p.lx, p.ly, iframe)
         iframe += 1
     step_params = None
     monitor = None
@@ -587,15 +654,20 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             info.iters.append(done); info.errs.append(errs)
             if running is not None and _stats_due(it, statistics, stats_every):
                 running.sample([f])                         # ns3d_time_step has swapped the names: f holds the new fields
+            _observe(trc, prb, f, p.dt)
             if do_vis and it % nvis == 0:                                                     # :143-167
                 ctx.sync()
                 save_frame_gpu(host(), ny, nz, iframe)
                 if vort is not None:
                     vortex_frame()
+                if trc is not None:
+                    save_frame_tracers(trc.record(), p.lx, p.ly, iframe)
                 iframe += 1
             if do_save and it % nsave == 0:                                                   # :168-170
                 ctx.sync()
                 _save_mat("out_save/step_%d.mat" % it, f, p, False)
+                if trc is not None:
+                    Tracers.save_bins(trc.record(), it // nsave)
             continue
         if fused:
             if it == nt:            # the stress arrays as the reference leaves them after its last step: same final state
@@ -650,15 +722,20 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=ctx)  # :142
         if running is not None and _stats_due(it, statistics, stats_every):
             running.sample([f])
+        _observe(trc, prb, f, p.dt)
         if do_vis and it % nvis == 0:                                                         # :143-167
             ctx.sync()
             save_frame_gpu(host(), ny, nz, iframe)
             if vort is not None:
                 vortex_frame()
+            if trc is not None:
+                save_frame_tracers(trc.record(), p.lx, p.ly, iframe)
             iframe += 1
         if do_save and it % nsave == 0:                                                       # :168-170
             ctx.sync()
             _save_mat("out_save/step_%d.mat" % it, f, p, False)
+            if trc is not None:
+                Tracers.save_bins(trc.record(), it // nsave)
     if fused and faithful and nt > 0:
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()
@@ -668,4 +745,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     if vort is not None:
         vort.compute([f])
         info.vortex = vort.local(0)
+    if trc is not None:
+        info.tracers = trc.record()
+    if prb is not None:
+        info.probes = prb.gathered()
     return f, info

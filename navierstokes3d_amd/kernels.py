@@ -385,6 +385,47 @@ def vortex(Vx, Vy, Vz, dx, dy, dz, *, Wx=None, Wy=None, Wz=None, Q=None, ctx=Non
                        _chk(Vz, (nx, ny, nz + 1), "Vz"), *_d(dx, dy, dz), nx, ny, nz)
 
 
+def _chk_points(t, n, blocks, dtype, name, ref):
+    """a contiguous device array of `blocks`·n elements of `dtype` on the fields' device: X and U are (3, n) float64, state (n,) uint8"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+        raise L.Ns3dError("%s must be a %s CUDA/HIP tensor" % (name, dtype))
+    if t.device != ref.device:
+        raise L.Ns3dError("%s is on %s, the field on %s" % (name, t.device, ref.device))
+    if not t.is_contiguous() or t.numel() != blocks * n:
+        raise L.Ns3dError("%s must be contiguous with %d x %d elements, got shape %s" % (name, blocks, n, tuple(t.shape)))
+    return C.c_void_p(t.data_ptr())
+
+
+def sample(A, X, out, state=None, stagger=(0, 0, 0), ctx=None):
+    """ns3d_sample: the field A (any extents ≥ 2; `stagger` flags the directions whose nodes sit at integers) interpolated at the
+    points X — a (3, n) float64 array of INDEX-space coordinates ξ | η | ζ — into out (n float64), trilinear as backtrack!
+    (include/ns3d.h has the definition; the same bits in every arithmetic mode).  Points that are dead (state, n uint8, optional),
+    not finite or outside the closed box receive NaN.  Enqueues; no read-back."""
+    n = out.numel() if isinstance(out, torch.Tensor) else 0
+    ex, ey, ez = A.shape
+    sx, sy, sz = (int(q) for q in stagger)
+    _ctx(ctx, A).call("sample", A, _chk_points(out, n, 1, torch.float64, "out", A), _chk_points(X, n, 3, torch.float64, "X", A),
+                      None if state is None else _chk_points(state, n, 1, torch.uint8, "state", A), C.c_long(n),
+                      _chk(A, None, "A"), ex, ey, ez, sx, sy, sz)
+
+
+def tracers_advance(X, state, Vx, Vy, Vz, cx, cy, cz, U=None, ctx=None):
+    """ns3d_tracers_advance: one explicit-midpoint step of the particles X ((3, n) float64, index space) with state (n uint8: 1 alive)
+    through the frozen field Vx, Vy, Vz; cx, cy, cz = dt/dx, dt/dy, dt/dz.  Particles that leave the closed box [0,nx]×[0,ny]×[0,nz]
+    or reach a non-finite position die where they are; U ((3, n) float64, optional) receives the velocity at the start points.
+    In place; enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    n = state.numel() if isinstance(state, torch.Tensor) else 0
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("tracers_advance", Vx, _chk_points(X, n, 3, torch.float64, "X", Vx),
+                       _chk_points(state, n, 1, torch.uint8, "state", Vx),
+                       None if U is None else _chk_points(U, n, 3, torch.float64, "U", Vx), C.c_long(n),
+                       _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"), _chk(Vz, (nx, ny, nz + 1), "Vz"),
+                       *_d(cx, cy, cz), nx, ny, nz)
+
+
 def _untyped(ctx, ref, name, *args):
     c = _ctx(ctx, ref)
     if not getattr(c, "_pinned", False) and torch.cuda.current_stream(c.device).cuda_stream != c._stream:

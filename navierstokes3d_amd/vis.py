@@ -118,3 +118,26 @@ def save_frame_vortex(rec, ny, nz, iframe, outdir="viz3D_out", gpu_names=False):
         heatmap_png(path, A[:, :, kz] if plane == "xy" else A[:, jy, :])
         out.append(path)
     return out
+
+
+def save_frame_tracers(rec, lx, ly, iframe, outdir="viz3D_out", width=512):
+    """One x-y scatter frame of the tracer particles (tracers.py: a record with x, y, z, alive; the box is [−lx/2, lx/2] ×
+    [−ly/2, ly/2], y upwards): `3D_NavierStokes_tracers_%04d.png`, live particles inferno-coloured by their z, on black; dead
+    particles and particles outside the frame are not drawn.  The reference draws nothing of the kind."""
+    os.makedirs(outdir, exist_ok=True)
+    w = int(width)
+    h = max(1, int(round(w * ly / lx)))
+    img = np.zeros((h, w, 3), dtype=np.uint8)
+    x, y, z = (np.asarray(getattr(rec, n), dtype=np.float64) for n in ("x", "y", "z"))
+    ok = np.asarray(rec.alive, dtype=bool) & np.isfinite(x) & np.isfinite(y) & np.isfinite(z)
+    if ok.any():
+        px = np.floor((x[ok] / lx + 0.5) * w).astype(np.int64)
+        py = np.floor((0.5 - y[ok] / ly) * h).astype(np.int64)
+        zz = z[ok]
+        lo, hi = float(zz.min()), float(zz.max())
+        col = colour_map(0.25 + 0.75 * ((zz - lo) / (hi - lo) if hi > lo else np.full_like(zz, 0.5)))
+        m = (px >= 0) & (px < w) & (py >= 0) & (py < h)
+        img[py[m], px[m]] = col[m]
+    path = os.path.join(outdir, "3D_NavierStokes_tracers_%04d.png" % iframe)
+    write_png(path, img)
+    return path
