@@ -327,6 +327,53 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
                         int ex, int ey, int ez, int stag_x, int stag_y, int stag_z);                          \
     int ns3d_tracers_advance_##S(ns3d_ctx *, double *X, unsigned char *state, double *U, long n, const T *Vx, \
                                  const T *Vy, const T *Vz, double cx, double cy, double cz, int nx, int ny, int nz); \
+    /* Isosurface: the triangles of the level set A = iso, extracted and compacted on the device — what one looks at instead of the field.  \
+     * A is any packed column-major array of extents (ex,ey,ez), each >= 2; its entries are NODES at the integer positions (i,j,k) (the     \
+     * caller knows where they sit physically: stagger and spacings are applied by the caller).  B (may be NULL) is a second array of the   \
+     * same extents whose values are interpolated at the surface's vertices.  box (may be NULL: the whole array) is six ints lo_x, lo_y,    \
+     * lo_z, hi_x, hi_y, hi_z, a closed node range with 0 <= lo_q < hi_q <= e_q-1; the CUBES processed are those whose eight corners lie    \
+     * in it (lower corner lo_q <= i_q <= hi_q-1).  origin (may be NULL: 0,0,0) is three ints added to the integer node indices BEFORE any  \
+     * fractional part, so that the ranks of a decomposed grid emit bit-identical vertices on a shared face.                                \
+     * Values are converted to double on load; all arithmetic after that is fp64 and NEVER contracted, in any build: STRICT, NS3D_IEEE_DIV  \
+     * and FAST contexts return the same bits, as for ns3d_sample.  The one division per vertex is the plain IEEE quotient.                 \
+     * MARCHING TETRAHEDRA on the Kuhn decomposition.  A cube's corners are numbered c = di + 2 dj + 4 dk.  Its six tetrahedra are the      \
+     * six axis orders pi in lexicographic order xyz, xzy, yxz, yzx, zxy, zyx; tetrahedron pi has the vertices v0 = corner 0, v1 = v0 +     \
+     * e_pi1, v2 = v1 + e_pi2, v3 = corner 7: a componentwise increasing chain, so every tetrahedron edge runs from a node `lo` to a node   \
+     * `hi` with hi_q - lo_q in {0,1}, hi being the end with the larger linear index.  The decomposition is the same in every cube:         \
+     * neighbouring cubes agree on their shared face diagonals, the surface is watertight.                                                  \
+     * A node is INSIDE if a >= iso, else OUTSIDE.  A cube with a non-finite corner (NaN, +-Inf) emits nothing.  iso must be finite.        \
+     * VERTEX on an edge with one inside and one outside end, always formed from lo towards hi, whichever tetrahedron or cube asks:         \
+     *   t = (iso - a_lo) / (a_hi - a_lo)            (the denominator is never 0)                                                           \
+     *   pos_q = (double)(lo_q + origin_q) + (hi_q > lo_q ? t : 0.0)                                                                        \
+     *   value = b_hi*t + b_lo*(1.0 - t)              (backtrack!'s lerp)                                                                   \
+     * A vertex depends only on its edge: every tetrahedron sharing the edge produces the same bits, a mesh can be indexed by exact         \
+     * comparison.  As NumPy, for the cubes with lower corner (I,J,K) (index arrays), a tetrahedron edge from corner clo to corner chi:     \
+     *   d = lambda c: ((c >> 0) & 1, (c >> 1) & 1, (c >> 2) & 1);  at = lambda F, c: F[I+d(c)[0], J+d(c)[1], K+d(c)[2]].astype(np.float64) \
+     *   t = (iso - at(A,clo)) / (at(A,chi) - at(A,clo))                                                                                    \
+     *   pos = [((I,J,K)[q] + d(clo)[q] + origin[q]).astype(np.float64) + (t if d(chi)[q] > d(clo)[q] else 0.0) for q in range(3)]          \
+     *   value = at(B,chi)*t + at(B,clo)*(1.0 - t)                                                                                          \
+     * TRIANGLES per tetrahedron, v0..v3 in the tetrahedron-local order, E(u,v) the vertex on the edge between v_u and v_v:                 \
+     *   0 or 4 inside: none.   1 or 3 inside: one; a the single vertex on its side, b < c < d the other three: E(a,b), E(a,c), E(a,d).     \
+     *   2 and 2: two; p < q inside, r < s outside: the quad E(p,r), E(p,s), E(q,s), E(q,r) split along E(p,r)-E(q,s) into                  \
+     *   (E(p,r), E(p,s), E(q,s)) and (E(p,r), E(q,s), E(q,r)).                                                                             \
+     * Each triangle is then oriented so that its right-hand normal points from the inside vertices towards the outside ones (towards       \
+     * decreasing A); it is flipped by swapping its last two vertices.  The orientation is COMBINATORIAL: a fixed bit per (tetrahedron,     \
+     * case), derived once by evaluating the rule on the unit cube with inside = 1, outside = 0, iso = 0.5, never a floating-point test     \
+     * at run time.  A node value equal to iso gives t = 0 or t = 1 and possibly zero-area triangles; they are emitted like any other:      \
+     * the count is a function of the inside masks alone.                                                                                   \
+     * ORDER: cubes in linear order over the box, x fastest, then y, then z; within a cube tetrahedra 0..5; within a tetrahedron as         \
+     * listed.  At most 12 triangles per cube.                                                                                              \
+     * OUTPUTS (device memory): tri holds 9 doubles per triangle, x0,y0,z0,x1,y1,z1,x2,y2,z2; val (may be NULL, must be NULL if B is) 3     \
+     * doubles per triangle.  *n_tri_host (host memory) receives the number of triangles the surface HAS; the call blocks for this          \
+     * read-back like ns3d_diagnostics.  Only the first min(n, cap) triangles, a complete prefix in the order above, are written;           \
+     * nothing is written beyond cap triangles.  cap = 0 with tri = NULL is the count-only form.  n > cap is NS3D_OK: the caller            \
+     * compares the two numbers.  Two calls on the same input return the same bits in the same order (no atomics decide a position).        \
+     * The inputs are read-only.  The context keeps 12 bytes of scratch per row segment of 64 cubes, grown lazily.                          \
+     * NS3D_ERR_ARG, with every output and *n_tri_host untouched: a null context, A or n_tri_host; an extent below 2; a box outside the     \
+     * array or with hi_q <= lo_q; cap < 0; tri == NULL with cap > 0; val != NULL with B == NULL; iso not finite.                           \
+     * There is no ns3d_mgpu form: a rank extracts the cubes it owns with its own box and origin, the pieces are concatenated. */           \
+    int ns3d_isosurface_##S(ns3d_ctx *, const T *A, const T *B, int ex, int ey, int ez, const int *box, const int *origin, \
+                            double iso, double *tri, double *val, long long cap, long long *n_tri_host);          \
     /* The monitor above on one rank.  Pr or C may be NULL: pr_min / pr_max resp. c_vol then come back as NaN (and take no    \
      * part in `nonfinite`).  Blocks for its read-back like ns3d_max_abs.  NS3D_ERR_ARG: null context / velocity / params /   \
      * output, a grid below 3×3×3, a cylinder form other than 0, 1, 2. */                                    \

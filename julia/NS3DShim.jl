@@ -44,6 +44,7 @@ export diagnostics, Diag, DiagParams
 export stats_zeros, stats_reset!, stats_accumulate!, stats_finalize
 export vortex
 export sample, tracers_advance!
+export isosurface_count, isosurface
 export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
 
 const libns3d = get(ENV, "NS3D_LIB", joinpath(@__DIR__, "..", "navierstokes3d_amd", "libns3d.so"))
@@ -434,6 +435,42 @@ function tracers_advance!(X, state, Vx, Vy, Vz, dt, dx, dy, dz; U = nothing)
                 (Ptr{Cvoid}, PF, Ptr{UInt8}, PF, Clong, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint),
                 _ctx(), ptr(X), convert(Ptr{UInt8}, pointer(state)), u, n, ptr(Vx), ptr(Vy), ptr(Vz), dt / dx, dt / dy, dt / dz, nx, ny, nz))
     return X
+end
+_iso_ints(v, n) = v === nothing ? Ptr{Cint}(C_NULL) : (length(v) == n ? Cint[Cint(q) for q in v] : error("isosurface: expected $n integers"))
+"""
+    isosurface_count(A, iso; box = nothing, origin = nothing)
+
+The number of triangles of the level set `A = iso` (`ns3d_isosurface_f64` in its count-only form; include/ns3d.h has the
+definition: marching tetrahedra on the nodes of `A`).  `box` = (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), a closed node range counted
+from 0; `origin` = three integers added to the node indices.
+"""
+function isosurface_count(A, iso; box = nothing, origin = nothing)
+    n = Ref{Clonglong}(0); _sync()
+    b, o = _iso_ints(box, 6), _iso_ints(origin, 3)
+    GC.@preserve b o check(ccall((:ns3d_isosurface_f64, libns3d), Cint,
+                (Ptr{Cvoid}, PF, PF, Cint, Cint, Cint, Ptr{Cint}, Ptr{Cint}, Cdouble, PF, PF, Clonglong, Ptr{Clonglong}),
+                _ctx(), ptr(A), PF(C_NULL), Cint(size(A, 1)), Cint(size(A, 2)), Cint(size(A, 3)), b, o, Float64(iso), PF(C_NULL), PF(C_NULL), 0, n))
+    return Int(n[])
+end
+"""
+    isosurface(A, iso; color = nothing, box = nothing, origin = nothing)
+
+The triangles of the level set `A = iso` in the index space of `A`'s nodes, counted from 0: a `9×n` Float64 device array
+(x0,y0,z0,x1,y1,z1,x2,y2,z2 per triangle) and, with `color` (an array of `A`'s size), a `3×n` array of its values at the vertices
+(`nothing` otherwise).  One count-only call, an allocation of exactly that size, one filling call.
+"""
+function isosurface(A, iso; color = nothing, box = nothing, origin = nothing)
+    n = isosurface_count(A, iso; box = box, origin = origin)
+    tri = AMDGPU.zeros(Float64, 9, n)
+    val = color === nothing ? nothing : AMDGPU.zeros(Float64, 3, n)
+    n == 0 && return tri, val
+    m = Ref{Clonglong}(0); _sync()
+    b, o = _iso_ints(box, 6), _iso_ints(origin, 3)
+    GC.@preserve b o check(ccall((:ns3d_isosurface_f64, libns3d), Cint,
+                (Ptr{Cvoid}, PF, PF, Cint, Cint, Cint, Ptr{Cint}, Ptr{Cint}, Cdouble, PF, PF, Clonglong, Ptr{Clonglong}),
+                _ctx(), ptr(A), color === nothing ? PF(C_NULL) : ptr(color), Cint(size(A, 1)), Cint(size(A, 2)), Cint(size(A, 3)), b, o,
+                Float64(iso), ptr(tri), val === nothing ? PF(C_NULL) : ptr(val), n, m))
+    return tri, val
 end
 mutable struct StepFields          # struct ns3d_step_fields (include/ns3d.h): device pointers, IN/OUT (the fused step swaps X and X_o)
     Pr::PF; dPrdtau::PF; divV::PF

@@ -28,6 +28,8 @@ UNITS = [
     ("ns3d_direct.hip", "ns3d_direct.o", []),
     # ns3d_sample / ns3d_tracers_advance: the same bits in every arithmetic mode, so one compilation and never an FMA
     ("ns3d_tracers.hip", "ns3d_tracers.o", ["-ffp-contract=off"]),
+    # ns3d_isosurface: likewise
+    ("ns3d_isosurface.hip", "ns3d_isosurface.o", ["-ffp-contract=off"]),
     ("ns3d_api.cpp", "ns3d_api.o", ["-x", "hip"]),
     ("ns3d_mgpu.cpp", "ns3d_mgpu.o", ["-x", "hip"]),
 ]

@@ -162,6 +162,7 @@ void ns3d_destroy(ns3d_ctx *c)
     if (c->pingpong_d) (void)hipFree(c->pingpong_d);
     if (c->diag_dev) (void)hipFree(c->diag_dev);
     if (c->diag_host) (void)hipHostFree(c->diag_host);
+    if (c->iso_dev) (void)hipFree(c->iso_dev);
     if (c->key_dev) (void)hipFree(c->key_dev);
     if (c->key_host) (void)hipHostFree(c->key_host);
     if (c->masked_stream) { (void)hipStreamSynchronize(c->masked_stream); (void)hipStreamDestroy(c->masked_stream); }
@@ -1047,6 +1048,48 @@ static int check_planes(const ns3d_pt_params *p, int k0, int k1, const char *fn)
 static int check_no_halos(const ns3d_pt_params *p, const char *fn)
 {
     if (p->z_lo_is_halo || p->z_hi_is_halo) return fail(NS3D_ERR_ARG, "%s: z-slab ranks pass ghost-extended buffers, not halo flags", fn);
+    return NS3D_OK;
+}
+// ns3d_isosurface: the argument checks that do not depend on the element type, the geometry of the launch and the context's scratch
+// (8 B for the total, 8 B per scan workgroup, 12 B per row segment of 64 cubes: counts and their scan), grown lazily
+static int iso_prepare(ns3d_ctx *c, int ex, int ey, int ez, const int *box, const int *origin, double iso, const void *tri, const void *val,
+                       const void *B, long long cap, const char *fn, ns3d_iso_geom *g, ns3d_iso_scratch *w)
+{
+    if (ex < 2 || ey < 2 || ez < 2) return fail(NS3D_ERR_ARG, "%s: extents %dx%dx%d too small (need >= 2 per direction)", fn, ex, ey, ez);
+    const int e[3] = {ex, ey, ez};
+    int lo[3] = {0, 0, 0}, hi[3] = {ex - 1, ey - 1, ez - 1};
+    if (box)
+        for (int q = 0; q < 3; ++q) {
+            lo[q] = box[q];
+            hi[q] = box[3 + q];
+            if (lo[q] < 0 || hi[q] <= lo[q] || hi[q] > e[q] - 1)
+                return fail(NS3D_ERR_ARG, "%s: box [%d,%d] in direction %d (need 0 <= lo < hi <= %d)", fn, lo[q], hi[q], q, e[q] - 1);
+        }
+    if (cap < 0) return fail(NS3D_ERR_ARG, "%s: cap = %lld is negative", fn, cap);
+    if (!tri && cap > 0) return fail(NS3D_ERR_ARG, "%s: tri is NULL with cap = %lld", fn, cap);
+    if (val && !B) return fail(NS3D_ERR_ARG, "%s: val given without B", fn);
+    if (!std::isfinite(iso)) return fail(NS3D_ERR_ARG, "%s: iso = %g is not finite", fn, iso);
+    g->ex = ex; g->ey = ey;
+    g->lox = lo[0]; g->loy = lo[1]; g->loz = lo[2];
+    g->cx = hi[0] - lo[0]; g->cy = hi[1] - lo[1]; g->cz = hi[2] - lo[2];
+    g->nseg = (g->cx + 63) / 64;
+    g->gy = (g->cy + NS3D_ISO_ROWS - 1) / NS3D_ISO_ROWS;
+    g->gz = (g->cz + NS3D_ISO_KZ - 1) / NS3D_ISO_KZ;
+    g->ox = origin ? origin[0] : 0; g->oy = origin ? origin[1] : 0; g->oz = origin ? origin[2] : 0;
+    if ((unsigned long long)g->nseg * g->gy * g->gz > 0x7fffffffull)
+        return fail(NS3D_ERR_ARG, "%s: a box of %dx%dx%d cubes exceeds one launch", fn, g->cx, g->cy, g->cz);
+    w->nsegs = (unsigned long long)g->nseg * g->cy * g->cz;
+    w->nblk = (unsigned)((w->nsegs + NS3D_ISO_SCAN_BLOCK - 1) / NS3D_ISO_SCAN_BLOCK);
+    const size_t need = 8 * (size_t)(1 + w->nblk + w->nsegs) + 4 * (size_t)w->nsegs;
+    if (c->iso_bytes < need) {
+        if (c->iso_dev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->iso_dev); c->iso_dev = nullptr; c->iso_bytes = 0; }
+        HIPCHK(c, hipMalloc(&c->iso_dev, need));
+        c->iso_bytes = need;
+    }
+    w->total = (unsigned long long *)c->iso_dev;
+    w->bsum = w->total + 1;
+    w->segbase = w->bsum + w->nblk;
+    w->segcnt = (unsigned *)(w->segbase + w->nsegs);
     return NS3D_OK;
 }
 extern "C" int ns3d_poisson_direct_f64(ns3d_ctx *, double *, double *, const double *, const ns3d_pt_params *);      // ns3d_direct.hip

@@ -137,6 +137,24 @@ extern "C" int NS3D_FN(tracers_advance)(ns3d_ctx *c, double *X, unsigned char *s
     if (n == 0) return NS3D_OK;
     return finish(c, ns3d_tracers::advance<T>(c->stream, X, state, U, n, Vx, Vy, Vz, cx, cy, cz, nx, ny, nz), "tracers_advance");
 }
+// ns3d_isosurface: count, scan and read the total back (blocking); then, where there is room for triangles, the emit launch
+extern "C" int NS3D_FN(isosurface)(ns3d_ctx *c, const T *A, const T *B, int ex, int ey, int ez, const int *box, const int *origin, double iso,
+                                   double *tri, double *val, long long cap, long long *n_tri_host)
+{
+    CHECK_CTX(c); CHECK_PTRS(A, n_tri_host);
+    ns3d_iso_geom g;
+    ns3d_iso_scratch w;
+    const int rc = iso_prepare(c, ex, ey, ez, box, origin, iso, tri, val, B, cap, __func__, &g, &w);
+    if (rc) return rc;
+    hipError_t e = ns3d_iso::count_scan<T>(c->stream, A, g, iso, w);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "isosurface count launch: %s", hipGetErrorString(e)); }
+    HIPCHK(c, hipMemcpyAsync(c->key_host, w.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const long long n = (long long)c->key_host[0];
+    *n_tri_host = n;
+    if (n == 0 || cap == 0) return NS3D_OK;
+    return finish(c, ns3d_iso::emit<T>(c->stream, A, B, g, iso, w, tri, val, cap), "isosurface");
+}
 extern "C" int NS3D_FN(correct_V)(ns3d_ctx *c, T *Vx, T *Vy, T *Vz, const T *Pr, double dt, double rho, double dx, double dy, double dz,
                                   int nx, int ny, int nz)
 {

@@ -50,6 +50,8 @@ struct ns3d_ctx {
     unsigned long long *diag_host = nullptr; // pinned mirror of the result / staging words
     void *direct_plan = nullptr;            // ns3d_direct.hip: eigenvector matrices and scratch of the direct Poisson solve
     void (*direct_free)(void *) = nullptr;
+    void *iso_dev = nullptr;                // ns3d_isosurface: segment counts, their scan and the total (grown lazily)
+    size_t iso_bytes = 0;
     void clear_graphs()
     {
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.exec);

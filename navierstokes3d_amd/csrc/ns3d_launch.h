@@ -84,6 +84,37 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
 // 8 / 16 / 32 planes at 512³ in fp64 and within 7 % of the best elsewhere (profiles/vortex_variants_ab.log).
 #define NS3D_VORTEX_KZ 16
 
+// ns3d_isosurface (ns3d_isosurface.hip, compiled once: no arithmetic mode to select).  k_iso_count / k_iso_emit: one wave per row
+// segment of 64 cubes in x, NS3D_ISO_ROWS rows (j) per workgroup, NS3D_ISO_KZ cube planes marched in z per workgroup; the scan
+// works on NS3D_ISO_SCAN_BLOCK segments per workgroup and scans the workgroups' sums with one wave, 64 at a time.
+#define NS3D_ISO_ROWS 4
+#define NS3D_ISO_KZ 8
+#define NS3D_ISO_SCAN_BLOCK 1024
+struct ns3d_iso_geom {
+    int ex, ey;                 // pitches of A and B
+    int lox, loy, loz;          // lowest node of the box
+    int cx, cy, cz;             // cubes per direction
+    int nseg, gy, gz;           // row segments per row; workgroups in y and z (launch: nseg·gy·gz workgroups, x fastest)
+    int ox, oy, oz;             // origin
+};
+struct ns3d_iso_scratch {       // device scratch of one call, carved out of the context's buffer
+    unsigned long long nsegs;   // nseg·cy·cz
+    unsigned nblk;              // scan workgroups
+    unsigned long long *total;  // [0]: the number of triangles
+    unsigned long long *bsum;   // nblk sums, then their exclusive prefix
+    unsigned long long *segbase; // nsegs: exclusive prefix of segcnt
+    unsigned *segcnt;           // nsegs: triangles per (segment, j, k)
+};
+namespace ns3d_iso {
+// count + scan: fills w.segbase and w.total[0]
+template <class T>
+hipError_t count_scan(hipStream_t, const T *A, const ns3d_iso_geom &, double iso, const ns3d_iso_scratch &w);
+// after count_scan on the same input: the first `cap` triangles into tri (and val, from B, when val is not null)
+template <class T>
+hipError_t emit(hipStream_t, const T *A, const T *B, const ns3d_iso_geom &, double iso, const ns3d_iso_scratch &w, double *tri,
+                double *val, long long cap);
+}
+
 #define NS3D_LAUNCHER_DECLS(NS)                                                                              \
     namespace NS {                                                                                           \
     template <class T>                                                                                       \

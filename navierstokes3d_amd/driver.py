@@ -24,7 +24,8 @@ from . import lib as L
 from .halo import ZSlabGrid
 from .slab import SlabPTSolver
 from .stats import RunningStats
-from .vortex import VortexFields, save_bins as _save_vortex_bins
+from . import isosurface as ISO
+from .vortex import NAMES as _VORTEX_NAMES, VortexFields, save_bins as _save_vortex_bins
 from .tracers import Probes, Tracers
 from .params import gpu_params, multi_params
 from .vis import save_frame_gpu, save_frame_multi, save_frame_tracers, save_frame_vortex
@@ -167,7 +168,7 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
-                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None):
+                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -212,7 +213,20 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     of shape (nt, M), NaN for a point outside the box.
     Both are read-only with respect to the flow — every other result keeps its bits — and leave `one_call` in use.  ONE RANK
     only: on more than one rank either keyword raises Ns3dError, because a particle that crosses a seam has to migrate to the
-    neighbouring rank and there is no ns3d_mgpu form of these calls yet."""
+    neighbouring rank and there is no ns3d_mgpu form of these calls yet.
+    isosurface=… (default None: not one extra call, file or attribute): a triangle surface of the final state, after the last
+    step's halo update (ns3d_isosurface, on the device, on every local rank's context; isosurface.extract).  A float q means the
+    Q-criterion at level q, uncoloured; a dict gives `field` (Q, Wx, Wy, Wz, Pr or C), `level` and optionally `color`, a field of
+    the same set interpolated at the vertices.  info.isosurface gets an isosurface.Isosurface in physical coordinates (the cell
+    grid's low corner is (−lx/2, −ly/2, −lz/2)).  Q, Wx, Wy, Wz are computed into scratch when `vortex` is off and extracted over
+    the interior nodes 1 … n−2 of the global grid (their outermost cells are +0.0 by contract, not flow); Pr and C over the whole
+    array.  The ranks of a decomposed grid extract the cubes they own — per decomposed direction the lower node runs from 1 (0 at
+    a physical low end) up to and including n−2 — with origin = coords·(n−2), and the pieces are concatenated in rank order: one
+    rank or a mgpu.MgpuGrid in the one-process form; in the one-process-per-GPU form the keyword raises Ns3dError (a
+    variable-length gather across processes is not provided).  A rank reads its arrays as the step leaves them, halo cells
+    included: :477 does not update C's halo, so next to a seam a surface of C, or coloured by it, is that of the rank's own copy.
+    do_save adds out_iso_%04d.ply per saved frame (same directory
+    and counter as the .bin files).  `one_call` stays in use; read-only: every other result keeps its bits."""
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -227,6 +241,10 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         raise L.Ns3dError("tracers= / probes= run on one rank only (this grid has %d): particles that cross a seam between ranks "
                           "would have to migrate, and ns3d_tracers_advance / ns3d_sample have no ns3d_mgpu form" % P)
     local_ranks = list(getattr(grid, "local_ranks", [grid.me]))
+    iso_spec = _iso_spec(isosurface)
+    if iso_spec is not None and len(local_ranks) != P:
+        raise L.Ns3dError("isosurface= needs every rank in this process (one rank, or a mgpu.MgpuGrid in the one-process form): "
+                          "this process drives %d of %d ranks" % (len(local_ranks), P))
     if hasattr(grid, "contexts"):
         ctxs = list(grid.contexts)                         # contexts of the ns3d_mgpu's ranks (their devices)
     else:
@@ -265,6 +283,13 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     ny_g_all = dims[1] * (ny - 2) + 2
     vort = VortexFields((nx, ny, nz), ctxs, (p.dx, p.dy, p.dz), dtype) if vortex else None
     trc, prb = _observers(tracers, probes, (nx, ny, nz), ctxs[0], p, nt)
+    iso = _IsoObserver(iso_spec, (nx, ny, nz), ctxs, p, dims, coords, grid, vort, dtype) if iso_spec is not None else None
+
+    def iso_frame():
+        surface = iso.extract(fs)
+        if _is_root(grid):
+            os.makedirs("./out_save", exist_ok=True)
+            surface.save_ply("out_save/out_iso_%04d.ply" % iframe)
 
     def tracers_frame(save, vis):
         rec = trc.record()
@@ -294,6 +319,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             vortex_frame(do_save, do_vis)
         if trc is not None:
             tracers_frame(do_save, do_vis)
+        if iso is not None and do_save:
+            iso_frame()
     iframe += 1
     pts = [K.pt_params(f.Pr, q.rho, q.dt, q.dtau, q.damp, q.dx, q.dy, q.dz, L.NS3D_BC_MULTI, q.owns_outlet, 0.0, q.g,
                        q.coords[2] > 0, q.coords[2] < dims[2] - 1) for f, q in zip(fs, ps)]
@@ -357,6 +384,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                 vortex_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
             if trc is not None:
                 tracers_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
+            if iso is not None and do_save and it % nsave == 0:
+                iso_frame()
             iframe += 1
 
     for it in range(1, nt + 1):                                                               # :446
@@ -477,6 +506,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     if vort is not None:
         vort.compute(fs)
         info.vortex = vort.gathered(grid)
+    if iso is not None:
+        info.isosurface = iso.extract(fs, computed=vort is not None)
     if trc is not None:
         info.tracers = trc.record()
     if prb is not None:
@@ -485,6 +516,68 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     info.local_fields = fs
     info.ctx = ctxs[0]
     return out + ((info,) if return_info else ())                                             # :535
+
+
+def _iso_spec(isosurface):
+    """(field, level, color) of the drivers' `isosurface=` keyword, None when it is off"""
+    if isosurface is None:
+        return None
+    if isinstance(isosurface, dict):
+        unknown = set(isosurface) - {"field", "level", "color"}
+        if unknown or "level" not in isosurface:
+            raise L.Ns3dError("isosurface = %r (a dict with field, level and optionally color)" % (isosurface,))
+        field, level, color = isosurface.get("field", "Q"), isosurface["level"], isosurface.get("color")
+    elif isinstance(isosurface, (int, float, np.integer, np.floating)) and not isinstance(isosurface, bool):
+        field, level, color = "Q", isosurface, None
+    else:
+        raise L.Ns3dError("isosurface = %r (a level of the Q-criterion, or a dict with field, level and optionally color)" % (isosurface,))
+    if field not in ISO_FIELDS or (color is not None and color not in ISO_FIELDS):
+        raise L.Ns3dError("isosurface: field = %r, color = %r (each one of %s)" % (field, color, ", ".join(ISO_FIELDS)))
+    if not np.isfinite(float(level)):
+        raise L.Ns3dError("isosurface: level = %r is not finite" % (level,))
+    return field, float(level), color
+
+
+ISO_FIELDS = ("Q", "Wx", "Wy", "Wz", "Pr", "C")
+
+
+class _IsoObserver:
+    """The drivers' `isosurface=` keyword: one isosurface.extract per local rank over the cubes that rank owns, concatenated in rank
+    order.  Q, Wx, Wy, Wz come from the run's VortexFields (`vort`) or from a scratch set of this observer's own."""
+
+    def __init__(self, spec, shape, ctxs, p, dims, coords, grid, vort, dtype):
+        self.field, self.level, self.color = spec
+        self.shape, self.ctxs, self.p, self.dims, self.coords, self.grid = tuple(shape), list(ctxs), p, tuple(dims), list(coords), grid
+        self.derived = [n for n in (self.field, self.color) if n in _VORTEX_NAMES]
+        self.vort = vort
+        if self.derived and vort is None:
+            self.vort = VortexFields(shape, ctxs, (p.dx, p.dy, p.dz), dtype)
+
+    def _array(self, name, l, fs):
+        if name is None:
+            return None
+        return getattr(self.vort.out[l], name) if name in _VORTEX_NAMES else getattr(fs[l], name)
+
+    def extract(self, fs, computed=False):
+        """the surface of the state in `fs` (one namespace of fields per local rank); computed: self.vort holds this state's fields"""
+        n = self.shape
+        if self.derived:
+            if not computed:
+                self.vort.compute(fs)
+            if len(fs) > 1:     # a seam's cubes need the neighbour's values in the halo cells, which ns3d_vortex leaves +0.0
+                self.grid.update_halo(*[[getattr(o, nm) for o in self.vort.out] for nm in dict.fromkeys(self.derived)])
+        pieces = []
+        for l, c in enumerate(self.ctxs):
+            co = self.coords[l]
+            lo = [0 if co[q] == 0 else 1 for q in range(3)]
+            hi = [n[q] - 1 for q in range(3)]
+            if self.derived:    # the global grid's outermost cells are +0.0 by ns3d_vortex's contract, not flow
+                lo = [1, 1, 1]
+                hi = [n[q] - 2 if co[q] == self.dims[q] - 1 else n[q] - 1 for q in range(3)]
+            pieces.append(ISO.extract(c, self._array(self.field, l, fs), self.level, color=self._array(self.color, l, fs), box=lo + hi,
+                                      origin=[co[q] * (n[q] - 2) for q in range(3)], spacings=(self.p.dx, self.p.dy, self.p.dz),
+                                      low_corner=(-self.p.lx / 2, -self.p.ly / 2, -self.p.lz / 2)))
+        return ISO.concat(pieces)
 
 
 def _observers(tracers, probes, shape, ctx, p, nt):
@@ -576,7 +669,7 @@ def _save_mat(path, f, p, step0):
 
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
-          diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None):
+          diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -590,7 +683,9 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     local arrays Wx, Wy, Wz, Q (their boundary entries are 0); do_vis adds 3D_NavierStokes_Wz_%04d.png, …_Q_…, …_long_Wy_…,
     …_long_Q_… (do_save's MAT files are left as the reference writes them).
     tracers / probes: as in run_navierstokes3D, advanced resp. sampled after :142; do_save adds out_save/out_tracers_%04d.bin beside
-    each MAT file (numbered 0, 1, … in the order the MAT files are written), do_vis 3D_NavierStokes_tracers_%04d.png per frame."""
+    each MAT file (numbered 0, 1, … in the order the MAT files are written), do_vis 3D_NavierStokes_tracers_%04d.png per frame.
+    isosurface: as in run_navierstokes3D, of the final state → info.isosurface; do_save adds out_save/out_iso_%04d.ply beside each
+    MAT file (numbered like the tracer dumps)."""
     if device is None:
         device = torch.cuda.current_device()
     _check_stats_options(statistics, stats_every)
@@ -617,6 +712,10 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     iframe = 0
     host = lambda: {n: K.to_numpy(getattr(f, n)) for n in ("Pr", "C", "Vx", "Vy", "Vz")}
     vort = VortexFields((nx, ny, nz), [ctx], (p.dx, p.dy, p.dz), dtype) if vortex else None
+    iso_spec = _iso_spec(isosurface)
+    iso = _IsoObserver(iso_spec, (nx, ny, nz), [ctx], p, (1, 1, 1), [(0, 0, 0)], None, vort, dtype) if iso_spec is not None else None
+    if iso is not None and do_save:
+        iso.extract([f]).save_ply("out_save/out_iso_%04d.ply" % 0)
 
     def vortex_frame():
         vort.compute([f])
@@ -668,6 +767,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
                 _save_mat("out_save/step_%d.mat" % it, f, p, False)
                 if trc is not None:
                     Tracers.save_bins(trc.record(), it // nsave)
+                if iso is not None:
+                    iso.extract([f]).save_ply("out_save/out_iso_%04d.ply" % (it // nsave))
             continue
         if fused:
             if it == nt:            # the stress arrays as the reference leaves them after its last step: same final state
@@ -736,6 +837,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             _save_mat("out_save/step_%d.mat" % it, f, p, False)
             if trc is not None:
                 Tracers.save_bins(trc.record(), it // nsave)
+            if iso is not None:
+                iso.extract([f]).save_ply("out_save/out_iso_%04d.ply" % (it // nsave))
     if fused and faithful and nt > 0:
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()
@@ -745,6 +848,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     if vort is not None:
         vort.compute([f])
         info.vortex = vort.local(0)
+    if iso is not None:
+        info.isosurface = iso.extract([f], computed=vort is not None)
     if trc is not None:
         info.tracers = trc.record()
     if prb is not None:

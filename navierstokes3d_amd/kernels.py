@@ -426,6 +426,35 @@ def tracers_advance(X, state, Vx, Vy, Vz, cx, cy, cz, U=None, ctx=None):
                        *_d(cx, cy, cz), nx, ny, nz)
 
 
+def isosurface(A, level, color=None, box=None, origin=None, tri=None, val=None, cap=0, ctx=None):
+    """ns3d_isosurface: the triangles of the level set A = level by marching tetrahedra (include/ns3d.h has the definition; the same
+    bits in every arithmetic mode), in index space.  A: any column-major array of extents ≥ 2 whose entries are nodes at integer
+    positions; color: a second array of the same shape, interpolated at the vertices into val; box = (lo_x, lo_y, lo_z, hi_x, hi_y,
+    hi_z), a closed node range (None: the whole array); origin: three ints added to the node indices.  tri (≥ 9·cap float64) and val
+    (≥ 3·cap float64) receive the first min(n, cap) triangles; cap = 0 without tri is the count-only form.  Returns n, the number
+    of triangles the surface has; blocks for that read-back."""
+    ex, ey, ez = A.shape
+    cap = int(cap)
+    if isinstance(color, torch.Tensor) and (color.dtype != A.dtype or color.device != A.device):
+        raise L.Ns3dError("color is %s on %s, A is %s on %s" % (color.dtype, color.device, A.dtype, A.device))
+    ptrs = []
+    for name, t, per in (("tri", tri, 9), ("val", val, 3)):
+        if t is None:
+            ptrs.append(None)
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.device != A.device:
+            raise L.Ns3dError("%s must be a contiguous float64 CUDA/HIP tensor on A's device" % name)
+        if t.numel() < per * cap:
+            raise L.Ns3dError("%s holds %d elements, cap = %d needs %d" % (name, t.numel(), cap, per * cap))
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    b = None if box is None else (C.c_int * 6)(*(int(q) for q in box))
+    o = None if origin is None else (C.c_int * 3)(*(int(q) for q in origin))
+    n = C.c_longlong(-1)
+    _ctx(ctx, A).call("isosurface", A, _chk(A, None, "A"), None if color is None else _chk(color, (ex, ey, ez), "color"), ex, ey, ez, b, o,
+                      C.c_double(float(level)), ptrs[0], ptrs[1], C.c_longlong(cap), C.byref(n))
+    return n.value
+
+
 def _untyped(ctx, ref, name, *args):
     c = _ctx(ctx, ref)
     if not getattr(c, "_pinned", False) and torch.cuda.current_stream(c.device).cuda_stream != c._stream:

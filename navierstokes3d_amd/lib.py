@@ -105,6 +105,7 @@ DERIVED_SIGNATURES = {
     "vortex": [_P] * 7 + [_D] * 3 + [_I] * 3,
     "sample": [_P] * 3 + [_L, _P] + [_I] * 6,
     "tracers_advance": [_P] * 3 + [_L] + [_P] * 3 + [_D] * 3 + [_I] * 3,
+    "isosurface": [_P] * 2 + [_I] * 3 + [C.POINTER(_I)] * 2 + [_D] + [_P] * 2 + [C.c_longlong, C.POINTER(C.c_longlong)],
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
