@@ -22,7 +22,31 @@
  *  - Every function returns 0 (NS3D_OK) or a non-zero status; the message is available from
  *    ns3d_last_error().  Nothing throws or aborts across the boundary.
  *  - Like `@parallel`, every call is synchronous to the caller unless the context was created with
- *    NS3D_ASYNC (then calls only enqueue on the context's stream; use ns3d_sync()).
+ *    NS3D_ASYNC (then calls only enqueue on the context's stream; use ns3d_sync()).  The same holds on whichever stream
+ *    the context launches on (ns3d_set_stream, ns3d_use_own_stream, ns3d_reserve_cus): inputs are read and outputs
+ *    written in that stream's order, and ns3d_sync() waits for everything a call started.
+ *    These calls wait for the stream even on an NS3D_ASYNC context (tests/test_gpu_stream_order.py takes each entry point
+ *    on three non-blocking streams, with inputs that arrive late and readers that follow early, and sorts them the same way):
+ *        call                                   waits for                          device outputs complete on return?
+ *        ns3d_max_abs, ns3d_residual_max        the value it returns               (none)
+ *        ns3d_diagnostics                       the record it returns              (none)
+ *        ns3d_selftest_exact_div                the count it returns               (none)
+ *        ns3d_isosurface                        the triangle count                 no: tri / val are enqueued behind the count
+ *        ns3d_pt_solve                          every residual check               no: the copies into Pr / dPrdtau are enqueued
+ *        ns3d_time_step                         as ns3d_pt_solve (pressure 0);     no: the rest of the step is enqueued behind the solve;
+ *                                               the whole step (pressure 1)        yes with pressure 1
+ *        ns3d_pt_iterate                        the block, WHEN it runs as the     no: the copies into Pr / dPrdtau are enqueued
+ *                                               one k_pt_persist launch (small
+ *                                               grids or persist mode 1)
+ *        ns3d_plan_pt, and the first            the timed launches of the tile     as the call otherwise
+ *        pt_iterate / pt_solve / pt_sweep2      shapes (grids of 1.5 M cells up,
+ *        of a grid                              autotune on)
+ *        ns3d_poisson_direct                    the stream, WHEN it builds or      no
+ *                                               replaces its plan (a new grid)
+ *        any call that grows a scratch buffer   the stream, before the old         as the call otherwise
+ *        of the context (ping-pong, monitor,    buffer is freed
+ *        isosurface) and ns3d_reserve_cus
+ *    Everything else only enqueues.
  *  - One host thread per context (as in the reference: one thread per rank); contexts are not
  *    thread-safe.
  *  - Arithmetic modes: NS3D_STRICT reproduces the reference's operation order with correctly rounded division

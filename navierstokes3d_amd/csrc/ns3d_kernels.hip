@@ -3733,7 +3733,9 @@ static hipError_t persist_scratch(ns3d_persist_state *st, hipStream_t s, size_t 
         if (st->H) { if ((e = hipEventSynchronize(st->ev)) != hipSuccess) return e; (void)hipFree(st->H); st->H = nullptr; st->bytes = 0; }
         const size_t red_bytes = (2 * (size_t)NS3D_PERSIST_MAXCHK + 8) * sizeof(unsigned long long);
         if ((e = hipMalloc(&st->H, bytes + 64 + red_bytes)) != hipSuccess) return e;
-        if ((e = hipMemset(st->H, 0, bytes + 64 + red_bytes)) != hipSuccess) return e;
+        // on the launch's own stream: hipMemset runs on the null stream, which a non-blocking stream does not wait for — the fill then
+        // lands in the middle of the launch, wipes hand-over pairs (expired waits) or the staged PersistCheck (a store through res = 0)
+        if ((e = hipMemsetAsync(st->H, 0, bytes + 64 + red_bytes, s)) != hipSuccess) return e;
         st->err = (unsigned *)((char *)st->H + bytes);
         st->red = (unsigned long long *)((char *)st->H + bytes + 64);
         st->bytes = bytes;

@@ -95,6 +95,14 @@ class Context:
         self._stream = s.cuda_stream
         L.check(self.lib.ns3d_set_stream(self.handle, C.c_void_p(s.cuda_stream)))
 
+    def use_own_stream(self):
+        """Back to the stream the context was created with (ns3d_use_own_stream: non-blocking, the context's own) and stay on it
+        whatever PyTorch's current stream becomes.  Returns it as a torch stream, like reserve_cus."""
+        L.check(self.lib.ns3d_use_own_stream(self.handle))
+        self._ext = torch.cuda.ExternalStream(int(self.lib.ns3d_get_stream(self.handle)), device=self.device)
+        self._pinned, self._stream = True, self._ext.cuda_stream
+        return self._ext
+
     def sync(self):
         L.check(self.lib.ns3d_sync(self.handle))
 

@@ -15,6 +15,18 @@ from . import kernels as K
 from . import lib as L
 
 
+def _pinned(ctx):
+    """the context launches on a stream of its own, whatever PyTorch's current stream is (use_torch_stream(pin=True), use_own_stream,
+    reserve_cus): nothing orders PyTorch's tensor work with its kernels"""
+    return ctx is not None and getattr(ctx, "_pinned", False)
+
+
+def _after_fill(ctx):
+    """a pinned context: PyTorch's fill of a fresh array (on ITS stream) comes first, as in stats.py"""
+    if _pinned(ctx):
+        torch.cuda.current_stream(ctx.device).synchronize()
+
+
 def _points(xyz):
     a = np.asarray(xyz, dtype=np.float64)
     if a.ndim != 2 or a.shape[1] != 3:
@@ -41,6 +53,7 @@ class Tracers:
         self.X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(self.device)
         self.state = torch.from_numpy(np.ascontiguousarray(state, dtype=np.uint8)).to(self.device)
         self.U = torch.full_like(self.X, float("nan")) if self.keep_velocity else None
+        _after_fill(self.ctx)
 
     @property
     def n(self):
@@ -74,6 +87,8 @@ class Tracers:
         """Put the physical points xyz (M,3) into DEAD slots only, lowest slots first; returns how many were placed
         (min(M, number of dead slots)).  Live particles and their order are untouched."""
         X = self.to_index(xyz)
+        if _pinned(self.ctx):
+            self.ctx.sync()             # an advance still queued on the context's own stream writes state and X
         dead = torch.nonzero(self.state == 0).flatten()
         k = min(int(dead.numel()), X.shape[1])
         if k:
@@ -82,6 +97,7 @@ class Tracers:
             self.state[slots] = torch.from_numpy(self._inside(X[:, :k]).astype(np.uint8)).to(self.device)
             if self.U is not None:
                 self.U[:, slots] = float("nan")
+            _after_fill(self.ctx)
         return k
 
     def advance(self, f, dt):
@@ -171,6 +187,7 @@ class Probes:
         self.X = torch.from_numpy(t.to_index(xyz)).to(t.device)
         self.m = int(self.X.shape[1])
         self.series = torch.full((4, max(int(nt), 0), self.m), float("nan"), dtype=torch.float64, device=t.device)
+        _after_fill(ctx)
         self.steps = 0
 
     def record(self, f):
