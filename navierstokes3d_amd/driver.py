@@ -11,6 +11,8 @@ limits; no axes — Plots.jl itself is out of scope).
 The time loops below follow the reference line by line (cited); with `fused=True` the inner pseudo-transient
 loop {update_dPrdτ!; update_Pr!; set_bc_Pr!}×n is replaced by ns3d_pt_solve / overlapped ns3d_pt_sweep calls
 that produce the same iterates (the redundant halo updates multi.jl:460,462 are dropped).
+What is not the reference's is marked: `monitor` (diagnostics=True: three positions inside the step) and `obs` (observers.py:
+statistics, vortex, tracers, probes, isosurface — at the end of a step, at a frame, after the loop).
 """
 import math
 import os
@@ -22,13 +24,10 @@ import torch
 from . import kernels as K
 from . import lib as L
 from .halo import ZSlabGrid
+from .observers import Observers, check_options
 from .slab import SlabPTSolver
-from .stats import RunningStats
-from . import isosurface as ISO
-from .vortex import NAMES as _VORTEX_NAMES, VortexFields, save_bins as _save_vortex_bins
-from .tracers import Probes, Tracers
 from .params import gpu_params, multi_params
-from .vis import save_frame_gpu, save_frame_multi, save_frame_tracers, save_frame_vortex
+from .vis import save_frame_gpu, save_frame_multi
 
 
 def _alloc(nx, ny, nz, dtype, device):
@@ -51,25 +50,14 @@ def save_array(Aname, A):
         fh.write(np.asfortranarray(A).tobytes(order="F"))
 
 
-def _inner(t):
-    """Array(A)[2:end-1,2:end-1,2:end-1] (multi.jl:399)"""
-    return K.to_numpy(t)[1:-1, 1:-1, 1:-1]
-
-
 def _gather_all(grid, fs):
-    """multi.jl:399-403 / :528-532 for the local ranks' fields `fs`"""
-    if hasattr(grid, "gather_fields"):                     # C-ABI grid: halo-stripping and transport inside libns3d
-        return tuple(grid.gather_fields([getattr(f, n) for f in fs]) for n in ("C", "Pr", "Vx", "Vy", "Vz"))
-    return tuple(grid.gather(_inner(getattr(fs[0], n))) for n in ("C", "Pr", "Vx", "Vy", "Vz"))
-
-
-def _is_root(grid):
-    return grid.is_root() if hasattr(grid, "is_root") else grid.me == 0
+    """multi.jl:399-403 / :528-532 for the local ranks' fields `fs` (halo cells stripped, :399)"""
+    return tuple(grid.gather_fields([getattr(f, n) for f in fs]) for n in ("C", "Pr", "Vx", "Vy", "Vz"))
 
 
 def _save_frame(grid, fields_v, iframe):
     """multi.jl:404-413 / :515-522 — rank 0 writes Float32 raw dumps of the gathered arrays."""
-    if not _is_root(grid):
+    if not grid.is_root():
         return
     os.makedirs("./out_save", exist_ok=True)
     for name, A in zip(("C", "Pr", "Vx", "Vy", "Vz"), fields_v):
@@ -88,6 +76,43 @@ def _diag_step_record(full, mom_predict, mom_correct, p):
     rec.mom_predict, rec.mom_correct = tuple(mom_predict), tuple(mom_correct)
     rec.force = tuple(p.rho * p.dx * p.dy * p.dz / p.dt * (mom_predict[q] + mom_correct[q]) for q in range(3))
     return rec
+
+
+def _monitor(grid, ctxs, fs, cyls, p):
+    """diagnostics=True: monitor(full) → the flow monitor's record of the GLOBAL arrays as they are at the call (ns3d_diagnostics on one
+    rank, through the grid on an ns3d_mgpu); full=False: velocities only (the masked momentum).  `cyls`: set_cylinder!'s scalars per
+    local rank."""
+    dps = [K.diag_params(p.nx, p.ny, p.nz, p.dx, p.dy, p.dz, p.rho, cylinder=cyl) for cyl in cyls]   # seam flags: set by the grid
+    col = lambda n: [getattr(f, n) for f in fs]
+
+    def monitor(full):
+        pr, cf = (col("Pr"), col("C")) if full else (None, None)
+        if grid.mg is not None:
+            return grid.diagnostics(col("Vx"), col("Vy"), col("Vz"), pr, cf, dps)[0]
+        return K.diagnostics(fs[0].Vx, fs[0].Vy, fs[0].Vz, pr and pr[0], cf and cf[0], dps[0], ctx=ctxs[0])
+    return monitor
+
+
+def _step_params(script, p, niter, faithful, pressure):
+    """lib.StepParams of ns3d_time_step on one rank.  script = lib.NS3D_BC_MULTI: p from multi_params, with the cylinder's global
+    origin, the inlet and outlet flags and vin; lib.NS3D_BC_GPU: p from gpu_params, whose script has none of them."""
+    multi = script == L.NS3D_BC_MULTI
+    xco_g, yco_g, zco_g = (p.xco_g, p.yco_g, p.zco_g) if multi else (0.0, 0.0, 0.0)
+    return L.StepParams(script=script, nx=p.nx, ny=p.ny, nz=p.nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau, damp=p.damp,
+                        dx=p.dx, dy=p.dy, dz=p.dz, eps=p.eps, niter=niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc,
+                        a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy, sinb=p.sinb, cosb=p.cosb, xco_g=xco_g, yco_g=yco_g, zco_g=zco_g,
+                        lx=p.lx, ly=p.ly, lz=p.lz, owns_inlet=int(multi and bool(p.owns_inlet)),
+                        owns_outlet=int(multi and bool(p.owns_outlet)), vin=p.vin if multi else 0.0, faithful=int(bool(faithful)),
+                        pressure=1 if pressure == "direct" else 0, write_stress=0)
+
+
+def _print_step(it, errs, nchk, rec=None):
+    """the reference's lines of a step (multi.jl:456,468 / gpu.jl:125,134), then the monitor's (diagnostics=True)"""
+    print("#it = %d" % it)
+    for q, e in enumerate(errs):
+        print("  #iter = %d, err = %1.3e" % ((q + 1) * nchk, e))
+    if rec is not None:
+        print(_diag_line(rec))
 
 
 def _check_wide_precondition(it, courant):
@@ -126,7 +151,7 @@ def pt_loop_reference(ctxs, grid, fs, ps, niter, do_print=False):
                 loc.append(K.max_abs(f.Rp, ctx=c))
             err = grid.max_g(loc if len(loc) > 1 else loc[0]) * (p.ly * p.ly) / p.psc                      # :466
             errs.append(err)
-            if _is_root(grid) and do_print:
+            if grid.is_root() and do_print:
                 print("  #iter = %d, err = %1.3e" % (it, err))                                            # :468
             if err < p.eps or not math.isfinite(err):                                                     # :469
                 done = it
@@ -231,29 +256,18 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
         device = torch.cuda.current_device()
-    _check_stats_options(statistics, stats_every)
     shape = dict(shape or {})
     if grid is None:
         p0 = multi_params(nx, **shape)
         grid = ZSlabGrid(p0.nx, p0.ny, p0.nz)                                                  # :325
-    P = grid.P
-    if P > 1 and (tracers is not None or probes is not None):
-        raise L.Ns3dError("tracers= / probes= run on one rank only (this grid has %d): particles that cross a seam between ranks "
-                          "would have to migrate, and ns3d_tracers_advance / ns3d_sample have no ns3d_mgpu form" % P)
-    local_ranks = list(getattr(grid, "local_ranks", [grid.me]))
-    iso_spec = _iso_spec(isosurface)
-    if iso_spec is not None and len(local_ranks) != P:
-        raise L.Ns3dError("isosurface= needs every rank in this process (one rank, or a mgpu.MgpuGrid in the one-process form): "
-                          "this process drives %d of %d ranks" % (len(local_ranks), P))
-    if hasattr(grid, "contexts"):
-        ctxs = list(grid.contexts)                         # contexts of the ns3d_mgpu's ranks (their devices)
-    else:
-        ctxs = [K.Context(device, mode, async_=True)]
-    dims = tuple(getattr(grid, "dims", (1, 1, P)))
-    coords = list(getattr(grid, "local_coords", [(0, 0, me) for me in local_ranks]))
-    ps = [multi_params(nx, dims=dims, coords=c3, **shape) for c3 in coords]
+    watch = dict(statistics=statistics, stats_every=stats_every, vortex=vortex, tracers=tracers, probes=probes, isosurface=isosurface)
+    check_options(grid, **watch)
+    P, dims, mg, root = grid.P, tuple(grid.dims), grid.mg, grid.is_root()
+    # the contexts of the ns3d_mgpu's ranks (their devices), or this rank's own
+    ctxs = list(grid.contexts) if grid.contexts is not None else [K.Context(device, mode, async_=True)]
+    ps = [multi_params(nx, dims=dims, coords=c3, **shape) for c3 in grid.local_coords]
     p = ps[0]
-    if fused and (dims[0] > 1 or dims[1] > 1) and getattr(grid, "mg", None) is None:
+    if fused and (dims[0] > 1 or dims[1] > 1) and mg is None:
         raise L.Ns3dError("a topology decomposed in x or y (dims = %r) needs the C-ABI grid (mgpu.MgpuGrid) or fused=False" % (dims,))
     # multi.jl:179 `xve_g == lx/2`: the outlet rule as the ranks on the last x coordinate evaluate it (the library applies it
     # on those ranks only; every z-slab rank is one of them)
@@ -269,7 +283,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         # :370 Pr = -(z_g-dz/2)*ρ*g (+0+0): identically 0 because g = 1/Fr² = 0 (:316); evaluated for fidelity
         zg = np.array([(me * (nz - 2) + iz) * q.dz for iz in range(nz)])
         f.Pr[:, :, :] = torch.from_numpy(-(zg - q.dz / 2) * q.rho * q.g + 0.0).to(f.Pr.device, dtype)[None, None, :]
-    if any(getattr(c, "_pinned", False) for c in ctxs):    # ranks on streams of their own: the torch writes above come first
+    if any(c._pinned for c in ctxs):                       # ranks on streams of their own: the torch writes above come first
         torch.cuda.synchronize()
     grid.update_halo(col("Pr"))                                                               # :371
     cyls = [(q.a2, q.b2, q.ox, q.oy, q.sinb, q.cosb, q.xco_g, q.yco_g, q.zco_g, q.lx, q.ly, q.lz, q.dx, q.dy, q.dz)
@@ -281,47 +295,22 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     iframe = 0
     nz_g_all = dims[2] * (nz - 2) + 2
     ny_g_all = dims[1] * (ny - 2) + 2
-    vort = VortexFields((nx, ny, nz), ctxs, (p.dx, p.dy, p.dz), dtype) if vortex else None
-    trc, prb = _observers(tracers, probes, (nx, ny, nz), ctxs[0], p, nt)
-    iso = _IsoObserver(iso_spec, (nx, ny, nz), ctxs, p, dims, coords, grid, vort, dtype) if iso_spec is not None else None
+    obs = Observers(grid, ctxs, p, nt, dtype, gathered=True, **watch)
 
-    def iso_frame():
-        surface = iso.extract(fs)
-        if _is_root(grid):
-            os.makedirs("./out_save", exist_ok=True)
-            surface.save_ply("out_save/out_iso_%04d.ply" % iframe)
-
-    def tracers_frame(save, vis):
-        rec = trc.record()
-        if save:
-            Tracers.save_bins(rec, iframe)
-        if vis:
-            save_frame_tracers(rec, p.lx, p.ly, iframe)
-
-    def vortex_frame(save, vis):
-        """the vortex fields of the state a frame shows: computed, gathered, written by the root"""
-        vort.compute(fs)
-        rec = vort.gathered(grid)
-        if _is_root(grid):
-            if save:
-                _save_vortex_bins(rec, iframe)
-            if vis:
-                save_frame_vortex(rec, ny_g_all, nz_g_all, iframe)
-
-    if do_save or do_vis:                                                                     # :399-403
+    def frame(save, vis):                           # :399-443 before the loop, :479-525 in it (one frame counter)
+        nonlocal iframe
+        if not (save or vis):
+            return
         sync()
-        gathered = _gather_all(grid, fs)
-        if do_save:                                                                           # :404-413
+        gathered = _gather_all(grid, fs)                                                      # :399-403
+        if save:                                                                              # :404-413 / :515-522
             _save_frame(grid, gathered, iframe)
-        if do_vis and _is_root(grid):                                                         # :416-443
+        if vis and root:                                                                      # :416-443 / :486-513
             save_frame_multi(gathered, ny_g_all, nz_g_all, iframe)
-        if vort is not None:
-            vortex_frame(do_save, do_vis)
-        if trc is not None:
-            tracers_frame(do_save, do_vis)
-        if iso is not None and do_save:
-            iso_frame()
-    iframe += 1
+        obs.frame(fs, iframe if save else None, iframe if vis else None)
+        iframe += 1
+
+    frame(do_save, do_vis)
     pts = [K.pt_params(f.Pr, q.rho, q.dt, q.dtau, q.damp, q.dx, q.dy, q.dz, L.NS3D_BC_MULTI, q.owns_outlet, 0.0, q.g,
                        q.coords[2] > 0, q.coords[2] < dims[2] - 1) for f, q in zip(fs, ps)]
     pt_all = K.pt_params(fs[0].Pr, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, L.NS3D_BC_MULTI, outlet_rule, 0.0, p.g,
@@ -329,7 +318,6 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     if not temporal:
         for c in ctxs:
             c.set_pt2_variant(-1)
-    mg = getattr(grid, "mg", None)
     if mg is not None:
         mg.set_temporal(4 if (temporal and nz >= 4) else 1)
     slab = None
@@ -343,17 +331,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         if P > 1 and mg is None:
             raise L.Ns3dError("diagnostics on %d ranks needs the C-ABI grid (mgpu.MgpuGrid)" % P)
         info.diag = []
-        dps = [K.diag_params(nx, ny, nz, p.dx, p.dy, p.dz, p.rho, cylinder=cyl) for cyl in cyls]   # seam flags: set by the grid
-
-        def monitor(full):
-            """the monitor of the global arrays; full=False: velocities only (the masked momentum)"""
-            pr, cf = (col("Pr"), col("C")) if full else (None, None)
-            if mg is not None:
-                return grid.diagnostics(col("Vx"), col("Vy"), col("Vz"), pr, cf, dps)[0]
-            return K.diagnostics(fs[0].Vx, fs[0].Vy, fs[0].Vz, pr and pr[0], cf and cf[0], dps[0], ctx=ctxs[0])
-    running = RunningStats((nx, ny, nz), ctxs) if statistics is not None else None
+        monitor = _monitor(grid, ctxs, fs, cyls, p)
+    obs.start()
     nsave = nvis = 10                                                                         # :330,332
-    root = _is_root(grid)
     # :450's halo update of the normal stresses may only go with the stress arrays where the interior planes two ranks both compute
     # are identical.  backtrack! clamps to the LOCAL array and rounds iz − δ rank by rank (DESIGN §6), so with the fixed third branch
     # (faithful=False: Vz IS advected) on several ranks and without the wide halo the two copies of a seam's Vz plane can differ —
@@ -362,259 +342,106 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     # one rank, fused: the whole step :449-477 is ONE library call (ns3d_time_step: the same entry points, enqueued from C) — a step
     # of the 255×153×153 case with the direct pressure solve is otherwise mostly this loop's ≈40 calls
     step_params = None
-    if fused and one_call and P == 1 and getattr(grid, "mg", None) is None and not diagnostics:
-        q = ps[0]
-        step_params = L.StepParams(script=L.NS3D_BC_MULTI, nx=nx, ny=ny, nz=nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau,
-                                   damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz, eps=p.eps, niter=niter, nchk=p.nchk, err_mul=p.ly * p.ly,
-                                   err_div=p.psc, a2=q.a2, b2=q.b2, ox=q.ox, oy=q.oy, sinb=q.sinb, cosb=q.cosb, xco_g=q.xco_g,
-                                   yco_g=q.yco_g, zco_g=q.zco_g, lx=q.lx, ly=q.ly, lz=q.lz, owns_inlet=int(bool(q.owns_inlet)),
-                                   owns_outlet=int(bool(q.owns_outlet)), vin=p.vin, faithful=int(bool(faithful)),
-                                   pressure=1 if pressure == "direct" else 0, write_stress=0)
-
-    def frames(it):                                                                           # :479-525 (one frame counter)
-        nonlocal iframe
-        if (do_vis and it % nvis == 0) or (do_save and it % nsave == 0):
-            sync()
-            gathered = _gather_all(grid, fs)
-            if do_vis and it % nvis == 0 and root:                                            # :486-513
-                save_frame_multi(gathered, ny_g_all, nz_g_all, iframe)
-            if do_save and it % nsave == 0:                                                   # :515-522
-                _save_frame(grid, gathered, iframe)
-            if vort is not None:
-                vortex_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
-            if trc is not None:
-                tracers_frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
-            if iso is not None and do_save and it % nsave == 0:
-                iso_frame()
-            iframe += 1
-
+    if fused and one_call and P == 1 and mg is None and not diagnostics:
+        step_params = _step_params(L.NS3D_BC_MULTI, p, niter, faithful, pressure)
     for it in range(1, nt + 1):                                                               # :446
-        if step_params is not None:
+        if step_params is not None:                             # :449-477 (ns3d_time_step swaps the names in fs[0] like the swaps below)
             step_params.write_stress = 1 if it == nt else 0     # the stress arrays as the reference leaves them after its last step
             done, errs = K.time_step(fs[0], step_params, ctx=ctxs[0])
-            if root and do_print:
-                print("#it = %d" % it)                                                        # :456
-                for q_, e in enumerate(errs):
-                    print("  #iter = %d, err = %1.3e" % ((q_ + 1) * p.nchk, e))
-            info.iters.append(done); info.errs.append(errs)
-            if running is not None and _stats_due(it, statistics, stats_every):
-                running.sample(fs)                          # ns3d_time_step has swapped the names: fs holds the new fields
-            _observe(trc, prb, fs[0], p.dt)
-            frames(it)
-            continue
-        if fuse_predictor:
-            # :449-451 in one pass (ns3d_predict_fused): the stresses evaluated on the fly, the predicted fields written into the
-            # *_o buffers (free until :475), the names swapped.  :450's halo update of τxx, τyy, τzz moves values every rank has
-            # already computed itself — the velocities it computes them from are consistent across ranks after :477 / :373 —
-            # and is dropped with the arrays (the multi-rank driver tests compare with the oracle, which performs it)
-            if it == nt:        # the stress arrays as the reference leaves them after its last step: same final state
+        else:
+            if fuse_predictor:
+                # :449-451 in one pass (ns3d_predict_fused): the stresses evaluated on the fly, the predicted fields written into the
+                # *_o buffers (free until :475), the names swapped.  :450's halo update of τxx, τyy, τzz moves values every rank has
+                # already computed itself — the velocities it computes them from are consistent across ranks after :477 / :373 —
+                # and is dropped with the arrays (the multi-rank driver tests compare with the oracle, which performs it)
+                if it == nt:        # the stress arrays as the reference leaves them after its last step: same final state
+                    for f, c in zip(fs, ctxs):
+                        K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=c)
+                    grid.update_halo(col("txx"), col("tyy"), col("tzz"))
                 for f, c in zip(fs, ctxs):
-                    K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=c)
-                grid.update_halo(col("txx"), col("tyy"), col("tzz"))
+                    _predict_swap(f, p, c)
+            else:
+                for f, c in zip(fs, ctxs):
+                    K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=c)  # :449
+                grid.update_halo(col("txx"), col("tyy"), col("tzz"))                          # :450
+                for f, c in zip(fs, ctxs):
+                    K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
+                                ctx=c)                                                        # :451
+            if monitor:
+                mom_predict = monitor(False).mom
+            for f, c, cyl in zip(fs, ctxs, cyls):
+                K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                            # :452
+            grid.update_halo(col("C"), col("Vx"), col("Vy"), col("Vz"))                       # :453
             for f, c in zip(fs, ctxs):
-                _predict_swap(f, p, c)
-        else:
+                K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=c)              # :454
+            grid.update_halo(col("divV"))                                                     # :455
+            if pressure == "direct" and P > 1:                                                # (:456, :468 print after the step)
+                if mg is None or not (dims[0] == 1 and dims[1] == 1):
+                    raise L.Ns3dError("pressure=\"direct\" on %d ranks needs z-slab ranks on the C-ABI grid (mgpu.MgpuGrid); this grid "
+                                      "is %s with dims = %r" % (P, type(grid).__name__, dims))
+                mg.poisson_direct(col("Pr"), col("dPrdtau"), col("divV"), pt_all)      # ns3d_poisson_direct_slab
+                loc = [K.residual_max(f.Pr, f.divV, q, ctx=c) for f, q, c in zip(fs, pts, ctxs)]
+                done, errs = 0, [grid.max_g(loc if len(loc) > 1 else loc[0]) * (p.ly * p.ly) / p.psc]
+            elif pressure == "direct":
+                K.poisson_direct(fs[0].Pr, fs[0].dPrdtau, fs[0].divV, pts[0], ctx=ctxs[0])
+                done, errs = 0, [K.residual_max(fs[0].Pr, fs[0].divV, pts[0], ctx=ctxs[0]) * (p.ly * p.ly) / p.psc]
+            elif not fused:                                                                   # :458-471
+                done, errs = pt_loop_reference(ctxs, grid, fs, ps, niter)
+            elif P == 1:
+                done, errs = K.pt_solve(fs[0].Pr, fs[0].dPrdtau, fs[0].divV, pts[0], p.eps, niter, p.nchk, p.ly * p.ly, p.psc,
+                                        ctx=ctxs[0])
+            elif mg is not None:                                    # the whole loop inside libns3d (ns3d_pt_solve_slab)
+                done, errs = mg.pt_solve_slab(col("Pr"), col("dPrdtau"), col("divV"), pt_all, p.eps, niter, p.nchk,
+                                              p.ly * p.ly, p.psc)
+            elif slab is not None:                                  # z-slab rank over torch.distributed, deep ghosts
+                slab.load(fs[0].Pr, fs[0].dPrdtau, fs[0].divV)
+                done, errs = slab.solve(p.eps, niter, p.nchk, p.ly * p.ly, p.psc)
+                slab.store(fs[0].Pr, fs[0].dPrdtau)
+            else:
+                done, errs = pt_loop_fused_slab(ctxs[0], grid, fs[0], p, pts[0], niter, scratch=scratch)
             for f, c in zip(fs, ctxs):
-                K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=c)  # :449
-            grid.update_halo(col("txx"), col("tyy"), col("tzz"))                              # :450
+                K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=c)     # :472
+            if monitor:
+                mom_correct = monitor(False).mom
+            for f, c, cyl, q in zip(fs, ctxs, cyls, ps):
+                K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                            # :473
+                K.set_bc_Vel_multi(f.Vx, f.Vy, f.Vz, q.owns_inlet, p.vin, ctx=c)              # :474 → :157-166
+            grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                 # :167
+            if monitor:
+                info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
+                if wide_advect_halo and P > 1:
+                    _check_wide_precondition(it, info.diag[-1].courant)
+            if wide_advect_halo and P > 1:                                                    # :475-477, decomposition-independent
+                if mg is None or not (dims[0] == 1 and dims[1] == 1):
+                    raise L.Ns3dError("wide_advect_halo needs z-slab ranks on the C-ABI grid (mgpu.MgpuGrid)")
+                mg.advect_wide(col("Vx"), col("Vx_o"), col("Vy"), col("Vy_o"), col("Vz"), col("Vz_o"), col("C"), col("C_o"),
+                               p.dt, p.dx, p.dy, p.dz, faithful)
             for f, c in zip(fs, ctxs):
-                K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
-                            ctx=c)                                                            # :451
-        if monitor:
-            mom_predict = monitor(False).mom
-        for f, c, cyl in zip(fs, ctxs, cyls):
-            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                                # :452
-        grid.update_halo(col("C"), col("Vx"), col("Vy"), col("Vz"))                           # :453
-        for f, c in zip(fs, ctxs):
-            K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=c)                  # :454
-        grid.update_halo(col("divV"))                                                         # :455
-        if root and do_print:
-            print("#it = %d" % it)                                                            # :456
-        show = (lambda i, e: print("  #iter = %d, err = %1.3e" % (i, e))) if (root and do_print) else None
-        if pressure == "direct" and P > 1:
-            if mg is None or not (dims[0] == 1 and dims[1] == 1):
-                raise L.Ns3dError("pressure=\"direct\" on %d ranks needs z-slab ranks on the C-ABI grid (mgpu.MgpuGrid); this grid "
-                                  "is %s with dims = %r" % (P, type(grid).__name__, dims))
-            mg.poisson_direct(col("Pr"), col("dPrdtau"), col("divV"), pt_all)      # ns3d_poisson_direct_slab
-            loc = [K.residual_max(f.Pr, f.divV, q, ctx=c) for f, q, c in zip(fs, pts, ctxs)]
-            done, errs = 0, [grid.max_g(loc if len(loc) > 1 else loc[0]) * (p.ly * p.ly) / p.psc]
-        elif pressure == "direct":
-            K.poisson_direct(fs[0].Pr, fs[0].dPrdtau, fs[0].divV, pts[0], ctx=ctxs[0])
-            done, errs = 0, [K.residual_max(fs[0].Pr, fs[0].divV, pts[0], ctx=ctxs[0]) * (p.ly * p.ly) / p.psc]
-        elif not fused:                                                                       # :458-471
-            done, errs = pt_loop_reference(ctxs, grid, fs, ps, niter, do_print)
-        elif P == 1:
-            done, errs = K.pt_solve(fs[0].Pr, fs[0].dPrdtau, fs[0].divV, pts[0], p.eps, niter, p.nchk, p.ly * p.ly, p.psc,
-                                    ctx=ctxs[0])
-        elif mg is not None:                                    # the whole loop inside libns3d (ns3d_pt_solve_slab)
-            done, errs = mg.pt_solve_slab(col("Pr"), col("dPrdtau"), col("divV"), pt_all, p.eps, niter, p.nchk,
-                                          p.ly * p.ly, p.psc)
-        elif slab is not None:                                  # z-slab rank over torch.distributed, deep ghosts
-            slab.load(fs[0].Pr, fs[0].dPrdtau, fs[0].divV)
-            done, errs = slab.solve(p.eps, niter, p.nchk, p.ly * p.ly, p.psc, show)
-            slab.store(fs[0].Pr, fs[0].dPrdtau)
-            show = None
-        else:
-            done, errs = pt_loop_fused_slab(ctxs[0], grid, fs[0], p, pts[0], niter, do_print, scratch)
-            show = None
-        if show is not None and fused:
-            for q, e in enumerate(errs):
-                show((q + 1) * p.nchk, e)
+                if wide_advect_halo and P > 1:
+                    break
+                if fused:       # :475-476 in one pass (ns3d_copy_advect): complete new fields into the *_o buffers, then the roles swap
+                    _copy_advect_swap(f, p, faithful, c)
+                    continue
+                K.copy(f.Vx_o, f.Vx, ctx=c); K.copy(f.Vy_o, f.Vy, ctx=c)                      # :475
+                K.copy(f.Vz_o, f.Vz, ctx=c); K.copy(f.C_o, f.C, ctx=c)
+                K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=c)  # :476
+            if not (wide_advect_halo and P > 1):
+                grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                             # :477 (not C)
         info.iters.append(done); info.errs.append(errs)
-        for f, c in zip(fs, ctxs):
-            K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=c)          # :472
-        if monitor:
-            mom_correct = monitor(False).mom
-        for f, c, cyl, q in zip(fs, ctxs, cyls, ps):
-            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                                # :473
-            K.set_bc_Vel_multi(f.Vx, f.Vy, f.Vz, q.owns_inlet, p.vin, ctx=c)                   # :474 → :157-166
-        grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                     # :167
-        if monitor:
-            rec = _diag_step_record(monitor(True), mom_predict, mom_correct, p)
-            info.diag.append(rec)
-            if root and do_print:
-                print(_diag_line(rec))
-            if wide_advect_halo and P > 1:
-                _check_wide_precondition(it, rec.courant)
-        if wide_advect_halo and P > 1:                                                         # :475-477, decomposition-independent
-            if mg is None or not (dims[0] == 1 and dims[1] == 1):
-                raise L.Ns3dError("wide_advect_halo needs z-slab ranks on the C-ABI grid (mgpu.MgpuGrid)")
-            mg.advect_wide(col("Vx"), col("Vx_o"), col("Vy"), col("Vy_o"), col("Vz"), col("Vz_o"), col("C"), col("C_o"),
-                           p.dt, p.dx, p.dy, p.dz, faithful)
-        for f, c in zip(fs, ctxs):
-            if wide_advect_halo and P > 1:
-                break
-            if fused:       # :475-476 in one pass (ns3d_copy_advect): complete new fields into the *_o buffers, then the roles swap
-                _copy_advect_swap(f, p, faithful, c)
-                continue
-            K.copy(f.Vx_o, f.Vx, ctx=c); K.copy(f.Vy_o, f.Vy, ctx=c)                          # :475
-            K.copy(f.Vz_o, f.Vz, ctx=c); K.copy(f.C_o, f.C, ctx=c)
-            K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=c)  # :476
-        if not (wide_advect_halo and P > 1):
-            grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                 # :477 (not C)
-        if running is not None and _stats_due(it, statistics, stats_every):
-            running.sample(fs)
-        _observe(trc, prb, fs[0], p.dt)
-        frames(it)
+        if root and do_print:                                                                 # :456, :468
+            _print_step(it, errs if fused or pressure != "direct" else [], p.nchk, info.diag[-1] if monitor else None)
+        obs.end_step(it, fs)
+        frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
             K.copy(f.Vz_o, f.Vz, ctx=c)     # the one copy of :475 the swaps skipped (Vz is never advected): same final state
     sync()
     out = _gather_all(grid, fs)                                                               # :528-532
-    if running is not None:
-        info.stats = running.gathered(grid) if running.n else SimpleNamespace(n=0, wsum=0.0, mean=None, rs=None)
-    if vort is not None:
-        vort.compute(fs)
-        info.vortex = vort.gathered(grid)
-    if iso is not None:
-        info.isosurface = iso.extract(fs, computed=vort is not None)
-    if trc is not None:
-        info.tracers = trc.record()
-    if prb is not None:
-        info.probes = prb.gathered()
+    obs.finish(info, fs)
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
     return out + ((info,) if return_info else ())                                             # :535
-
-
-def _iso_spec(isosurface):
-    """(field, level, color) of the drivers' `isosurface=` keyword, None when it is off"""
-    if isosurface is None:
-        return None
-    if isinstance(isosurface, dict):
-        unknown = set(isosurface) - {"field", "level", "color"}
-        if unknown or "level" not in isosurface:
-            raise L.Ns3dError("isosurface = %r (a dict with field, level and optionally color)" % (isosurface,))
-        field, level, color = isosurface.get("field", "Q"), isosurface["level"], isosurface.get("color")
-    elif isinstance(isosurface, (int, float, np.integer, np.floating)) and not isinstance(isosurface, bool):
-        field, level, color = "Q", isosurface, None
-    else:
-        raise L.Ns3dError("isosurface = %r (a level of the Q-criterion, or a dict with field, level and optionally color)" % (isosurface,))
-    if field not in ISO_FIELDS or (color is not None and color not in ISO_FIELDS):
-        raise L.Ns3dError("isosurface: field = %r, color = %r (each one of %s)" % (field, color, ", ".join(ISO_FIELDS)))
-    if not np.isfinite(float(level)):
-        raise L.Ns3dError("isosurface: level = %r is not finite" % (level,))
-    return field, float(level), color
-
-
-ISO_FIELDS = ("Q", "Wx", "Wy", "Wz", "Pr", "C")
-
-
-class _IsoObserver:
-    """The drivers' `isosurface=` keyword: one isosurface.extract per local rank over the cubes that rank owns, concatenated in rank
-    order.  Q, Wx, Wy, Wz come from the run's VortexFields (`vort`) or from a scratch set of this observer's own."""
-
-    def __init__(self, spec, shape, ctxs, p, dims, coords, grid, vort, dtype):
-        self.field, self.level, self.color = spec
-        self.shape, self.ctxs, self.p, self.dims, self.coords, self.grid = tuple(shape), list(ctxs), p, tuple(dims), list(coords), grid
-        self.derived = [n for n in (self.field, self.color) if n in _VORTEX_NAMES]
-        self.vort = vort
-        if self.derived and vort is None:
-            self.vort = VortexFields(shape, ctxs, (p.dx, p.dy, p.dz), dtype)
-
-    def _array(self, name, l, fs):
-        if name is None:
-            return None
-        return getattr(self.vort.out[l], name) if name in _VORTEX_NAMES else getattr(fs[l], name)
-
-    def extract(self, fs, computed=False):
-        """the surface of the state in `fs` (one namespace of fields per local rank); computed: self.vort holds this state's fields"""
-        n = self.shape
-        if self.derived:
-            if not computed:
-                self.vort.compute(fs)
-            if len(fs) > 1:     # a seam's cubes need the neighbour's values in the halo cells, which ns3d_vortex leaves +0.0
-                self.grid.update_halo(*[[getattr(o, nm) for o in self.vort.out] for nm in dict.fromkeys(self.derived)])
-        pieces = []
-        for l, c in enumerate(self.ctxs):
-            co = self.coords[l]
-            lo = [0 if co[q] == 0 else 1 for q in range(3)]
-            hi = [n[q] - 1 for q in range(3)]
-            if self.derived:    # the global grid's outermost cells are +0.0 by ns3d_vortex's contract, not flow
-                lo = [1, 1, 1]
-                hi = [n[q] - 2 if co[q] == self.dims[q] - 1 else n[q] - 1 for q in range(3)]
-            pieces.append(ISO.extract(c, self._array(self.field, l, fs), self.level, color=self._array(self.color, l, fs), box=lo + hi,
-                                      origin=[co[q] * (n[q] - 2) for q in range(3)], spacings=(self.p.dx, self.p.dy, self.p.dz),
-                                      low_corner=(-self.p.lx / 2, -self.p.ly / 2, -self.p.lz / 2)))
-        return ISO.concat(pieces)
-
-
-def _observers(tracers, probes, shape, ctx, p, nt):
-    """(Tracers | None, Probes | None) of a one-rank run from the drivers' `tracers=` / `probes=` keywords; the box's low corner is
-    (−lx/2, −ly/2, −lz/2) in both scripts"""
-    spacings, origin = (p.dx, p.dy, p.dz), (-p.lx / 2, -p.ly / 2, -p.lz / 2)
-    trc = prb = None
-    if tracers is not None:
-        trc = Tracers(shape, ctx, spacings, origin)
-        if isinstance(tracers, (int, np.integer)) and not isinstance(tracers, bool):
-            if tracers < 0:
-                raise L.Ns3dError("tracers = %r (a number of particles >= 0, or an (N,3) array of start points)" % (tracers,))
-            trc.seed_random(int(tracers), 0)
-        else:
-            trc.seed_points(tracers)
-    if probes is not None:
-        prb = Probes(shape, ctx, spacings, origin, probes, nt)
-    return trc, prb
-
-
-def _observe(trc, prb, f, dt):
-    """end of a time step: the particles move through the step's final velocity field, the probes sample the final state"""
-    if trc is not None:
-        trc.advance(f, dt)
-    if prb is not None:
-        prb.record(f)
-
-
-def _check_stats_options(statistics, stats_every):
-    if statistics is not None and (int(statistics) != statistics or statistics < 1):
-        raise L.Ns3dError("statistics = %r (None, or the first step to sample: an integer >= 1)" % (statistics,))
-    if int(stats_every) != stats_every or stats_every < 1:
-        raise L.Ns3dError("stats_every = %r (an integer >= 1)" % (stats_every,))
-
-
-def _stats_due(it, first, every):
-    return it >= first and (it - first) % every == 0
 
 
 def _predict_swap(f, p, ctx):
@@ -688,11 +515,13 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     MAT file (numbered like the tracer dumps)."""
     if device is None:
         device = torch.cuda.current_device()
-    _check_stats_options(statistics, stats_every)
-    dev = torch.device("cuda", device)
-    ctx = K.Context(device, mode, async_=True)
     p = gpu_params(nx)
     nx, ny, nz = p.nx, p.ny, p.nz
+    grid = ZSlabGrid(nx, ny, nz, alone=True)                # the observers' view of this script: one rank
+    watch = dict(statistics=statistics, stats_every=stats_every, vortex=vortex, tracers=tracers, probes=probes, isosurface=isosurface)
+    check_options(grid, **watch)
+    dev = torch.device("cuda", device)
+    ctx = K.Context(device, mode, async_=True)
     niter = p.niter if niter_cap is None else min(p.niter, niter_cap)
     f = _alloc(nx, ny, nz, dtype, dev)
     Vx0, Pr0 = initial if initial is not None else gpu_initial_fields(p)
@@ -702,156 +531,93 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     pt = K.pt_params(f.Pr, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, L.NS3D_BC_GPU, False, 0.0, p.g)
     info = SimpleNamespace(iters=[], errs=[], params=p)
     nsave = nvis = 10                                                                         # :50,52
-    trc, prb = _observers(tracers, probes, (nx, ny, nz), ctx, p, nt)
-    if do_save:                                                                               # :89
+    obs = Observers(grid, [ctx], p, nt, dtype, gathered=False, **watch)
+    iframe = 0
+
+    def saved(it):                                  # :89 / :168-170; the observers' dumps are numbered in the MAT files' order
         os.makedirs("./out_save", exist_ok=True)
         ctx.sync()
-        _save_mat("out_save/step_0.mat", f, p, True)
-        if trc is not None:
-            Tracers.save_bins(trc.record(), 0)
-    iframe = 0
-    host = lambda: {n: K.to_numpy(getattr(f, n)) for n in ("Pr", "C", "Vx", "Vy", "Vz")}
-    vort = VortexFields((nx, ny, nz), [ctx], (p.dx, p.dy, p.dz), dtype) if vortex else None
-    iso_spec = _iso_spec(isosurface)
-    iso = _IsoObserver(iso_spec, (nx, ny, nz), [ctx], p, (1, 1, 1), [(0, 0, 0)], None, vort, dtype) if iso_spec is not None else None
-    if iso is not None and do_save:
-        iso.extract([f]).save_ply("out_save/out_iso_%04d.ply" % 0)
+        _save_mat("out_save/step_%d.mat" % it, f, p, it == 0)
+        obs.frame([f], save=it // nsave)
 
-    def vortex_frame():
-        vort.compute([f])
-        save_frame_vortex(vort.local(0), ny, nz, iframe, gpu_names=True)
-
-    if do_vis:                                                                                # :90-117
+    def drawn():                                    # :90-117 / :143-167
+        nonlocal iframe
         ctx.sync()
-        save_frame_gpu(host(), ny, nz, iframe)
-        if vort is not None:
-            vortex_frame()
-        if trc is not None:
-            save_frame_tracers(trc.record(), p.lx, p.ly, iframe)
+        save_frame_gpu({n: K.to_numpy(getattr(f, n)) for n in ("Pr", "C", "Vx", "Vy", "Vz")}, ny, nz, iframe)
+        obs.frame([f], vis=iframe)
         iframe += 1
-    step_params = None
+
+    if do_save:                                                                               # :89
+        saved(0)
+    if do_vis:                                                                                # :90-117
+        drawn()
     monitor = None
-    running = RunningStats((nx, ny, nz), [ctx]) if statistics is not None else None
     if diagnostics:
         info.diag = []
-        dp = K.diag_params(nx, ny, nz, p.dx, p.dy, p.dz, p.rho, cylinder=cyl)
-        monitor = lambda full: K.diagnostics(f.Vx, f.Vy, f.Vz, f.Pr if full else None, f.C if full else None, dp, ctx=ctx)
-    if fused and one_call and not diagnostics:      # the whole step :121-142 as ONE library call (ns3d_time_step)
-        step_params = L.StepParams(script=L.NS3D_BC_GPU, nx=nx, ny=ny, nz=nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau,
-                                   damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz, eps=p.eps, niter=niter, nchk=p.nchk, err_mul=p.ly * p.ly,
-                                   err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy, sinb=p.sinb, cosb=p.cosb, xco_g=0.0, yco_g=0.0,
-                                   zco_g=0.0, lx=p.lx, ly=p.ly, lz=p.lz, owns_inlet=0, owns_outlet=0, vin=0.0,
-                                   faithful=int(bool(faithful)), pressure=1 if pressure == "direct" else 0, write_stress=0)
+        monitor = _monitor(grid, [ctx], [f], [cyl], p)
+    obs.start()
+    step_params = None
+    if fused and one_call and not diagnostics:
+        step_params = _step_params(L.NS3D_BC_GPU, p, niter, faithful, pressure)
     for it in range(1, nt + 1):                                                               # :119
-        if step_params is not None:
+        if step_params is not None:                         # :121-142 (ns3d_time_step swaps the names in f like the swaps below)
             step_params.write_stress = 1 if it == nt else 0
             done, errs = K.time_step(f, step_params, ctx=ctx)
-            if do_print:
-                print("#it = %d" % it)                                                        # :125
-                for q_, e in enumerate(errs):
-                    print("  #iter = %d, err = %1.3e" % ((q_ + 1) * p.nchk, e))                # :134
-            info.iters.append(done); info.errs.append(errs)
-            if running is not None and _stats_due(it, statistics, stats_every):
-                running.sample([f])                         # ns3d_time_step has swapped the names: f holds the new fields
-            _observe(trc, prb, f, p.dt)
-            if do_vis and it % nvis == 0:                                                     # :143-167
-                ctx.sync()
-                save_frame_gpu(host(), ny, nz, iframe)
-                if vort is not None:
-                    vortex_frame()
-                if trc is not None:
-                    save_frame_tracers(trc.record(), p.lx, p.ly, iframe)
-                iframe += 1
-            if do_save and it % nsave == 0:                                                   # :168-170
-                ctx.sync()
-                _save_mat("out_save/step_%d.mat" % it, f, p, False)
-                if trc is not None:
-                    Tracers.save_bins(trc.record(), it // nsave)
-                if iso is not None:
-                    iso.extract([f]).save_ply("out_save/out_iso_%04d.ply" % (it // nsave))
-            continue
-        if fused:
-            if it == nt:            # the stress arrays as the reference leaves them after its last step: same final state
-                K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)
-            _predict_swap(f, p, ctx)                                                          # :121-122 in one pass
         else:
-            K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)  # :121
-            K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
-                        ctx=ctx)                                                              # :122
-        if monitor:
-            mom_predict = monitor(False).mom
-        K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                                  # :123
-        K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=ctx)                    # :124
-        if do_print:
-            print("#it = %d" % it)                                                            # :125
-        if pressure == "direct":        # outside parity: the exact solution of what :126-137 iterates towards
-            K.poisson_direct(f.Pr, f.dPrdtau, f.divV, pt, ctx=ctx)
-            done, errs = 0, [K.residual_max(f.Pr, f.divV, pt, ctx=ctx) * (p.ly * p.ly) / p.psc]
-        elif fused:
-            done, errs = K.pt_solve(f.Pr, f.dPrdtau, f.divV, pt, p.eps, niter, p.nchk, p.ly * p.ly, p.psc, ctx=ctx)
-        else:
-            errs, done = [], niter
-            for itr in range(1, niter + 1):                                                   # :126
-                K.update_dPrdtau(f.Pr, f.dPrdtau, f.divV, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, ctx=ctx)  # :127
-                K.update_Pr(f.Pr, f.dPrdtau, p.dtau, ctx=ctx)                                 # :128
-                K.set_bc_Pr_gpu(f.Pr, p.dz, nz, p.g, p.rho, ctx=ctx)                          # :129
-                if itr % p.nchk == 0:                                                         # :130
-                    K.compute_res(f.Rp, f.Pr, f.divV, p.rho, p.dt, p.dx, p.dy, p.dz, ctx=ctx)  # :131
-                    err = K.max_abs(f.Rp, ctx=ctx) * (p.ly * p.ly) / p.psc                      # :132
-                    errs.append(err)
-                    if err < p.eps or not math.isfinite(err):                                 # :135
-                        done = itr
-                        break
-        if do_print:
-            for q, e in enumerate(errs):
-                print("  #iter = %d, err = %1.3e" % ((q + 1) * p.nchk, e))                    # :134
+            if fused:
+                if it == nt:            # the stress arrays as the reference leaves them after its last step: same final state
+                    K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)
+                _predict_swap(f, p, ctx)                                                      # :121-122 in one pass
+            else:
+                K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)  # :121
+                K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
+                            ctx=ctx)                                                          # :122
+            if monitor:
+                mom_predict = monitor(False).mom
+            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                              # :123
+            K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=ctx)                # :124
+            if pressure == "direct":        # (:125, :134 print after the step)  outside parity: the exact solution of what :126-137 iterates towards
+                K.poisson_direct(f.Pr, f.dPrdtau, f.divV, pt, ctx=ctx)
+                done, errs = 0, [K.residual_max(f.Pr, f.divV, pt, ctx=ctx) * (p.ly * p.ly) / p.psc]
+            elif fused:
+                done, errs = K.pt_solve(f.Pr, f.dPrdtau, f.divV, pt, p.eps, niter, p.nchk, p.ly * p.ly, p.psc, ctx=ctx)
+            else:
+                errs, done = [], niter
+                for itr in range(1, niter + 1):                                               # :126
+                    K.update_dPrdtau(f.Pr, f.dPrdtau, f.divV, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, ctx=ctx)  # :127
+                    K.update_Pr(f.Pr, f.dPrdtau, p.dtau, ctx=ctx)                             # :128
+                    K.set_bc_Pr_gpu(f.Pr, p.dz, nz, p.g, p.rho, ctx=ctx)                      # :129
+                    if itr % p.nchk == 0:                                                     # :130
+                        K.compute_res(f.Rp, f.Pr, f.divV, p.rho, p.dt, p.dx, p.dy, p.dz, ctx=ctx)  # :131
+                        err = K.max_abs(f.Rp, ctx=ctx) * (p.ly * p.ly) / p.psc                      # :132
+                        errs.append(err)
+                        if err < p.eps or not math.isfinite(err):                             # :135
+                            done = itr
+                            break
+            K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=ctx)       # :138
+            if monitor:
+                mom_correct = monitor(False).mom
+            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                              # :139
+            K.set_bc_Vel_gpu(f.Vx, f.Vy, f.Vz, ctx=ctx)                                       # :140
+            if monitor:
+                info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
+            if fused:
+                _copy_advect_swap(f, p, faithful, ctx)                                        # :141-142 in one pass
+            else:
+                K.copy(f.Vx_o, f.Vx, ctx=ctx); K.copy(f.Vy_o, f.Vy, ctx=ctx)                  # :141
+                K.copy(f.Vz_o, f.Vz, ctx=ctx); K.copy(f.C_o, f.C, ctx=ctx)
+                K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=ctx)  # :142
         info.iters.append(done); info.errs.append(errs)
-        K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=ctx)            # :138
-        if monitor:
-            mom_correct = monitor(False).mom
-        K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                                  # :139
-        K.set_bc_Vel_gpu(f.Vx, f.Vy, f.Vz, ctx=ctx)                                           # :140
-        if monitor:
-            info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
-            if do_print:
-                print(_diag_line(info.diag[-1]))
-        if fused:
-            _copy_advect_swap(f, p, faithful, ctx)                                            # :141-142 in one pass
-        else:
-            K.copy(f.Vx_o, f.Vx, ctx=ctx); K.copy(f.Vy_o, f.Vy, ctx=ctx)                      # :141
-            K.copy(f.Vz_o, f.Vz, ctx=ctx); K.copy(f.C_o, f.C, ctx=ctx)
-            K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful, ctx=ctx)  # :142
-        if running is not None and _stats_due(it, statistics, stats_every):
-            running.sample([f])
-        _observe(trc, prb, f, p.dt)
+        if do_print:                                                                          # :125, :134
+            _print_step(it, errs, p.nchk, info.diag[-1] if monitor else None)
+        obs.end_step(it, [f])
         if do_vis and it % nvis == 0:                                                         # :143-167
-            ctx.sync()
-            save_frame_gpu(host(), ny, nz, iframe)
-            if vort is not None:
-                vortex_frame()
-            if trc is not None:
-                save_frame_tracers(trc.record(), p.lx, p.ly, iframe)
-            iframe += 1
+            drawn()
         if do_save and it % nsave == 0:                                                       # :168-170
-            ctx.sync()
-            _save_mat("out_save/step_%d.mat" % it, f, p, False)
-            if trc is not None:
-                Tracers.save_bins(trc.record(), it // nsave)
-            if iso is not None:
-                iso.extract([f]).save_ply("out_save/out_iso_%04d.ply" % (it // nsave))
+            saved(it)
     if fused and faithful and nt > 0:
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()
     info.ctx = ctx
-    if running is not None:
-        info.stats = running.local(0) if running.n else SimpleNamespace(n=0, wsum=0.0, mean=None, rs=None)
-    if vort is not None:
-        vort.compute([f])
-        info.vortex = vort.local(0)
-    if iso is not None:
-        info.isosurface = iso.extract([f], computed=vort is not None)
-    if trc is not None:
-        info.tracers = trc.record()
-    if prb is not None:
-        info.probes = prb.gathered()
+    obs.finish(info, [f])
     return f, info

@@ -19,10 +19,11 @@ import torch.distributed as dist
 
 
 class ZSlabGrid:
-    def __init__(self, nx, ny, nz, group=None, transport="auto"):
+    def __init__(self, nx, ny, nz, group=None, transport="auto", alone=False):
+        """alone: one rank, whatever process group exists (the single-device script's grid)"""
         self.nx, self.ny, self.nz = int(nx), int(ny), int(nz)
         self.group = group
-        if dist.is_available() and dist.is_initialized():
+        if not alone and dist.is_available() and dist.is_initialized():
             self.me = dist.get_rank(group)
             self.P = dist.get_world_size(group)
             self.backend = dist.get_backend(group)
@@ -31,6 +32,8 @@ class ZSlabGrid:
         self.dims = (1, 1, self.P)
         self.coords = (0, 0, self.me)
         self.nlocal, self.local_ranks = 1, [self.me]     # one rank per process (mgpu.MgpuGrid may hold several)
+        self.local_coords = [self.coords]
+        self.mg = self.contexts = None                   # no ns3d_mgpu behind this grid: the driver brings its own context
         self.lower = self.me - 1 if self.me > 0 else None
         self.upper = self.me + 1 if self.me < self.P - 1 else None
         if transport == "auto":
@@ -197,6 +200,16 @@ class ZSlabGrid:
             return np.asfortranarray(torch.cat([q.cpu() for q in parts], dim=0).numpy().transpose(2, 1, 0))
         dist.gather(t, None, dst=self._global_rank(0), group=self.group)
         return None
+
+    def is_root(self):
+        return self.me == 0
+
+    def gather_fields(self, A):
+        """gather of this rank's device array (`A`: the per-local-rank list of one, or the array), halo cells stripped:
+        Array(A)[2:end-1,2:end-1,2:end-1] (multi.jl:399)"""
+        t = A[0] if isinstance(A, (list, tuple)) else A
+        host = np.asfortranarray(t.permute(2, 1, 0).contiguous().cpu().numpy().transpose(2, 1, 0))
+        return self.gather(host[1:-1, 1:-1, 1:-1])
 
     def barrier(self):
         if self.P > 1:

@@ -17,6 +17,7 @@ import torch
 from . import lib as L
 
 _DT = {torch.float64: "f64", torch.float32: "f32"}
+ESIZE = {torch.float64: 8, torch.float32: 4, np.float64: 8, np.float32: 4, "f64": 8, "f32": 4}     # bytes per element
 
 
 # ---- column-major device arrays -------------------------------------------------------------------------
@@ -54,6 +55,12 @@ def _chk(t, shape=None, name="array"):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise L.Ns3dError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     return C.c_void_p(t.data_ptr())
+
+
+def _chk_V(Vx, Vy, Vz, n, tag=""):
+    """the three staggered velocity arrays of an n = (nx,ny,nz) cell grid, checked in this order"""
+    nx, ny, nz = n
+    return _chk(Vx, (nx + 1, ny, nz), "Vx" + tag), _chk(Vy, (nx, ny + 1, nz), "Vy" + tag), _chk(Vz, (nx, ny, nz + 1), "Vz" + tag)
 
 
 class Context:
@@ -95,13 +102,28 @@ class Context:
         self._stream = s.cuda_stream
         L.check(self.lib.ns3d_set_stream(self.handle, C.c_void_p(s.cuda_stream)))
 
+    def _pin_to_library_stream(self):
+        """the stream the library now launches on, as a torch stream; the context stays on it whatever PyTorch's current stream becomes"""
+        self._ext = torch.cuda.ExternalStream(int(self.lib.ns3d_get_stream(self.handle)), device=self.device)
+        self._pinned, self._stream = True, self._ext.cuda_stream
+        return self._ext
+
     def use_own_stream(self):
         """Back to the stream the context was created with (ns3d_use_own_stream: non-blocking, the context's own) and stay on it
         whatever PyTorch's current stream becomes.  Returns it as a torch stream, like reserve_cus."""
         L.check(self.lib.ns3d_use_own_stream(self.handle))
-        self._ext = torch.cuda.ExternalStream(int(self.lib.ns3d_get_stream(self.handle)), device=self.device)
-        self._pinned, self._stream = True, self._ext.cuda_stream
-        return self._ext
+        return self._pin_to_library_stream()
+
+    def follow_torch_stream(self):
+        """Launch where PyTorch launches now (`with torch.cuda.stream(...)` blocks), unless the context is pinned."""
+        if not self._pinned and torch.cuda.current_stream(self.device).cuda_stream != self._stream:
+            self.use_torch_stream()
+
+    def after_torch_fill(self):
+        """Fresh arrays on a pinned context: PyTorch fills a new array (zeros, uploads) on ITS current stream, which nothing orders with
+        a pinned context's kernels — so that stream is waited for first.  A context that follows PyTorch's stream needs nothing."""
+        if self._pinned:
+            torch.cuda.current_stream(self.device).synchronize()
 
     def sync(self):
         L.check(self.lib.ns3d_sync(self.handle))
@@ -115,9 +137,7 @@ class Context:
             self._ext = None
             self.use_torch_stream()
             return torch.cuda.current_stream(self.device)
-        self._ext = torch.cuda.ExternalStream(int(self.lib.ns3d_get_stream(self.handle)), device=self.device)
-        self._pinned, self._stream = True, self._ext.cuda_stream
-        return self._ext
+        return self._pin_to_library_stream()
 
     def set_pt_variant(self, v):
         L.check(self.lib.ns3d_set_pt_variant(self.handle, int(v)))
@@ -186,8 +206,7 @@ class Context:
             pass
 
     def call(self, name, ref, *args):
-        if not getattr(self, "_pinned", False) and torch.cuda.current_stream(self.device).cuda_stream != self._stream:
-            self.use_torch_stream()     # follow `with torch.cuda.stream(...)` blocks
+        self.follow_torch_stream()
         fn = getattr(self.lib, "ns3d_%s_%s" % (name, _DT[ref.dtype]))
         L.check(fn(self.handle, *args))
 
@@ -229,37 +248,31 @@ def update_tau(txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu, dx, dy, dz, ctx=Non
     nx, ny, nz = txx.shape
     c = (nx, ny, nz); s = (nx - 1, ny - 1, nz - 1)
     _ctx(ctx, txx).call("update_tau", txx, _chk(txx, c, "txx"), _chk(tyy, c, "tyy"), _chk(tzz, c, "tzz"),
-                        _chk(txy, s, "txy"), _chk(txz, s, "txz"), _chk(tyz, s, "tyz"),
-                        _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                        _chk(Vz, (nx, ny, nz + 1), "Vz"), *_d(mu, dx, dy, dz), nx, ny, nz)
+                        _chk(txy, s, "txy"), _chk(txz, s, "txz"), _chk(tyz, s, "tyz"), *_chk_V(Vx, Vy, Vz, c), *_d(mu, dx, dy, dz), nx, ny, nz)
 
 
 def predict_V(Vx, Vy, Vz, txx, tyy, tzz, txy, txz, tyz, rho, g, dt, dx, dy, dz, ctx=None):
     """predict_V!  multi.jl:50-55 / gpu.jl:187-192"""
     nx, ny, nz = txx.shape
     c = (nx, ny, nz); s = (nx - 1, ny - 1, nz - 1)
-    _ctx(ctx, txx).call("predict_V", txx, _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                        _chk(Vz, (nx, ny, nz + 1), "Vz"), _chk(txx, c, "txx"), _chk(tyy, c, "tyy"),
-                        _chk(tzz, c, "tzz"), _chk(txy, s, "txy"), _chk(txz, s, "txz"), _chk(tyz, s, "tyz"),
-                        *_d(rho, g, dt, dx, dy, dz), nx, ny, nz)
-
+    _ctx(ctx, txx).call("predict_V", txx, *_chk_V(Vx, Vy, Vz, c), _chk(txx, c, "txx"), _chk(tyy, c, "tyy"),
+                        _chk(tzz, c, "tzz"), _chk(txy, s, "txy"), _chk(txz, s, "txz"), _chk(tyz, s, "tyz"), *_d(rho, g, dt, dx, dy, dz), nx, ny, nz)
 
 
 def predict_fused(Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu, rho, g, dt, dx, dy, dz, ctx=None):
     """{update_τ!; predict_V!} (multi.jl:449,451) in one pass: complete predicted fields into buffers of their own, the stress
     arrays neither read nor written; the caller swaps the names."""
     nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    _ctx(ctx, Vx).call("predict_fused", Vx, _chk(Vx_new, (nx + 1, ny, nz), "Vx_new"), _chk(Vy_new, (nx, ny + 1, nz), "Vy_new"),
-                       _chk(Vz_new, (nx, ny, nz + 1), "Vz_new"), _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                       _chk(Vz, (nx, ny, nz + 1), "Vz"), *_d(mu, rho, g, dt, dx, dy, dz), nx, ny, nz)
+    _ctx(ctx, Vx).call("predict_fused", Vx, *_chk_V(Vx_new, Vy_new, Vz_new, (nx, ny, nz), "_new"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)),
+                       *_d(mu, rho, g, dt, dx, dy, dz), nx, ny, nz)
+
 
 def set_cylinder(Cf, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb, *rest, ctx=None):
     """set_cylinder!  multi.jl:249-281 (19 arguments: …,xco_g,yco_g,zco_g,lx,ly,lz,dx,dy,dz) or
     gpu.jl:336-368 (16 arguments: …,lx,ly,lz,dx,dy,dz) — dispatched on the argument count like the two
     scripts' definitions."""
     nx, ny, nz = Cf.shape
-    ptrs = (_chk(Cf, (nx, ny, nz), "C"), _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-            _chk(Vz, (nx, ny, nz + 1), "Vz"))
+    ptrs = (_chk(Cf, (nx, ny, nz), "C"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)))
     if len(rest) == 9:
         _ctx(ctx, Cf).call("set_cylinder", Cf, *ptrs, *_d(a2, b2, ox, oy, sinb, cosb, *rest), nx, ny, nz)
     elif len(rest) == 6:
@@ -271,9 +284,7 @@ def set_cylinder(Cf, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb, *rest, ctx=None):
 def update_divV(divV, Vx, Vy, Vz, dx, dy, dz, ctx=None):
     """update_∇V!  multi.jl:61-64 / gpu.jl:194-197"""
     nx, ny, nz = divV.shape
-    _ctx(ctx, divV).call("update_divV", divV, _chk(divV, None, "divV"), _chk(Vx, (nx + 1, ny, nz), "Vx"),
-                         _chk(Vy, (nx, ny + 1, nz), "Vy"), _chk(Vz, (nx, ny, nz + 1), "Vz"), *_d(dx, dy, dz),
-                         nx, ny, nz)
+    _ctx(ctx, divV).call("update_divV", divV, _chk(divV, None, "divV"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), *_d(dx, dy, dz), nx, ny, nz)
 
 
 def update_dPrdtau(Pr, dPrdtau, divV, rho, dt, dtau, damp, dx, dy, dz, ctx=None):
@@ -304,191 +315,10 @@ def max_abs(A, ctx=None):
     return out.value
 
 
-def diag_params(nx, ny, nz, dx, dy, dz, rho, seam_lo=(0, 0, 0), seam_hi=(0, 0, 0), cylinder=None):
-    """lib.DiagParams for ns3d_diagnostics.  cylinder: None, or set_cylinder!'s scalars in the reference's own order —
-    15 values (a2,b2,ox,oy,sinβ,cosβ,xco_g,yco_g,zco_g,lx,ly,lz,dx,dy,dz: multi.jl:249) or 12 (…,cosβ,lx,ly,lz,dx,dy,dz: gpu.jl:336),
-    told apart by their number like set_cylinder's own arguments."""
-    dp = L.DiagParams(nx=int(nx), ny=int(ny), nz=int(nz), dx=dx, dy=dy, dz=dz, rho=rho)
-    dp.seam_lo[:] = [int(bool(q)) for q in seam_lo]
-    dp.seam_hi[:] = [int(bool(q)) for q in seam_hi]
-    if cylinder is not None:
-        cyl = tuple(float(q) for q in cylinder)
-        if len(cyl) == 15:
-            dp.cylinder = 1
-            dp.a2, dp.b2, dp.ox, dp.oy, dp.sinb, dp.cosb, dp.xco_g, dp.yco_g, dp.zco_g, dp.lx, dp.ly, dp.lz = cyl[:12]
-        elif len(cyl) == 12:
-            dp.cylinder = 2
-            dp.a2, dp.b2, dp.ox, dp.oy, dp.sinb, dp.cosb, dp.lx, dp.ly, dp.lz = cyl[:9]
-        else:
-            raise TypeError("diag_params: cylinder takes set_cylinder!'s 15 (multi.jl) or 12 (gpu.jl) scalars")
-    return dp
-
-
-def diag_record(d):
-    """lib.Diag → a namespace of Python values (vmax, mom, n_masked: tuples per direction)."""
-    from types import SimpleNamespace
-    return SimpleNamespace(vmax=tuple(d.vmax), div_max=d.div_max, pr_min=d.pr_min, pr_max=d.pr_max, ke=d.ke, c_vol=d.c_vol,
-                           mom=tuple(d.mom), n_masked=tuple(int(q) for q in d.n_masked), nonfinite=int(d.nonfinite))
-
-
-def diagnostics(Vx, Vy, Vz, Pr, Cf, dp, ctx=None):
-    """ns3d_diagnostics: the flow monitor — one read-only pass over the fields on the device (include/ns3d.h): max|V| per
-    direction, max|∇V|, min / max Pr, kinetic energy, Σ C·dV, the momentum set_cylinder! is about to remove and a non-finite flag,
-    over the entries this rank owns (dp.seam_lo / seam_hi).  Pr or Cf may be None (their entries come back NaN).  Blocks."""
-    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    if (dp.nx, dp.ny, dp.nz) != (nx, ny, nz):
-        raise L.Ns3dError("diagnostics: params grid %r differs from the fields' %r" % ((dp.nx, dp.ny, dp.nz), (nx, ny, nz)))
-    out = L.Diag()
-    opt = lambda t, n: None if t is None else _chk(t, (nx, ny, nz), n)
-    _ctx(ctx, Vx).call("diagnostics", Vx, _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                       _chk(Vz, (nx, ny, nz + 1), "Vz"), opt(Pr, "Pr"), opt(Cf, "C"), C.byref(dp), C.byref(out))
-    return diag_record(out)
-
-
-def _chk_blocks(t, nblocks, cells, name):
-    """a float64 device array of `nblocks` consecutive column-major (nx,ny,nz) blocks: kernels.zeros((nx, ny, nz·nblocks)) or any
-    contiguous float64 tensor of that many elements"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
-        raise L.Ns3dError("%s must be a float64 CUDA/HIP tensor" % name)
-    if t.numel() != nblocks * cells:
-        raise L.Ns3dError("%s has %d elements, expected %d blocks of %d" % (name, t.numel(), nblocks, cells))
-    if t.dim() == 3:
-        return _chk(t, None, name)
-    if not t.is_contiguous():
-        raise L.Ns3dError("%s must be contiguous" % name)
-    return C.c_void_p(t.data_ptr())
-
-
-def stats_accumulate(S, Vx, Vy, Vz, Pr, weight=1.0, ctx=None):
-    """ns3d_stats_accumulate: one sample into the running sums S (lib.NS3D_STATS_SLOTS blocks of (nx,ny,nz) float64, slot order
-    stats.SLOTS): S += weight·(u, v, w, p, uu, vv, ww, uv, uw, vw, pp) of the cell-centred values, one fused pass on the device.
-    Pr may be None (slots p and pp are left alone).  Enqueues; no read-back."""
-    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    c = _ctx(ctx, Vx)
-    c.call("stats_accumulate", Vx, _chk_blocks(S, L.NS3D_STATS_SLOTS, nx * ny * nz, "S"), _chk(Vx, (nx + 1, ny, nz), "Vx"),
-           _chk(Vy, (nx, ny + 1, nz), "Vy"), _chk(Vz, (nx, ny, nz + 1), "Vz"),
-           None if Pr is None else _chk(Pr, (nx, ny, nz), "Pr"), C.c_double(float(weight)), nx, ny, nz)
-
-
-def vortex(Vx, Vy, Vz, dx, dy, dz, *, Wx=None, Wy=None, Wz=None, Q=None, ctx=None):
-    """ns3d_vortex: the vorticity components Wx, Wy, Wz and the Q-criterion of the staggered velocity field, each a cell-centred
-    (nx,ny,nz) array of the fields' dtype, in one fused pass on the device (include/ns3d.h has the expression).  Interior cells
-    receive the values, every other entry +0.0.  Only the outputs that are given are computed; at least one is needed.
-    Enqueues; no read-back."""
-    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    outs = []
-    for name, t in (("Wx", Wx), ("Wy", Wy), ("Wz", Wz), ("Q", Q)):
-        if t is None:
-            outs.append(None)
-            continue
-        outs.append(_chk(t, (nx, ny, nz), name))
-        if t.dtype != Vx.dtype or t.device != Vx.device:
-            raise L.Ns3dError("%s is %s on %s, the velocities are %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
-    if all(o is None for o in outs):
-        raise L.Ns3dError("vortex: give at least one of Wx, Wy, Wz, Q")
-    for name, t in (("Vy", Vy), ("Vz", Vz)):
-        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
-            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
-    _ctx(ctx, Vx).call("vortex", Vx, *outs, _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                       _chk(Vz, (nx, ny, nz + 1), "Vz"), *_d(dx, dy, dz), nx, ny, nz)
-
-
-def _chk_points(t, n, blocks, dtype, name, ref):
-    """a contiguous device array of `blocks`·n elements of `dtype` on the fields' device: X and U are (3, n) float64, state (n,) uint8"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-        raise L.Ns3dError("%s must be a %s CUDA/HIP tensor" % (name, dtype))
-    if t.device != ref.device:
-        raise L.Ns3dError("%s is on %s, the field on %s" % (name, t.device, ref.device))
-    if not t.is_contiguous() or t.numel() != blocks * n:
-        raise L.Ns3dError("%s must be contiguous with %d x %d elements, got shape %s" % (name, blocks, n, tuple(t.shape)))
-    return C.c_void_p(t.data_ptr())
-
-
-def sample(A, X, out, state=None, stagger=(0, 0, 0), ctx=None):
-    """ns3d_sample: the field A (any extents ≥ 2; `stagger` flags the directions whose nodes sit at integers) interpolated at the
-    points X — a (3, n) float64 array of INDEX-space coordinates ξ | η | ζ — into out (n float64), trilinear as backtrack!
-    (include/ns3d.h has the definition; the same bits in every arithmetic mode).  Points that are dead (state, n uint8, optional),
-    not finite or outside the closed box receive NaN.  Enqueues; no read-back."""
-    n = out.numel() if isinstance(out, torch.Tensor) else 0
-    ex, ey, ez = A.shape
-    sx, sy, sz = (int(q) for q in stagger)
-    _ctx(ctx, A).call("sample", A, _chk_points(out, n, 1, torch.float64, "out", A), _chk_points(X, n, 3, torch.float64, "X", A),
-                      None if state is None else _chk_points(state, n, 1, torch.uint8, "state", A), C.c_long(n),
-                      _chk(A, None, "A"), ex, ey, ez, sx, sy, sz)
-
-
-def tracers_advance(X, state, Vx, Vy, Vz, cx, cy, cz, U=None, ctx=None):
-    """ns3d_tracers_advance: one explicit-midpoint step of the particles X ((3, n) float64, index space) with state (n uint8: 1 alive)
-    through the frozen field Vx, Vy, Vz; cx, cy, cz = dt/dx, dt/dy, dt/dz.  Particles that leave the closed box [0,nx]×[0,ny]×[0,nz]
-    or reach a non-finite position die where they are; U ((3, n) float64, optional) receives the velocity at the start points.
-    In place; enqueues; no read-back."""
-    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    n = state.numel() if isinstance(state, torch.Tensor) else 0
-    for name, t in (("Vy", Vy), ("Vz", Vz)):
-        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
-            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
-    _ctx(ctx, Vx).call("tracers_advance", Vx, _chk_points(X, n, 3, torch.float64, "X", Vx),
-                       _chk_points(state, n, 1, torch.uint8, "state", Vx),
-                       None if U is None else _chk_points(U, n, 3, torch.float64, "U", Vx), C.c_long(n),
-                       _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"), _chk(Vz, (nx, ny, nz + 1), "Vz"),
-                       *_d(cx, cy, cz), nx, ny, nz)
-
-
-def isosurface(A, level, color=None, box=None, origin=None, tri=None, val=None, cap=0, ctx=None):
-    """ns3d_isosurface: the triangles of the level set A = level by marching tetrahedra (include/ns3d.h has the definition; the same
-    bits in every arithmetic mode), in index space.  A: any column-major array of extents ≥ 2 whose entries are nodes at integer
-    positions; color: a second array of the same shape, interpolated at the vertices into val; box = (lo_x, lo_y, lo_z, hi_x, hi_y,
-    hi_z), a closed node range (None: the whole array); origin: three ints added to the node indices.  tri (≥ 9·cap float64) and val
-    (≥ 3·cap float64) receive the first min(n, cap) triangles; cap = 0 without tri is the count-only form.  Returns n, the number
-    of triangles the surface has; blocks for that read-back."""
-    ex, ey, ez = A.shape
-    cap = int(cap)
-    if isinstance(color, torch.Tensor) and (color.dtype != A.dtype or color.device != A.device):
-        raise L.Ns3dError("color is %s on %s, A is %s on %s" % (color.dtype, color.device, A.dtype, A.device))
-    ptrs = []
-    for name, t, per in (("tri", tri, 9), ("val", val, 3)):
-        if t is None:
-            ptrs.append(None)
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.device != A.device:
-            raise L.Ns3dError("%s must be a contiguous float64 CUDA/HIP tensor on A's device" % name)
-        if t.numel() < per * cap:
-            raise L.Ns3dError("%s holds %d elements, cap = %d needs %d" % (name, t.numel(), cap, per * cap))
-        ptrs.append(C.c_void_p(t.data_ptr()))
-    b = None if box is None else (C.c_int * 6)(*(int(q) for q in box))
-    o = None if origin is None else (C.c_int * 3)(*(int(q) for q in origin))
-    n = C.c_longlong(-1)
-    _ctx(ctx, A).call("isosurface", A, _chk(A, None, "A"), None if color is None else _chk(color, (ex, ey, ez), "color"), ex, ey, ez, b, o,
-                      C.c_double(float(level)), ptrs[0], ptrs[1], C.c_longlong(cap), C.byref(n))
-    return n.value
-
-
-def _untyped(ctx, ref, name, *args):
-    c = _ctx(ctx, ref)
-    if not getattr(c, "_pinned", False) and torch.cuda.current_stream(c.device).cuda_stream != c._stream:
-        c.use_torch_stream()
-    L.check(getattr(c.lib, name)(c.handle, *args))
-
-
-def stats_reset(S, shape, ctx=None):
-    """ns3d_stats_reset: S = 0 on the context's stream; shape = (nx, ny, nz) of one block."""
-    nx, ny, nz = (int(q) for q in shape)
-    _untyped(ctx, S, "ns3d_stats_reset", _chk_blocks(S, L.NS3D_STATS_SLOTS, nx * ny * nz, "S"), nx, ny, nz)
-
-
-def stats_finalize(S, wsum, mean, rs, shape, ctx=None):
-    """ns3d_stats_finalize: mean (4 blocks) = S[u,v,w,p]/wsum; rs (7 blocks, or None) = S[uu…vw,pp]/wsum − ā·b̄."""
-    nx, ny, nz = (int(q) for q in shape)
-    n = nx * ny * nz
-    _untyped(ctx, S, "ns3d_stats_finalize", _chk_blocks(S, L.NS3D_STATS_SLOTS, n, "S"), C.c_double(float(wsum)),
-             _chk_blocks(mean, 4, n, "mean"), None if rs is None else _chk_blocks(rs, 7, n, "rs"), nx, ny, nz)
-
-
 def correct_V(Vx, Vy, Vz, Pr, dt, rho, dx, dy, dz, ctx=None):
     """correct_V!  multi.jl:97-102 / gpu.jl:214-219"""
     nx, ny, nz = Pr.shape
-    _ctx(ctx, Pr).call("correct_V", Pr, _chk(Vx, (nx + 1, ny, nz), "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                       _chk(Vz, (nx, ny, nz + 1), "Vz"), _chk(Pr, None, "Pr"), *_d(dt, rho, dx, dy, dz), nx, ny, nz)
+    _ctx(ctx, Pr).call("correct_V", Pr, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), _chk(Pr, None, "Pr"), *_d(dt, rho, dx, dy, dz), nx, ny, nz)
 
 
 def _bc(name, A, *extra, ctx=None):
@@ -577,15 +407,13 @@ def set_bc_Vel_multi(Vx, Vy, Vz, owns_inlet, vin, ctx=None):
     """set_bc_Vel!(Vx,Vy,Vz,xvo_g,lx,vin) of multi.jl:156-166 (flag instead of `xvo_g == -lx/2`; halo update
     multi.jl:167 is the caller's)."""
     nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    _ctx(ctx, Vx).call("set_bc_Vel", Vx, _chk(Vx, None, "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                       _chk(Vz, (nx, ny, nz + 1), "Vz"), L.NS3D_BC_MULTI, int(bool(owns_inlet)), *_d(vin), nx, ny, nz)
+    _ctx(ctx, Vx).call("set_bc_Vel", Vx, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), L.NS3D_BC_MULTI, int(bool(owns_inlet)), *_d(vin), nx, ny, nz)
 
 
 def set_bc_Vel_gpu(Vx, Vy, Vz, ctx=None):
     """set_bc_Vel!(Vx,Vy,Vz,Vprof) of gpu.jl:264-279 (Vprof is unused there)."""
     nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
-    _ctx(ctx, Vx).call("set_bc_Vel", Vx, _chk(Vx, None, "Vx"), _chk(Vy, (nx, ny + 1, nz), "Vy"),
-                       _chk(Vz, (nx, ny, nz + 1), "Vz"), L.NS3D_BC_GPU, 0, *_d(0.0), nx, ny, nz)
+    _ctx(ctx, Vx).call("set_bc_Vel", Vx, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), L.NS3D_BC_GPU, 0, *_d(0.0), nx, ny, nz)
 
 
 # ---- fused pseudo-transient path ------------------------------------------------------------------------
@@ -698,3 +526,178 @@ def pt_solve(Pr, dPrdtau, divV, p, eps, niter, nchk, err_mul, err_div, ctx=None)
                        _chk(divV, (nx, ny, nz), "divV"), C.byref(p), C.c_double(eps), int(niter), int(nchk),
                        C.c_double(err_mul), C.c_double(err_div), C.byref(it), hist, cap, C.byref(nchecks))
     return it.value, list(hist[: nchecks.value])
+
+
+# ---- observers of a running flow: monitor, statistics, vortex fields, tracers and probes, isosurfaces ----------------
+def diag_params(nx, ny, nz, dx, dy, dz, rho, seam_lo=(0, 0, 0), seam_hi=(0, 0, 0), cylinder=None):
+    """lib.DiagParams for ns3d_diagnostics.  cylinder: None, or set_cylinder!'s scalars in the reference's own order —
+    15 values (a2,b2,ox,oy,sinβ,cosβ,xco_g,yco_g,zco_g,lx,ly,lz,dx,dy,dz: multi.jl:249) or 12 (…,cosβ,lx,ly,lz,dx,dy,dz: gpu.jl:336),
+    told apart by their number like set_cylinder's own arguments."""
+    dp = L.DiagParams(nx=int(nx), ny=int(ny), nz=int(nz), dx=dx, dy=dy, dz=dz, rho=rho)
+    dp.seam_lo[:] = [int(bool(q)) for q in seam_lo]
+    dp.seam_hi[:] = [int(bool(q)) for q in seam_hi]
+    if cylinder is not None:
+        cyl = tuple(float(q) for q in cylinder)
+        if len(cyl) == 15:
+            dp.cylinder = 1
+            dp.a2, dp.b2, dp.ox, dp.oy, dp.sinb, dp.cosb, dp.xco_g, dp.yco_g, dp.zco_g, dp.lx, dp.ly, dp.lz = cyl[:12]
+        elif len(cyl) == 12:
+            dp.cylinder = 2
+            dp.a2, dp.b2, dp.ox, dp.oy, dp.sinb, dp.cosb, dp.lx, dp.ly, dp.lz = cyl[:9]
+        else:
+            raise TypeError("diag_params: cylinder takes set_cylinder!'s 15 (multi.jl) or 12 (gpu.jl) scalars")
+    return dp
+
+
+def diag_record(d):
+    """lib.Diag → a namespace of Python values (vmax, mom, n_masked: tuples per direction)."""
+    from types import SimpleNamespace
+    return SimpleNamespace(vmax=tuple(d.vmax), div_max=d.div_max, pr_min=d.pr_min, pr_max=d.pr_max, ke=d.ke, c_vol=d.c_vol,
+                           mom=tuple(d.mom), n_masked=tuple(int(q) for q in d.n_masked), nonfinite=int(d.nonfinite))
+
+
+def diagnostics(Vx, Vy, Vz, Pr, Cf, dp, ctx=None):
+    """ns3d_diagnostics: the flow monitor — one read-only pass over the fields on the device (include/ns3d.h): max|V| per
+    direction, max|∇V|, min / max Pr, kinetic energy, Σ C·dV, the momentum set_cylinder! is about to remove and a non-finite flag,
+    over the entries this rank owns (dp.seam_lo / seam_hi).  Pr or Cf may be None (their entries come back NaN).  Blocks."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    if (dp.nx, dp.ny, dp.nz) != (nx, ny, nz):
+        raise L.Ns3dError("diagnostics: params grid %r differs from the fields' %r" % ((dp.nx, dp.ny, dp.nz), (nx, ny, nz)))
+    out = L.Diag()
+    opt = lambda t, n: None if t is None else _chk(t, (nx, ny, nz), n)
+    _ctx(ctx, Vx).call("diagnostics", Vx, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), opt(Pr, "Pr"), opt(Cf, "C"), C.byref(dp), C.byref(out))
+    return diag_record(out)
+
+
+def _chk_blocks(t, nblocks, cells, name):
+    """a float64 device array of `nblocks` consecutive column-major (nx,ny,nz) blocks: kernels.zeros((nx, ny, nz·nblocks)) or any
+    contiguous float64 tensor of that many elements"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+        raise L.Ns3dError("%s must be a float64 CUDA/HIP tensor" % name)
+    if t.numel() != nblocks * cells:
+        raise L.Ns3dError("%s has %d elements, expected %d blocks of %d" % (name, t.numel(), nblocks, cells))
+    if t.dim() == 3:
+        return _chk(t, None, name)
+    if not t.is_contiguous():
+        raise L.Ns3dError("%s must be contiguous" % name)
+    return C.c_void_p(t.data_ptr())
+
+
+def stats_accumulate(S, Vx, Vy, Vz, Pr, weight=1.0, ctx=None):
+    """ns3d_stats_accumulate: one sample into the running sums S (lib.NS3D_STATS_SLOTS blocks of (nx,ny,nz) float64, slot order
+    stats.SLOTS): S += weight·(u, v, w, p, uu, vv, ww, uv, uw, vw, pp) of the cell-centred values, one fused pass on the device.
+    Pr may be None (slots p and pp are left alone).  Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    c = _ctx(ctx, Vx)
+    c.call("stats_accumulate", Vx, _chk_blocks(S, L.NS3D_STATS_SLOTS, nx * ny * nz, "S"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)),
+           None if Pr is None else _chk(Pr, (nx, ny, nz), "Pr"), C.c_double(float(weight)), nx, ny, nz)
+
+
+def vortex(Vx, Vy, Vz, dx, dy, dz, *, Wx=None, Wy=None, Wz=None, Q=None, ctx=None):
+    """ns3d_vortex: the vorticity components Wx, Wy, Wz and the Q-criterion of the staggered velocity field, each a cell-centred
+    (nx,ny,nz) array of the fields' dtype, in one fused pass on the device (include/ns3d.h has the expression).  Interior cells
+    receive the values, every other entry +0.0.  Only the outputs that are given are computed; at least one is needed.
+    Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    outs = []
+    for name, t in (("Wx", Wx), ("Wy", Wy), ("Wz", Wz), ("Q", Q)):
+        if t is None:
+            outs.append(None)
+            continue
+        outs.append(_chk(t, (nx, ny, nz), name))
+        if t.dtype != Vx.dtype or t.device != Vx.device:
+            raise L.Ns3dError("%s is %s on %s, the velocities are %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    if all(o is None for o in outs):
+        raise L.Ns3dError("vortex: give at least one of Wx, Wy, Wz, Q")
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("vortex", Vx, *outs, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), *_d(dx, dy, dz), nx, ny, nz)
+
+
+def _chk_points(t, n, blocks, dtype, name, ref):
+    """a contiguous device array of `blocks`·n elements of `dtype` on the fields' device: X and U are (3, n) float64, state (n,) uint8"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+        raise L.Ns3dError("%s must be a %s CUDA/HIP tensor" % (name, dtype))
+    if t.device != ref.device:
+        raise L.Ns3dError("%s is on %s, the field on %s" % (name, t.device, ref.device))
+    if not t.is_contiguous() or t.numel() != blocks * n:
+        raise L.Ns3dError("%s must be contiguous with %d x %d elements, got shape %s" % (name, blocks, n, tuple(t.shape)))
+    return C.c_void_p(t.data_ptr())
+
+
+def sample(A, X, out, state=None, stagger=(0, 0, 0), ctx=None):
+    """ns3d_sample: the field A (any extents ≥ 2; `stagger` flags the directions whose nodes sit at integers) interpolated at the
+    points X — a (3, n) float64 array of INDEX-space coordinates ξ | η | ζ — into out (n float64), trilinear as backtrack!
+    (include/ns3d.h has the definition; the same bits in every arithmetic mode).  Points that are dead (state, n uint8, optional),
+    not finite or outside the closed box receive NaN.  Enqueues; no read-back."""
+    n = out.numel() if isinstance(out, torch.Tensor) else 0
+    ex, ey, ez = A.shape
+    sx, sy, sz = (int(q) for q in stagger)
+    _ctx(ctx, A).call("sample", A, _chk_points(out, n, 1, torch.float64, "out", A), _chk_points(X, n, 3, torch.float64, "X", A),
+                      None if state is None else _chk_points(state, n, 1, torch.uint8, "state", A), C.c_long(n),
+                      _chk(A, None, "A"), ex, ey, ez, sx, sy, sz)
+
+
+def tracers_advance(X, state, Vx, Vy, Vz, cx, cy, cz, U=None, ctx=None):
+    """ns3d_tracers_advance: one explicit-midpoint step of the particles X ((3, n) float64, index space) with state (n uint8: 1 alive)
+    through the frozen field Vx, Vy, Vz; cx, cy, cz = dt/dx, dt/dy, dt/dz.  Particles that leave the closed box [0,nx]×[0,ny]×[0,nz]
+    or reach a non-finite position die where they are; U ((3, n) float64, optional) receives the velocity at the start points.
+    In place; enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    n = state.numel() if isinstance(state, torch.Tensor) else 0
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("tracers_advance", Vx, _chk_points(X, n, 3, torch.float64, "X", Vx), _chk_points(state, n, 1, torch.uint8, "state", Vx),
+                       None if U is None else _chk_points(U, n, 3, torch.float64, "U", Vx), C.c_long(n),
+                       *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), *_d(cx, cy, cz), nx, ny, nz)
+
+
+def isosurface(A, level, color=None, box=None, origin=None, tri=None, val=None, cap=0, ctx=None):
+    """ns3d_isosurface: the triangles of the level set A = level by marching tetrahedra (include/ns3d.h has the definition; the same
+    bits in every arithmetic mode), in index space.  A: any column-major array of extents ≥ 2 whose entries are nodes at integer
+    positions; color: a second array of the same shape, interpolated at the vertices into val; box = (lo_x, lo_y, lo_z, hi_x, hi_y,
+    hi_z), a closed node range (None: the whole array); origin: three ints added to the node indices.  tri (≥ 9·cap float64) and val
+    (≥ 3·cap float64) receive the first min(n, cap) triangles; cap = 0 without tri is the count-only form.  Returns n, the number
+    of triangles the surface has; blocks for that read-back."""
+    ex, ey, ez = A.shape
+    cap = int(cap)
+    if isinstance(color, torch.Tensor) and (color.dtype != A.dtype or color.device != A.device):
+        raise L.Ns3dError("color is %s on %s, A is %s on %s" % (color.dtype, color.device, A.dtype, A.device))
+    ptrs = []
+    for name, t, per in (("tri", tri, 9), ("val", val, 3)):
+        if t is None:
+            ptrs.append(None)
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.device != A.device:
+            raise L.Ns3dError("%s must be a contiguous float64 CUDA/HIP tensor on A's device" % name)
+        if t.numel() < per * cap:
+            raise L.Ns3dError("%s holds %d elements, cap = %d needs %d" % (name, t.numel(), cap, per * cap))
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    b = None if box is None else (C.c_int * 6)(*(int(q) for q in box))
+    o = None if origin is None else (C.c_int * 3)(*(int(q) for q in origin))
+    n = C.c_longlong(-1)
+    _ctx(ctx, A).call("isosurface", A, _chk(A, None, "A"), None if color is None else _chk(color, (ex, ey, ez), "color"), ex, ey, ez, b, o,
+                      C.c_double(float(level)), ptrs[0], ptrs[1], C.c_longlong(cap), C.byref(n))
+    return n.value
+
+
+def _untyped(ctx, ref, name, *args):
+    c = _ctx(ctx, ref)
+    c.follow_torch_stream()
+    L.check(getattr(c.lib, name)(c.handle, *args))
+
+
+def stats_reset(S, shape, ctx=None):
+    """ns3d_stats_reset: S = 0 on the context's stream; shape = (nx, ny, nz) of one block."""
+    nx, ny, nz = (int(q) for q in shape)
+    _untyped(ctx, S, "ns3d_stats_reset", _chk_blocks(S, L.NS3D_STATS_SLOTS, nx * ny * nz, "S"), nx, ny, nz)
+
+
+def stats_finalize(S, wsum, mean, rs, shape, ctx=None):
+    """ns3d_stats_finalize: mean (4 blocks) = S[u,v,w,p]/wsum; rs (7 blocks, or None) = S[uu…vw,pp]/wsum − ā·b̄."""
+    nx, ny, nz = (int(q) for q in shape)
+    n = nx * ny * nz
+    _untyped(ctx, S, "ns3d_stats_finalize", _chk_blocks(S, L.NS3D_STATS_SLOTS, n, "S"), C.c_double(float(wsum)),
+             _chk_blocks(mean, 4, n, "mean"), None if rs is None else _chk_blocks(rs, 7, n, "rs"), nx, ny, nz)

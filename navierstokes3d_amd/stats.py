@@ -4,7 +4,6 @@ sample, ns3d_stats_accumulate; ns3d_stats_finalize at the end); this module owns
 gathers the result through the grid.  PyTorch does no arithmetic here."""
 from types import SimpleNamespace
 
-import numpy as np
 import torch
 
 from . import kernels as K
@@ -16,9 +15,6 @@ MEAN = ("U", "V", "W", "P")                                  # blocks of ns3d_st
 RS = ("uu", "vv", "ww", "uv", "uw", "vw", "pp")               # blocks of its `rs`
 
 
-_ESIZE = {torch.float64: 8, torch.float32: 4, np.float64: 8, np.float32: 4, "f64": 8, "f32": 4}
-
-
 def bytes_per_cell(dtype=torch.float64, with_pr=True):
     """NOMINAL memory traffic of one ns3d_stats_accumulate call per cell, the accounting the rates are quoted in: one read of each
     field, one load and one store of each accumulator (fp64 whatever the fields are) — 208 / 192 bytes for fp64 / fp32 fields.
@@ -26,14 +22,14 @@ def bytes_per_cell(dtype=torch.float64, with_pr=True):
     interface was specified with; it is 16 bytes above what the kernel then moves, because the call leaves BOTH slots p and pp
     alone — bytes_moved_per_cell gives that figure (168 / 156).  With Pr the two agree."""
     nfields, nslots = (4, len(SLOTS)) if with_pr else (3, len(SLOTS) - 1)
-    return nfields * _ESIZE[dtype] + nslots * 2 * 8
+    return nfields * K.ESIZE[dtype] + nslots * 2 * 8
 
 
 def bytes_moved_per_cell(dtype=torch.float64, with_pr=True):
     """What k_stats reads and writes per cell: the fields it reads once and a load and a store of every slot it touches — all
     eleven with Pr (208 / 192 bytes), nine without (slots p and pp are neither read nor written: 168 / 156 bytes)."""
     nfields, nslots = (4, len(SLOTS)) if with_pr else (3, len(SLOTS) - 2)
-    return nfields * _ESIZE[dtype] + nslots * 2 * 8
+    return nfields * K.ESIZE[dtype] + nslots * 2 * 8
 
 
 def _blocks(t, n):
@@ -56,10 +52,8 @@ class RunningStats:
         self.reset()
 
     def _after_alloc(self):
-        """contexts pinned to streams of their own: PyTorch's fill of a fresh array (on ITS stream) comes first"""
         for c in self.ctxs:
-            if getattr(c, "_pinned", False):
-                torch.cuda.current_stream(c.device).synchronize()
+            c.after_torch_fill()
 
     def reset(self):
         for S, c in zip(self.S, self.ctxs):
@@ -99,13 +93,9 @@ class RunningStats:
 
     def gathered(self, grid):
         """The record of the GLOBAL, halo-stripped statistics on the root (entries None elsewhere), gathered like the fields
-        (multi.jl:399-403): through ns3d_gather_f64 on the C-ABI grid, ZSlabGrid.gather otherwise."""
+        (multi.jl:399-403): grid.gather_fields."""
         fin = self.finalize()
         for c in self.ctxs:
             c.sync()
-        per_block = lambda which, n: [[_blocks(f[which], n)[q] for f in fin] for q in range(n)]
-        if hasattr(grid, "gather_fields"):
-            g = lambda lst: grid.gather_fields(lst)
-        else:
-            g = lambda lst: grid.gather(K.to_numpy(lst[0])[1:-1, 1:-1, 1:-1])
-        return self._record([g(lst) for lst in per_block(0, 4)], [g(lst) for lst in per_block(1, 7)])
+        per_block = lambda which, n: [grid.gather_fields([_blocks(f[which], n)[q] for f in fin]) for q in range(n)]
+        return self._record(per_block(0, 4), per_block(1, 7))

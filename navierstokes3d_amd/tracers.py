@@ -15,16 +15,10 @@ from . import kernels as K
 from . import lib as L
 
 
-def _pinned(ctx):
-    """the context launches on a stream of its own, whatever PyTorch's current stream is (use_torch_stream(pin=True), use_own_stream,
-    reserve_cus): nothing orders PyTorch's tensor work with its kernels"""
-    return ctx is not None and getattr(ctx, "_pinned", False)
-
-
 def _after_fill(ctx):
-    """a pinned context: PyTorch's fill of a fresh array (on ITS stream) comes first, as in stats.py"""
-    if _pinned(ctx):
-        torch.cuda.current_stream(ctx.device).synchronize()
+    """fresh or rewritten particle arrays: kernels.Context.after_torch_fill (ctx=None: the arrays are on the CPU)"""
+    if ctx is not None:
+        ctx.after_torch_fill()
 
 
 def _points(xyz):
@@ -87,7 +81,7 @@ class Tracers:
         """Put the physical points xyz (M,3) into DEAD slots only, lowest slots first; returns how many were placed
         (min(M, number of dead slots)).  Live particles and their order are untouched."""
         X = self.to_index(xyz)
-        if _pinned(self.ctx):
+        if self.ctx is not None and self.ctx._pinned:
             self.ctx.sync()             # an advance still queued on the context's own stream writes state and X
         dead = torch.nonzero(self.state == 0).flatten()
         k = min(int(dead.numel()), X.shape[1])

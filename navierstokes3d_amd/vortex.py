@@ -11,15 +11,13 @@ from . import kernels as K
 
 NAMES = ("Wx", "Wy", "Wz", "Q")
 
-_ESIZE = {torch.float64: 8, torch.float32: 4, np.float64: 8, np.float32: 4, "f64": 8, "f32": 4}
-
 
 def bytes_per_cell(dtype=torch.float64, n_out=4):
     """NOMINAL memory traffic of one ns3d_vortex call per cell, the accounting the rates are quoted in: one read of each velocity
     component and one write of each requested output, all of the element type — 56 / 28 bytes for fp64 / fp32 with all four."""
     if not 1 <= int(n_out) <= 4:
         raise ValueError("n_out = %r (1 … 4 outputs)" % (n_out,))
-    return (3 + int(n_out)) * _ESIZE[dtype]
+    return (3 + int(n_out)) * K.ESIZE[dtype]
 
 
 class VortexFields:
@@ -31,9 +29,8 @@ class VortexFields:
         self.ctxs = list(ctxs)
         self.spacings = tuple(float(q) for q in spacings)
         self.out = [SimpleNamespace(**{n: K.zeros(self.shape, dtype, torch.device("cuda", c.device)) for n in NAMES}) for c in self.ctxs]
-        for c in self.ctxs:         # contexts pinned to streams of their own: PyTorch's fill of a fresh array (on ITS stream) comes first
-            if getattr(c, "_pinned", False):
-                torch.cuda.current_stream(c.device).synchronize()
+        for c in self.ctxs:
+            c.after_torch_fill()
         self.n = 0                  # calls made so far
 
     def compute(self, fs):
@@ -49,12 +46,10 @@ class VortexFields:
 
     def gathered(self, grid):
         """The GLOBAL, halo-stripped fields on the root (entries None elsewhere), gathered like the flow's own fields
-        (multi.jl:399-403): through ns3d_gather_* on the C-ABI grid, ZSlabGrid.gather otherwise."""
+        (multi.jl:399-403): grid.gather_fields."""
         for c in self.ctxs:
             c.sync()
-        if hasattr(grid, "gather_fields"):
-            return SimpleNamespace(**{n: grid.gather_fields([getattr(o, n) for o in self.out]) for n in NAMES})
-        return SimpleNamespace(**{n: grid.gather(K.to_numpy(getattr(self.out[0], n))[1:-1, 1:-1, 1:-1]) for n in NAMES})
+        return SimpleNamespace(**{n: grid.gather_fields([getattr(o, n) for o in self.out]) for n in NAMES})
 
 
 def save_bins(rec, iframe, outdir="out_save"):
