@@ -159,6 +159,15 @@ int ns3d_set_graph_mode(ns3d_ctx *ctx, int mode);
  * such launches.  (NS3D_COOP_CHECK=1: the launch itself blocks, checks and fails with NS3D_ERR_HIP instead.)  Env NS3D_PT_PERSIST sets the default. */
 int ns3d_set_persist_mode(ns3d_ctx *ctx, int mode);
 int ns3d_persist_faults(const ns3d_ctx *ctx);
+/* Shape 29 of the N-iteration sweep (variant 29xx) is shape 28 whose workgroups re-align in z: the tiles of one XCD meet every pace_z
+ * z-steps at a bounded wait, so that the rows neighbouring tiles both read are still in that XCD's L2.  A hint — results never depend
+ * on it — used only when all workgroups of the launch are resident together (one z-chunk, no tile window, not during stream capture).
+ * ns3d_set_pt_pace: -1 automatic (the planner's value, grids from 3 M cells), 0 off, otherwise a multiple of 4.
+ * ns3d_last_pt_pace: the pace_z the latest N-iteration launch really used, 0 when it was not paced.
+ * ns3d_set_pt_pace_test (tests): raise every wait's target by extra_arrivals and bound it by `ticks` shader clocks (<= 0: the default). */
+int ns3d_set_pt_pace(ns3d_ctx *ctx, int pace_z);
+int ns3d_last_pt_pace(const ns3d_ctx *ctx);
+int ns3d_set_pt_pace_test(ns3d_ctx *ctx, int extra_arrivals, int ticks);
 int ns3d_cached_graphs(const ns3d_ctx *ctx);      /* residual-check blocks this context holds as instantiated HIP graphs */
 
 /* Parameters of the fused pseudo-transient path (ns3d_pt_iterate / ns3d_pt_solve). */

@@ -152,6 +152,7 @@ void ns3d_destroy(ns3d_ctx *c)
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     c->clear_graphs();
     if (c->persist.H) (void)hipFree(c->persist.H);
+    if (c->pace.ctr) (void)hipFree(c->pace.ctr);
     if (c->persist.err_host) (void)hipHostFree(c->persist.err_host);
     if (c->persist.ev) (void)hipEventDestroy(c->persist.ev);
     if (c->direct_plan && c->direct_free) c->direct_free(c->direct_plan);
@@ -280,6 +281,22 @@ int ns3d_set_ptn_variant(ns3d_ctx *c, int v)
 }
 
 int ns3d_persist_faults(const ns3d_ctx *c) { return c ? (int)c->persist.faults : -1; }
+int ns3d_last_pt_pace(const ns3d_ctx *c) { return c ? c->pace.last : -1; }
+int ns3d_set_pt_pace(ns3d_ctx *c, int pace_z)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_pt_pace: null context");
+    if (pace_z < -1 || (pace_z > 0 && pace_z % 4 != 0)) return fail(NS3D_ERR_ARG, "ns3d_set_pt_pace: %d z-steps (-1, 0 or a multiple of 4)", pace_z);
+    c->pace.pace_z = pace_z;
+    return NS3D_OK;
+}
+int ns3d_set_pt_pace_test(ns3d_ctx *c, int extra_arrivals, int ticks)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_pt_pace_test: null context");
+    if (extra_arrivals < 0) return fail(NS3D_ERR_ARG, "ns3d_set_pt_pace_test: %d extra arrivals", extra_arrivals);
+    c->pace.test_extra = extra_arrivals;
+    c->pace.ticks = ticks > 0 ? ticks : NS3D_PACE_TICKS_DEFAULT;
+    return NS3D_OK;
+}
 int ns3d_set_pt_depth(ns3d_ctx *c, int depth)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_pt_depth: null context");
@@ -507,7 +524,7 @@ static Plan tune_plan(ns3d_ctx *c, hipStream_t s, int mode, const T *src, T *dst
             if (rep == 1) ok = hipEventRecord(c->tune_ev[0], s) == hipSuccess;
             const int tf = ns3d_pass_flags_cus(c->reserved_cus);      // compute units the launch must not count on
             hipError_t e = depth == 2 ? DISPATCHM(mode, pt_sweep2<T>(s, v, src, dst, dsrc, ddst, divV, *p, k0, k1, tf))
-                                      : DISPATCHM(mode, pt_sweepn<T>(s, depth, v, src, dst, dsrc, ddst, divV, *p, k0, k1, tf));
+                                      : DISPATCHM(mode, pt_sweepn<T>(s, depth, v, src, dst, dsrc, ddst, divV, *p, k0, k1, tf, nullptr, &c->pace));
             ok = ok && e == hipSuccess;
         }
         ok = ok && hipEventRecord(c->tune_ev[1], s) == hipSuccess && hipEventSynchronize(c->tune_ev[1]) == hipSuccess &&
@@ -584,15 +601,18 @@ static Plan tune_plan(ns3d_ctx *c, hipStream_t s, int mode, const T *src, T *dst
         if (nk >= 16) {
             // 3800 (round 4): k_pt_sweepD, the planes of P⁰ through an LDS-DMA ring — what lets fp64 fit a 1024-thread 64×32 tile;
             // ties 2800 at 512³ (180 tiles for 256 CUs), so it has to win its place by 2 % like every later candidate
-            static const int cand4_f32[] = {2400, 2200, 1100, 0, 0}, cand4_f64[] = {2800, 2891, 2300, 2391, 3800};
+            // 12900 / 22900 / 42900: 2900 — 2800 with its XCD groups' tiles re-aligned every 32 / 64 / 128 z-steps (k_pt_sweepN's PACE);
+            // where the launch cannot be paced they are 2800 again and lose the 2 %
+            static const int cand4_f32[] = {2400, 2200, 1100, 0, 0, 0, 0, 0}, cand4_f64[] = {2800, 2891, 2300, 2391, 3800, 12900, 22900, 42900};
             const int *cand4 = sizeof(T) == 4 ? cand4_f32 : cand4_f64;
             const float cur_per_it = pl.depth == 3 ? best3 / 3.f : ms2 / 2.f;
             int best4v = 0;
             float best4 = 0.f;
-            for (int q4 = 0; q4 < 5; ++q4) {
+            for (int q4 = 0; q4 < 8; ++q4) {
                 const int v = cand4[q4];
                 if (v == 0) continue;
                 if (c->ptn_variant > 0 && v != c->ptn_variant) continue;
+                if (v >= 10000 && c->pace.pace_z >= 0) continue;      // the context's own pace_z (or none) overrides the plan's
                 if (!time_launch(4, v, ms)) continue;
                 if (best4 == 0.f || ms < 0.98f * best4) { best4 = ms; best4v = v; }
             }
@@ -652,8 +672,8 @@ static hipError_t launch_pass(ns3d_ctx *c, hipStream_t s, int depth, const Plan 
         c->last_pt2 = pl.v2;
         return DISPATCHM(mode, pt_sweep2<T>(s, pl.v2, src, dst, dsrc, ddst, divV, *p, k0, k1, flags, win));
     }
-    c->last_ptn = pl.vn;
-    return DISPATCHM(mode, pt_sweepn<T>(s, depth, pl.vn, src, dst, dsrc, ddst, divV, *p, k0, k1, flags, win));
+    c->last_ptn = pl.vn % 10000;                            // above: the planned pace_z of shape 29, in units of 32 z-steps
+    return DISPATCHM(mode, pt_sweepn<T>(s, depth, pl.vn, src, dst, dsrc, ddst, divV, *p, k0, k1, flags, win, &c->pace));
 }
 // iterations of the next pass when `rem` remain until the next residual check / the end
 static int next_depth(const Plan &pl, bool blocked, int rem)
@@ -697,7 +717,7 @@ int ns3d_plan_pt_internal(ns3d_ctx *c, const T *src, T *dst, const T *dsrc, T *d
                           int k0, int k1)
 {
     const Plan pl = pick_plan<T>(c, c->stream, mode_of(c, p->dx, p->dy, p->dz), src, dst, dsrc, ddst, divV, p, k0, k1, true);
-    c->last_pt2 = pl.v2; c->last_ptn = pl.vn; c->last_depth = pl.depth;
+    c->last_pt2 = pl.v2; c->last_ptn = pl.vn % 10000; c->last_depth = pl.depth;
     return pl.depth;
 }
 template <class T>

@@ -45,6 +45,7 @@ struct ns3d_ctx {
     };
     std::vector<BlockGraph> graphs;
     ns3d_persist_state persist;             // k_pt_persist's exchange area
+    ns3d_pt_pace pace;                      // k_pt_sweepN's PACE instance (shape 29): arrival counters, launch number, settings
     unsigned long long *diag_dev = nullptr;  // ns3d_diagnostics: NS3D_DIAG_RESULT_WORDS result / staging words, then the workgroups' partials
     size_t diag_words = 0;
     unsigned long long *diag_host = nullptr; // pinned mirror of the result / staging words

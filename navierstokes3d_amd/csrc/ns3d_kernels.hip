@@ -1551,8 +1551,16 @@ struct SweepArgs {
     int k0, k1; // interior planes [k0,k1) handled by this launch
     int kz;     // planes per block
     int tx0, ty0; // origin of the launch's tile window in the plane's tile grid (0, 0: the whole grid)
-    const ns3d_tile_window *win;  // host side only: the window asked for / the geometry query (ns3d_launch.h); nullptr: everything
-    int cus_off;  // host side only: compute units the stream's CU mask leaves out (ns3d_reserve_cus) — the z-chunking counts the rest
+    // Two fields the host alone reads.  A launch of k_pt_sweepN's PACE instance overwrites them in ITS kernel arguments with what the
+    // rendezvous needs, so that the struct — and with it every other kernel that takes it — stays what it was:
+    union {
+        const ns3d_tile_window *win;    // host: the window asked for / the geometry query (ns3d_launch.h); nullptr: everything
+        unsigned long long *pace_ctr;   // PACE launch: ns3d_pt_pace::ctr — four header words, then the counters [rendezvous][XCD group]
+    };
+    union {
+        int cus_off;                    // host: compute units the stream's CU mask leaves out (ns3d_reserve_cus) — the z-chunking counts the rest
+        unsigned pace_seq;              // PACE launch: its number since the counters were zeroed (a group waits for pace_seq × its workgroups); 0: no rendezvous
+    };
     int no_faces; // NS3D_PASS_SKIP_FACES: no k_pt_faces launch behind the sweep (a split pass completes the boundary cells itself: box_pass_overlapped)
 };
 // Every field of SweepArgs from the PT parameters, for the output planes [k0,k1), with the single-rank defaults: the whole tile grid,
@@ -2503,7 +2511,31 @@ static hipError_t launch_sweep2(hipStream_t s, SweepArgs<T> &a, int kz)
 // =========================================================================================================
 // PF: where the loads of the next step are issued — 0: between and after the levels; 1 (EARLY): before level 1.  (Loads two
 // steps ahead through a second set of staging registers were measured and dropped: no gain, 16 more registers.)
-template <class T, int NL, int WX, int WY, int CPT, int PF, int MINW = 1, bool FOLD = false>
+// PACE (shape 29): the workgroups of an XCD group (blockIdx & 7: they share an L2 and sweep neighbouring tiles) start together and
+// drift apart in z, so that the overlap rows one tile has fetched have left the 4 MB L2 when its neighbour asks for them.  Every
+// pace_z z-steps, on a trip boundary of the bulk loop, lane 0 of wave 0 adds 1 to the counter of (rendezvous, group) and polls it
+// until all workgroups of the group have arrived or pace_ticks shader clocks have passed; the other waves run on into the step and
+// meet wave 0 at its barrier.  Nothing is published through the counter (relaxed, no fence) and every workgroup arrives exactly
+// once per rendezvous whether it waits or not: a hint, the results cannot depend on it.  Needs all workgroups of the launch resident
+// together and marching the same plane range (launch_sweepN decides; pace_z == 0 otherwise).
+template <class T>
+__device__ __forceinline__ void pace_rendezvous(const SweepArgs<T> &a, int idx, int grp, int gsize)
+{
+    if ((unsigned)idx >= (unsigned)NS3D_PACE_SLOTS) return;
+    unsigned long long *ctr = a.pace_ctr + (NS3D_PACE_HEADER + idx * 8 + grp);
+    if (threadIdx.x == 0) {
+        __hip_atomic_fetch_add(ctr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned *hdr = (const unsigned *)a.pace_ctr;       // [0] pace_z, [1] bound in s_memtime ticks, [2] test offset of the target
+        const unsigned long long ticks = hdr[1];
+        const unsigned long long target = (unsigned long long)a.pace_seq * (unsigned long long)gsize + (unsigned long long)hdr[2];
+        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+            if (__builtin_amdgcn_s_memtime() - t0 > ticks) break;
+            __builtin_amdgcn_s_sleep(4);
+        }
+    }
+}
+template <class T, int NL, int WX, int WY, int CPT, int PF, int MINW = 1, bool FOLD = false, bool PACE = false>
 __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a, int ntx, int nty)
 {
     static_assert(NL >= 2 && NL <= 5, "levels");
@@ -2883,11 +2915,26 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
             step(s, std::true_type{});
             step(s + 1, std::true_type{});
         }
-        if (s == h0)
+        if (s == h0) {
+            if constexpr (PACE) {
+                // the trip that starts at h0 + n·pace_z (n ≥ 1) holds rendezvous n − 1; h0 and hot_hi are the same for every workgroup
+                // of a paced launch (one z-chunk)
+                const int pace_z = a.pace_seq != 0 ? (int)*(const unsigned *)a.pace_ctr : 0;      // header word 0
+                int left = pace_z > 0 ? pace_z : 0x40000000;
+                for (; s + UNR <= hot_hi; s += UNR) {
+                    if ((left -= UNR) < 0) {                  // wave-uniform
+                        left += pace_z;
+                        if (wy == 0) pace_rendezvous<T>(a, (s - h0) / pace_z - 1, xcd, q + (xcd < rem ? 1 : 0));
+                    }
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u) step(s + u, std::false_type{});
+                }
+            } else
             for (; s + UNR <= hot_hi; s += UNR) {
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) step(s + u, std::false_type{});
             }
+        }
     }
     for (; s < nsteps; ++s) step(s, std::true_type{});
     if constexpr (FOLD) {       // the boundary cells next to this tile's own output, instead of a k_pt_faces launch (fold_faces)
@@ -2897,8 +2944,8 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void k_pt_sweepN(SweepArgs<T> a
     }
 }
 
-template <class T, int NL, int WX, int WY, int CPT, int PF, int MINW = 1, bool FOLD = false>
-static hipError_t launch_sweepN(hipStream_t s, SweepArgs<T> &a, int kz)
+template <class T, int NL, int WX, int WY, int CPT, int PF, int MINW = 1, bool FOLD = false, bool PACE = false>
+static hipError_t launch_sweepN(hipStream_t s, SweepArgs<T> &a, int kz, ns3d_pt_pace *pc = nullptr, int pace_plan = 0)
 {
     constexpr int TX = 64 * WX, TY = CPT * WY, OV = 2 * (NL - 1);
     constexpr size_t lds = (2ul * (TY + 2) * (TX + 2) + 2ul * (NL - 1) * TY * TX) * sizeof(T) + 64;
@@ -2912,7 +2959,7 @@ static hipError_t launch_sweepN(hipStream_t s, SweepArgs<T> &a, int kz)
         // chunks per tile column that minimise the z-steps the slowest CU marches: rounds of workgroups × (planes per chunk + the
         // 2(NL−1) steps a chunk spends filling its pipeline) — the tail round of an unlucky tile count (1024²: 1026 tiles on 256
         // CUs) costs a whole chunk, so such grids want shorter chunks
-        static const int per_cu = workgroups_per_cu((const void *)k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD>, 64 * WX * WY);
+        static const int per_cu = workgroups_per_cu((const void *)k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD, PACE>, 64 * WX * WY);
         const long slots = (long)max(8, device_cus() - a.cus_off) * per_cu, tiles = (long)ntx * nty;
         const int cmax = max(1, nk / (6 * NL));
         long best_c = 1, best_cost = -1;
@@ -2924,7 +2971,7 @@ static hipError_t launch_sweepN(hipStream_t s, SweepArgs<T> &a, int kz)
         }
         kz = (int)((nk + best_c - 1) / best_c);
     } else if (kz > 90) {
-        static const int per_cu = workgroups_per_cu((const void *)k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD>, 64 * WX * WY);
+        static const int per_cu = workgroups_per_cu((const void *)k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD, PACE>, 64 * WX * WY);
         const long slots = (long)max(8, device_cus() - a.cus_off) * per_cu, tiles = (long)ntx * nty;
         const int want = kz - 90;
         const int cmax = max(1, nk / (6 * NL));              // short chunks are mostly pipeline fill (2(NL−1) steps each)
@@ -2943,8 +2990,59 @@ static hipError_t launch_sweepN(hipStream_t s, SweepArgs<T> &a, int kz)
     }
     a.kz = kz;
     const int ntz = (nk + kz - 1) / kz;
-    hipLaunchKernelGGL((k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX, WY, 1), 0, s, a,
+    const ns3d_tile_window *const win_host = a.win;     // a PACE launch carries the counters and its number in these two host-side fields
+    const int cus_off_host = a.cus_off;
+    if constexpr (PACE) {
+        // Paced only when every workgroup of the launch is resident together and marches the same planes: one z-chunk, no more
+        // workgroups than the CUs the launch may count on hold, the whole tile grid, and not while the stream is being captured (a
+        // replayed graph would keep the launch number of its capture).  pace_plan: the planner's value (variant / 10000 · 32), used
+        // while the context's setting is automatic and the launch has the cells of the planner's gate for deep passes.
+        int used = 0;
+        unsigned seq = 0;
+        if (pc) {
+            static const int per_cu = workgroups_per_cu((const void *)k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD, PACE>, 64 * WX * WY);
+            const long slots = (long)max(8, device_cus() - a.cus_off) * per_cu, wgs = (long)ntx * nty;
+            int pz = pc->pace_z;
+            if (pz < 0) pz = (long long)a.nx * a.ny * nk >= 3ll * 1000 * 1000 ? (pace_plan > 0 ? pace_plan : 64) : 0;
+            bool on = pz >= 4 && pz % 4 == 0 && ntz == 1 && wgs <= slots && !(a.win && a.win->x1 > a.win->x0) && nk + OV > pz;
+            if (on) {
+                hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+                if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); on = false; }
+                else if (cap != hipStreamCaptureStatusNone) on = false;
+            }
+            constexpr size_t words = NS3D_PACE_HEADER + 8ul * NS3D_PACE_SLOTS;
+            if (on && !pc->ctr) {
+                if (hipMalloc((void **)&pc->ctr, words * sizeof(unsigned long long)) != hipSuccess) {
+                    (void)hipGetLastError(); pc->ctr = nullptr; on = false;
+                }
+                pc->sig[5] = 0; pc->hdr[0] = pc->hdr[1] = pc->hdr[2] = -1;      // neither counters nor header written yet
+            }
+            if (on) {
+                // counters of another geometry are not multiples of this one's groups, and a 32-bit launch number ends: start again from
+                // zero.  Header words that changed are rewritten.  Both as fills on the launch's own stream: in order with the launches.
+                const int sig[8] = {a.nx, a.ny, a.nz, a.k0, a.k1, (int)wgs, NL * 1000 + (int)sizeof(T), pz};
+                if (std::memcmp(sig, pc->sig, sizeof sig) != 0 || pc->seq >= 0xfffffff0ull) {
+                    if (hipMemsetAsync(pc->ctr + NS3D_PACE_HEADER, 0, 8ul * NS3D_PACE_SLOTS * sizeof(unsigned long long), s) != hipSuccess) {
+                        (void)hipGetLastError(); on = false; pc->sig[5] = 0;
+                    } else { std::memcpy(pc->sig, sig, sizeof sig); pc->seq = 0; }
+                }
+                const int hdr[3] = {pz, pc->ticks < 1 ? 1 : pc->ticks, pc->test_extra};
+                for (int w = 0; w < 3 && on; ++w)
+                    if (hdr[w] != pc->hdr[w]) {
+                        if (hipMemsetD32Async((hipDeviceptr_t)((unsigned *)pc->ctr + w), hdr[w], 1, s) != hipSuccess) {
+                            (void)hipGetLastError(); on = false; pc->hdr[w] = -1;
+                        } else pc->hdr[w] = hdr[w];
+                    }
+            }
+            if (on) { seq = (unsigned)++pc->seq; used = pz; }
+            pc->last = used;
+        }
+        a.pace_ctr = pc ? pc->ctr : nullptr;
+        a.pace_seq = seq;
+    }
+    hipLaunchKernelGGL((k_pt_sweepN<T, NL, WX, WY, CPT, PF, MINW, FOLD, PACE>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX, WY, 1), 0, s, a,
                        ntx, nty);
+    a.win = win_host; a.cus_off = cus_off_host;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && !a.no_faces && !FOLD) e = launch_faces<T>(s, a);
     return e;
@@ -3348,7 +3446,7 @@ static hipError_t launch_sweepD(hipStream_t s, SweepArgs<T> &a, int kz)
 // rows per thread, one wave per SIMD, 64×20/64×24 with 256 threads, 64×48 with 1024 — are no longer instantiated.)
 template <class T>
 hipError_t pt_sweepn(hipStream_t s, int nlev, int variant, const T *Pin, T *Pout, const T *Din, T *Dout, const T *RHS,
-                     const ns3d_pt_params &p, int k0, int k1, int pass_flags, const ns3d_tile_window *win)
+                     const ns3d_pt_params &p, int k0, int k1, int pass_flags, const ns3d_tile_window *win, ns3d_pt_pace *pace)
 {
     SweepArgs<T> a = make_sweep_args<T>(p, Pin, Pout, Din, Dout, RHS, k0, k1);
     a.zlo_halo = a.zhi_halo = 0;
@@ -3356,6 +3454,10 @@ hipError_t pt_sweepn(hipStream_t s, int nlev, int variant, const T *Pin, T *Pout
     a.no_faces = (pass_flags & NS3D_PASS_SKIP_FACES) ? 1 : 0;
     a.cus_off = ns3d_pass_cus_off(pass_flags);
     if (k1 <= k0) return hipSuccess;
+    // variant / 10000: the planner's pace_z in units of 32 z-steps (shape 29 only)
+    const int pace_plan = (variant / 10000) * 32;
+    variant %= 10000;
+    if (pace) pace->last = 0;
     int shape = variant / 100, kz = variant % 100;
     // built-in: 64×32 columns, next step's loads issued before level 1 (measured best at 512³ for three levels); four levels
     // want three or four waves per SIMD: 64×24 columns with 768 threads in fp64 (loads between the levels: measured best once the
@@ -3374,6 +3476,7 @@ hipError_t pt_sweepn(hipStream_t s, int nlev, int variant, const T *Pin, T *Pout
     case 25: if constexpr (sizeof(T) == 4) { NS3D_SWN(NLV, 1, 16, 2, 2); } else return hipErrorInvalidValue;   /* fp32 A/B: shape 24 with the loads two steps ahead */ \
     case 28: if (fold_wanted<T>(a)) return launch_sweepN<T, NLV, 1, 12, 2, false, 1, true>(s, a, kz);       /* small grids: boundary cells folded in */ \
              NS3D_SWN(NLV, 1, 12, 2, false);                                                                \
+    case 29: return launch_sweepN<T, NLV, 1, 12, 2, false, 1, false, true>(s, a, kz, pace, pace_plan);            /* 28 with PACE: an XCD group's tiles meet every pace_z z-steps; never folded */ \
     case 11: NS3D_SWN(NLV, 1, 8, 4, true);                                                                  \
     case 12: NS3D_SWN(NLV, 2, 4, 4, true);                                                                  \
     default: return hipErrorInvalidValue;                                                                   \
@@ -4423,7 +4526,7 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
     template hipError_t pt_sweep2<T>(hipStream_t, int, const T *, T *, const T *, T *, const T *,            \
                                      const ns3d_pt_params &, int, int, int, const ns3d_tile_window *);       \
     template hipError_t pt_sweepn<T>(hipStream_t, int, int, const T *, T *, const T *, T *, const T *,       \
-                                     const ns3d_pt_params &, int, int, int, const ns3d_tile_window *);       \
+                                     const ns3d_pt_params &, int, int, int, const ns3d_tile_window *, ns3d_pt_pace *); \
     template hipError_t pt_faces_region<T>(hipStream_t, T *, const ns3d_pt_params &, const int *, const int *, int); \
     template hipError_t residual_max_key<T>(hipStream_t, const T *, const T *, const ns3d_pt_params &,       \
                                             unsigned long long *);                                           \

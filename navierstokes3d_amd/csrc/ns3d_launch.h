@@ -35,6 +35,23 @@ struct ns3d_persist_state {
     unsigned long long *red = nullptr;
     unsigned long long *res_host = nullptr, *res_host_dev = nullptr;
 };
+// Pacing of k_pt_sweepN's PACE instance (shape 29): the workgroups of one XCD group (blockIdx & 7) meet every pace_z z-steps at an arrival
+// counter per (rendezvous, group).  Counters only grow: launch number `seq` since they were last zeroed waits for seq × (workgroups of
+// the group).  A launch whose geometry differs from the one before zeroes them first, on its own stream.  A hint: waits are bounded and
+// no result depends on them.  Owned by a context, freed with it.
+#define NS3D_PACE_SLOTS 256            /* rendezvous per launch that have a counter; later ones are skipped */
+#define NS3D_PACE_HEADER 4             /* 64-bit words before the counters; 32-bit words 0…2: pace_z, the bound of a wait, the test offset */
+#define NS3D_PACE_TICKS_DEFAULT 65536  /* bound of one wait in s_memtime ticks: 14 µs, about five z-steps of the 512³ fp64 pass (profiles/pt_realign_ab.log) */
+struct ns3d_pt_pace {
+    unsigned long long *ctr = nullptr;  // device: NS3D_PACE_HEADER header words, then 8 × NS3D_PACE_SLOTS counters
+    int hdr[3] = {-1, -1, -1};          // what the header holds
+    unsigned long long seq = 0;         // paced launches since the counters were zeroed
+    int sig[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // geometry of those launches: nx, ny, nz, k0, k1, workgroups, levels·1000 + element size, pace_z
+    int pace_z = -1;                    // ns3d_set_pt_pace: −1 automatic (the plan's value, never below the planner's gate), 0 off, else z-steps
+    int ticks = NS3D_PACE_TICKS_DEFAULT;
+    int test_extra = 0;                 // test hook: arrivals the target is raised by, so that every wait expires
+    int last = 0;                       // pace_z of the latest N-iteration launch, 0: not paced
+};
 #define NS3D_PERSIST_MAXCHK 2048
 #define NS3D_PERSIST_MAXWG 1024        /* < MAXCHK: the workgroups' pairs, the result pair and the parameters share one block */
 
@@ -169,7 +186,8 @@ hipError_t emit(hipStream_t, const T *A, const T *B, const ns3d_iso_geom &, doub
                          const ns3d_pt_params &, int k0, int k1, int pass_flags, const ns3d_tile_window *win = nullptr); \
     template <class T>                                                                                       \
     hipError_t pt_sweepn(hipStream_t, int nlev, int variant, const T *, T *, const T *, T *, const T *,      \
-                         const ns3d_pt_params &, int k0, int k1, int pass_flags, const ns3d_tile_window *win = nullptr); \
+                         const ns3d_pt_params &, int k0, int k1, int pass_flags, const ns3d_tile_window *win = nullptr, \
+                         ns3d_pt_pace *pace = nullptr);                                                       \
     /* the boundary cells of Pout whose SOURCE cell (the interior cell they clamp onto) lies inside (want_core) or outside the  \
      * box [c0,c1) of cells: the partial boundary-cell launches of a split pass (box_pass_overlapped) */      \
     template <class T>                                                                                       \

@@ -182,6 +182,20 @@ class Context:
         """Tile shape of the N-iteration sweep (pt_sweepn): shape*100 + kz, 0 = built-in."""
         L.check(self.lib.ns3d_set_ptn_variant(self.handle, int(v)))
 
+    def set_pt_pace(self, pace_z):
+        """Shape 29 of the N-iteration sweep (variant 29xx): z-steps between the rendezvous of an XCD's tiles; -1 automatic (the
+        planner's value, large grids only), 0 off, otherwise a multiple of 4.  Same results."""
+        L.check(self.lib.ns3d_set_pt_pace(self.handle, int(pace_z)))
+
+    def last_pt_pace(self):
+        """The pace_z the latest N-iteration launch really used; 0: it was not paced."""
+        return int(self.lib.ns3d_last_pt_pace(self.handle))
+
+    def set_pt_pace_test(self, extra_arrivals, ticks):
+        """Tests: raise the target of every pacing wait by extra_arrivals (it then expires) and bound it by `ticks` shader clocks
+        (<= 0: the default bound)."""
+        L.check(self.lib.ns3d_set_pt_pace_test(self.handle, int(extra_arrivals), int(ticks)))
+
     def set_pt_depth(self, depth):
         """PT iterations per pass over memory in pt_iterate / pt_solve: 0 automatic, 1…4 forced (5: float32 fields only)."""
         L.check(self.lib.ns3d_set_pt_depth(self.handle, int(depth)))

@@ -111,6 +111,7 @@ CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destr
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
                    "ns3d_set_pt2_variant", "ns3d_set_ptn_variant", "ns3d_set_pt_depth", "ns3d_set_graph_mode", "ns3d_set_autotune", "ns3d_last_pt2_variant", "ns3d_last_ptn_variant", "ns3d_last_pt_depth",
                    "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
+                   "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test",
                    "ns3d_stats_reset", "ns3d_stats_finalize"]
 NS3D_STATS_SLOTS = 11
 
@@ -210,6 +211,12 @@ def load():
     lib.ns3d_set_persist_mode.restype = _I
     lib.ns3d_persist_faults.argtypes = [_P]
     lib.ns3d_persist_faults.restype = _I
+    lib.ns3d_set_pt_pace.argtypes = [_P, _I]
+    lib.ns3d_set_pt_pace.restype = _I
+    lib.ns3d_last_pt_pace.argtypes = [_P]
+    lib.ns3d_last_pt_pace.restype = _I
+    lib.ns3d_set_pt_pace_test.argtypes = [_P, _I, _I]
+    lib.ns3d_set_pt_pace_test.restype = _I
     lib.ns3d_cached_graphs.argtypes = [_P]
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
