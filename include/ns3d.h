@@ -32,7 +32,9 @@
  *        ns3d_diagnostics                       the record it returns              (none)
  *        ns3d_selftest_exact_div                the count it returns               (none)
  *        ns3d_isosurface                        the triangle count                 no: tri / val are enqueued behind the count
- *        ns3d_pt_solve                          every residual check               no: the copies into Pr / dPrdtau are enqueued
+ *        ns3d_tracers_migrate_mgpu              the counts of leavers and empty    no: pack, exchange and insert are enqueued behind them
+ *                                               slots of every rank
+ *        ns3d_pt_solve                          every residual check              no: the copies into Pr / dPrdtau are enqueued
  *        ns3d_time_step                         as ns3d_pt_solve (pressure 0);     no: the rest of the step is enqueued behind the solve;
  *                                               the whole step (pressure 1)        yes with pressure 1
  *        ns3d_pt_iterate                        the block, WHEN it runs as the     no: the copies into Pr / dPrdtau are enqueued
@@ -357,12 +359,35 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
      * NS3D_ERR_ARG, with every output untouched: a null context, X, field or `out`; a null `state` in the advance; n < 0 (n == 0 is \
      * a successful no-op); a grid below 3x3x3 resp. extents below 2 in the sample; a stagger flag other than 0 or 1; a Courant \
      * factor that is not finite.                                                                                         \
-     * There is NO ns3d_mgpu form: a particle that crosses a seam between ranks has to migrate to its neighbour, and that is a \
-     * design of its own.  Positions are local to the arrays passed in. */                                                \
+     * Positions are local to the arrays passed in: these two calls know one rank.  On a decomposed grid a particle that crosses a \
+     * seam between ranks has to migrate to its neighbour — the _at forms below and the two ns3d_mgpu calls further down are that \
+     * design. */                                                                                                         \
     int ns3d_sample_##S(ns3d_ctx *, double *out, const double *X, const unsigned char *state, long n, const T *A, \
                         int ex, int ey, int ez, int stag_x, int stag_y, int stag_z);                          \
     int ns3d_tracers_advance_##S(ns3d_ctx *, double *X, unsigned char *state, double *U, long n, const T *Vx, \
                                  const T *Vy, const T *Vz, double cx, double cy, double cz, int nx, int ny, int nz); \
+    /* The ORIGIN forms, for the ranks of a decomposed grid.  X is in the GLOBAL index space of the cell grid \
+     * n_g[q] = dims[q]*(n[q]-2)+2, whatever rank holds the particle; the rank with coordinates co has origin[q] = co[q]*(n[q]-2) and \
+     * interpolates at p_q = X_q - (double)origin_q — exact for 0 <= origin <= X, so the local node is the global one minus origin \
+     * and the weights have the same bits — with the same I as above.                                                       \
+     * ns3d_sample_at_*: the sample call evaluated at X - origin; the inside test is the local one, 0 <= p_q <= e_q - stag_q, NaN \
+     *   otherwise.  origin NULL means zeros, and then the call returns the bits of the one-rank form.                      \
+     * ns3d_tracers_advance_at_*: the advance with its "inside the closed box" tests taken on the GLOBAL box [0, n_g] and the  \
+     *   interpolation at X - origin (the midpoint too); Xn, U and the state are stored as above.  origin / n_g NULL mean zeros \
+     *   resp. (nx,ny,nz), and then the call returns the bits of the one-rank form.  A live particle the rank does not own is the \
+     *   caller's mistake: it is advanced with the clamped interpolation.                                                   \
+     * OWNERSHIP, per direction with D = dims[q], n = n[q]: rank coordinate k owns k(n-2)+1 <= X_q < (k+1)(n-2)+1, k = 0 from 0 and \
+     * k = D-1 up to n_g inclusive: a partition of the closed global box, decided by comparisons.                          \
+     * GUARANTEE (of the form of the wide advection's |dz| < 2 cells): with halos that agree with the global field, P ranks \
+     * reproduce the one-rank step bit for bit in X, state and U while every active particle's first-stage Courant number \
+     * |v1_q*c_q| is below 1 in the decomposed directions (undecomposed directions are unrestricted).  Beyond that the midpoint is \
+     * clamped to the local array, as backtrack! clamps.  No address outside the arrays is ever read.                      \
+     * NS3D_ERR_ARG as for the one-rank forms, and for origin_q < 0 or n_g[q] < origin_q + n_q. */                         \
+    int ns3d_sample_at_##S(ns3d_ctx *, double *out, const double *X, const unsigned char *state, long n, const T *A, \
+                           int ex, int ey, int ez, int stag_x, int stag_y, int stag_z, const int *origin);        \
+    int ns3d_tracers_advance_at_##S(ns3d_ctx *, double *X, unsigned char *state, double *U, long n, const T *Vx, \
+                                    const T *Vy, const T *Vz, double cx, double cy, double cz, int nx, int ny, int nz, \
+                                    const int *origin, const int *n_g);                                        \
     /* Isosurface: the triangles of the level set A = iso, extracted and compacted on the device — what one looks at instead of the field.  \
      * A is any packed column-major array of extents (ex,ey,ez), each >= 2; its entries are NODES at the integer positions (i,j,k) (the     \
      * caller knows where they sit physically: stagger and spacings are applied by the caller).  B (may be NULL) is a second array of the   \
@@ -633,6 +658,22 @@ int ns3d_mgpu_ghost_depth(const ns3d_mgpu *m);
 int ns3d_slab_iterate(ns3d_mgpu *m, int n_iters);
 int ns3d_slab_plan(ns3d_mgpu *m);
 int ns3d_slab_residual(ns3d_mgpu *m, double *out);
+/* Tracers on a decomposed grid, second half: after the advance on every rank, ns3d_tracers_advance_mgpu below, every particle that left its rank's part of
+ * the global box travels to its owner (the ownership rule is with ns3d_tracers_advance_at).  No element type: no field is touched.
+ * Each local rank l has cap[l] SLOTS: X[l] three blocks of cap[l] doubles, state[l] one byte per slot, id[l] one long long per slot
+ * (>= 0 occupied, -1 empty), U[l] (the list may be NULL) three blocks of payload carried along.  A LEAVER is an occupied slot with
+ * state 1 and finite coordinates whose owner is another rank; dead particles never move (they record where they left).  A leaver's
+ * slot becomes empty: id -1, state 0, its X and U entries NaN.  The arrivals at a rank are ordered by source rank ascending and
+ * within a source by slot ascending, and go into that rank's empty slots in ascending slot order, the slots vacated in this call
+ * included.  Count, scan, compact: no atomic decides a position, two calls on the same input give the same arrays.
+ * *moved_host receives the number of particles moved.  If some rank has fewer empty slots than arrivals NOTHING is modified on any
+ * rank, need_host[l] is the shortfall of local rank l (0 where there is room), *moved_host is 0 and the call returns NS3D_ERR_STATE:
+ * the rule is a pure function of the positions, so the caller enlarges its arrays and calls again.  Blocks for the counts like
+ * ns3d_diagnostics_mgpu.  One-process form only (peer copies, virtual ranks on one device included); in the one-process-per-GPU
+ * form the call returns NS3D_ERR_STATE.  NS3D_ERR_ARG, nothing touched: a null list or output, cap[l] < 0, a null array of a rank
+ * with cap[l] > 0 (a rank with cap[l] = 0 is fine). */
+int ns3d_tracers_migrate_mgpu(ns3d_mgpu *m, double *const *X, unsigned char *const *state, long long *const *id, double *const *U,
+                              const long *cap, long long *moved_host, long *need_host);
 
 #define NS3D_MGPU_DECL(T, S)                                                                                \
     /* extents: 3 ints (sx,sy,sz) per field */                                                              \
@@ -675,7 +716,13 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out);
      * one-process-per-GPU form (every process receives the global record).  Pr or C may be NULL (as a list).  Blocks. */      \
     int ns3d_diagnostics_mgpu_##S(ns3d_mgpu *m, const T *const *Vx, const T *const *Vy, const T *const *Vz,  \
                                   const T *const *Pr, const T *const *C, const ns3d_diag_params *per_rank,   \
-                                  ns3d_diag *out_global, ns3d_diag *out_local);
+                                  ns3d_diag *out_global, ns3d_diag *out_local);                              \
+    /* Tracers on a decomposed grid, first half: ns3d_tracers_advance_at on every local rank's context with that rank's origin and \
+     * the grid's n_g; cap[l] slots per rank (empty and dead slots are inactive particles), U may be NULL.  Both transports.  \
+     * Enqueues; blocks only as every mgpu call does without NS3D_ASYNC.  Everything is checked before the first launch. */  \
+    int ns3d_tracers_advance_mgpu_##S(ns3d_mgpu *m, double *const *X, unsigned char *const *state, double *const *U, \
+                                      const long *cap, T *const *Vx, T *const *Vy, T *const *Vz, double cx, double cy, \
+                                      double cz);
 NS3D_MGPU_DECL(double, f64)
 NS3D_MGPU_DECL(float, f32)
 #undef NS3D_MGPU_DECL

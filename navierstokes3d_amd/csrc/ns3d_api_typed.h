@@ -137,6 +137,45 @@ extern "C" int NS3D_FN(tracers_advance)(ns3d_ctx *c, double *X, unsigned char *s
     if (n == 0) return NS3D_OK;
     return finish(c, ns3d_tracers::advance<T>(c->stream, X, state, U, n, Vx, Vy, Vz, cx, cy, cz, nx, ny, nz), "tracers_advance");
 }
+// the origin forms for the ranks of a decomposed grid: positions in the global index space, interpolation at X - origin
+extern "C" int NS3D_FN(sample_at)(ns3d_ctx *c, double *out, const double *X, const unsigned char *state, long n, const T *A, int ex, int ey,
+                                  int ez, int stag_x, int stag_y, int stag_z, const int *origin)
+{
+    CHECK_CTX(c); CHECK_PTRS(out, X, A);
+    const int rc = tracers_count_check(n, __func__);
+    if (rc) return rc;
+    if (ex < 2 || ey < 2 || ez < 2) return fail(NS3D_ERR_ARG, "%s: extents %dx%dx%d too small (need >= 2 per direction)", __func__, ex, ey, ez);
+    if ((stag_x | stag_y | stag_z) & ~1)
+        return fail(NS3D_ERR_ARG, "%s: stagger flags %d, %d, %d (each 0 or 1)", __func__, stag_x, stag_y, stag_z);
+    const int zero[3] = {0, 0, 0};
+    const int *o = origin ? origin : zero;
+    if (o[0] < 0 || o[1] < 0 || o[2] < 0) return fail(NS3D_ERR_ARG, "%s: origin %d, %d, %d (each >= 0)", __func__, o[0], o[1], o[2]);
+    if (n == 0) return NS3D_OK;
+    return finish(c, ns3d_tracers::sample_at<T>(c->stream, out, X, state, n, A, ex, ey, ez, stag_x, stag_y, stag_z, o), "sample_at");
+}
+extern "C" int NS3D_FN(tracers_advance_at)(ns3d_ctx *c, double *X, unsigned char *state, double *U, long n, const T *Vx, const T *Vy,
+                                           const T *Vz, double cx, double cy, double cz, int nx, int ny, int nz, const int *origin,
+                                           const int *n_g)
+{
+    CHECK_CTX(c); CHECK_PTRS(X, state, Vx, Vy, Vz);
+    const int rc = tracers_count_check(n, __func__);
+    if (rc) return rc;
+    CHECK_GRID(nx, ny, nz, 3);
+    if (!(std::isfinite(cx) && std::isfinite(cy) && std::isfinite(cz)))
+        return fail(NS3D_ERR_ARG, "%s: Courant factors %g, %g, %g (need finite values)", __func__, cx, cy, cz);
+    const int zero[3] = {0, 0, 0}, loc[3] = {nx, ny, nz};
+    const int *o = origin ? origin : zero;
+    if (o[0] < 0 || o[1] < 0 || o[2] < 0) return fail(NS3D_ERR_ARG, "%s: origin %d, %d, %d (each >= 0)", __func__, o[0], o[1], o[2]);
+    int g[3];
+    for (int q = 0; q < 3; ++q) {
+        g[q] = n_g ? n_g[q] : loc[q];
+        if ((long)g[q] < (long)o[q] + loc[q])
+            return fail(NS3D_ERR_ARG, "%s: global grid %d in direction %d is smaller than origin %d + local grid %d", __func__, g[q], q, o[q],
+                        loc[q]);
+    }
+    if (n == 0) return NS3D_OK;
+    return finish(c, ns3d_tracers::advance_at<T>(c->stream, X, state, U, n, Vx, Vy, Vz, cx, cy, cz, nx, ny, nz, o, g), "tracers_advance_at");
+}
 // ns3d_isosurface: count, scan and read the total back (blocking); then, where there is room for triangles, the emit launch
 extern "C" int NS3D_FN(isosurface)(ns3d_ctx *c, const T *A, const T *B, int ex, int ey, int ez, const int *box, const int *origin, double iso,
                                    double *tri, double *val, long long cap, long long *n_tri_host)

@@ -193,6 +193,24 @@ hipError_t ns3d_direct_unpack(hipStream_t s, const double *src, double *dst, int
 
 // ---- ns3d_tracers.hip: ns3d_sample / ns3d_tracers_advance.  One compilation without contraction serves every arithmetic mode (the
 // entry points' contract: the same bits from STRICT, NS3D_IEEE_DIV and FAST contexts).  n > 0; state (sample) and U (advance) may be null.
+// The _at forms take positions in the GLOBAL index space of a decomposed grid: origin (3 ints, not null) is the rank's first cell,
+// n_g (3 ints, not null) the global cell grid of the advance's "inside" tests.
+// ns3d_tracers_migrate_mgpu's routing (ns3d_mgpu.cpp drives it): mig_count classifies a rank's slots and leaves the per-workgroup
+// counts, their prefix sums and the P+1 totals in the scratch; mig_pack moves the leavers into records and empties their slots;
+// mig_insert puts received records into the empty slots.
+#define NS3D_MIG_REC 8             // doubles per travelling particle: x, y, z, the id's bits, u, v, w, unused
+struct ns3d_mig_geom {
+    int dims[3], n[3];             // topology and local cell grid
+    double inv[3];                 // 1/(n−2): the owner's first estimate (comparisons decide)
+    int me, P;
+};
+struct ns3d_mig_scratch {          // device scratch of one rank and one call, carved out of the rank's buffer; nwg = ceil(cap/256)
+    int *dest, *code;              // per slot
+    unsigned *counts;              // (P+1) rows × nwg
+    unsigned long long *offs;      // (P+1) rows × nwg
+    unsigned long long *totals;    // P+1
+    unsigned long long *dbase;     // P: where the records for each destination start in the send buffer
+};
 namespace ns3d_tracers {
 template <class T>
 hipError_t sample(hipStream_t s, double *out, const double *X, const unsigned char *state, long n, const T *A, int ex, int ey, int ez,
@@ -200,4 +218,16 @@ hipError_t sample(hipStream_t s, double *out, const double *X, const unsigned ch
 template <class T>
 hipError_t advance(hipStream_t s, double *X, unsigned char *state, double *U, long n, const T *Vx, const T *Vy, const T *Vz, double cx,
                    double cy, double cz, int nx, int ny, int nz);
+template <class T>
+hipError_t sample_at(hipStream_t s, double *out, const double *X, const unsigned char *state, long n, const T *A, int ex, int ey, int ez,
+                     int stag_x, int stag_y, int stag_z, const int *origin);
+template <class T>
+hipError_t advance_at(hipStream_t s, double *X, unsigned char *state, double *U, long n, const T *Vx, const T *Vy, const T *Vz, double cx,
+                      double cy, double cz, int nx, int ny, int nz, const int *origin, const int *n_g);
+hipError_t mig_count(hipStream_t s, const ns3d_mig_scratch &w, const double *X, const unsigned char *state, const long long *id, long cap,
+                     const ns3d_mig_geom &g);
+hipError_t mig_pack(hipStream_t s, const ns3d_mig_scratch &w, double *rec, double *X, unsigned char *state, long long *id, double *U,
+                    long cap);
+hipError_t mig_insert(hipStream_t s, const ns3d_mig_scratch &w, int P, const double *rec, long n_arr, double *X, unsigned char *state,
+                      long long *id, double *U, long cap);
 }

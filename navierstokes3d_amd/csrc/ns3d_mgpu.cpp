@@ -132,6 +132,11 @@ struct MRank {
     void *wbuf = nullptr;                          // advect_wide: the four old and four new fields, one plane wider per seam
     size_t wbuf_bytes = 0;
     DirectSlab ds;                                 // ns3d_poisson_direct_slab: eigenbases and transposed scratch
+    void *tbuf = nullptr;                          // ns3d_tracers_migrate_mgpu: per-slot codes, per-workgroup counts and offsets, totals
+    size_t tbuf_bytes = 0;
+    void *tsend = nullptr, *trecv = nullptr;       // … the leavers' records by destination, the arrivals' by source
+    size_t tsend_bytes = 0, trecv_bytes = 0;
+    unsigned long long *thost = nullptr;           // … pinned: P+1 totals read back, then P send-buffer bases uploaded
 };
 struct Block {                    // one contiguous piece that travels to both neighbours (pointers on the owning rank)
     void *send_lo, *recv_lo, *send_hi, *recv_hi;
@@ -1526,9 +1531,165 @@ int diag_mgpu(ns3d_mgpu *m, const T *const *Vx, const T *const *Vy, const T *con
     return NS3D_OK;
 }
 
+// ---- tracers on a decomposed grid ----------------------------------------------------------------------------------------
+inline int advance_at(ns3d_ctx *c, double *X, unsigned char *st, double *U, long n, const double *Vx, const double *Vy, const double *Vz,
+                      double cx, double cy, double cz, int nx, int ny, int nz, const int *o, const int *g)
+{
+    return ns3d_tracers_advance_at_f64(c, X, st, U, n, Vx, Vy, Vz, cx, cy, cz, nx, ny, nz, o, g);
+}
+inline int advance_at(ns3d_ctx *c, double *X, unsigned char *st, double *U, long n, const float *Vx, const float *Vy, const float *Vz,
+                      double cx, double cy, double cz, int nx, int ny, int nz, const int *o, const int *g)
+{
+    return ns3d_tracers_advance_at_f32(c, X, st, U, n, Vx, Vy, Vz, cx, cy, cz, nx, ny, nz, o, g);
+}
+const long TRACERS_MAX = 256L * 0x7fffffffL;      // one launch
+
+// ns3d_tracers_advance_at on every local rank with its origin and the grid's n_g; everything is checked before the first launch
+template <class T>
+int tracers_advance_all(ns3d_mgpu *m, double *const *X, unsigned char *const *state, double *const *U, const long *cap, T *const *Vx,
+                        T *const *Vy, T *const *Vz, double cx, double cy, double cz)
+{
+    const char *fn = "ns3d_tracers_advance_mgpu";
+    const int n = (int)m->loc.size();
+    if (!(std::isfinite(cx) && std::isfinite(cy) && std::isfinite(cz)))
+        return fail(NS3D_ERR_ARG, "%s: Courant factors %g, %g, %g (need finite values)", fn, cx, cy, cz);
+    for (int l = 0; l < n; ++l) {
+        if (cap[l] < 0 || cap[l] > TRACERS_MAX) return fail(NS3D_ERR_ARG, "%s: cap = %ld (local rank %d)", fn, cap[l], l);
+        if (!Vx[l] || !Vy[l] || !Vz[l]) return fail(NS3D_ERR_ARG, "%s: null field pointer (local rank %d)", fn, l);
+        if (cap[l] > 0 && (!X[l] || !state[l] || (U && !U[l]))) return fail(NS3D_ERR_ARG, "%s: null particle array (local rank %d)", fn, l);
+    }
+    const int loc[3] = {m->nx, m->ny, m->nz};
+    int n_g[3];
+    for (int q = 0; q < 3; ++q) n_g[q] = m->dims[q] * (loc[q] - 2) + 2;
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        if (cap[l] == 0) continue;
+        int o[3];
+        for (int q = 0; q < 3; ++q) o[q] = r.coords[q] * (loc[q] - 2);
+        const int rc = advance_at(r.ctx, X[l], state[l], U ? U[l] : nullptr, cap[l], Vx[l], Vy[l], Vz[l], cx, cy, cz, m->nx, m->ny, m->nz, o,
+                                  n_g);
+        if (rc) return rc;
+    }
+    return NS3D_OK;
+}
+
+// a rank's scratch buffer, at least `need` bytes: grown behind everything its streams hold
+int grow_buffer(MRank &r, void *&buf, size_t &have, size_t need)
+{
+    if (have >= need && buf) return NS3D_OK;
+    if (buf) {
+        HIPCHK(0, hipStreamSynchronize(compute(r)));
+        HIPCHK(0, hipStreamSynchronize(r.comm));
+        HIPCHK(0, hipFree(buf));
+        buf = nullptr; have = 0;
+    }
+    if (need < 256) need = 256;
+    HIPCHK(0, hipMalloc(&buf, need));
+    have = need;
+    return NS3D_OK;
+}
+
+// ns3d_tracers_migrate_mgpu (one-process form: local index == rank).  Count on every rank, read the (P+1)·P totals back, decide on
+// the host whether every rank has room; only then pack, exchange (alltoall: the receivers pull) and insert.
+int tracers_migrate(ns3d_mgpu *m, double *const *X, unsigned char *const *state, long long *const *id, double *const *U, const long *cap,
+                    long long *moved_host, long *need_host)
+{
+    const char *fn = "ns3d_tracers_migrate_mgpu";
+    const int n = (int)m->loc.size(), P = m->P;
+    for (int l = 0; l < n; ++l) {
+        if (cap[l] < 0 || cap[l] > TRACERS_MAX) return fail(NS3D_ERR_ARG, "%s: cap = %ld (local rank %d)", fn, cap[l], l);
+        if (cap[l] > 0 && (!X[l] || !state[l] || !id[l] || (U && !U[l])))
+            return fail(NS3D_ERR_ARG, "%s: null particle array (local rank %d)", fn, l);
+    }
+    std::vector<ns3d_mig_scratch> ws(n);
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        const size_t nwg = (size_t)((cap[l] + 255) / 256), rows = (size_t)P + 1;
+        const size_t words = rows + (size_t)P + rows * nwg;                        // 8-byte entries: totals, dbase, offs
+        const size_t bytes = words * 8 + rows * nwg * sizeof(unsigned) + 2 * (size_t)cap[l] * sizeof(int);
+        int rc = grow_buffer(r, r.tbuf, r.tbuf_bytes, bytes);
+        if (rc) return rc;
+        if (!r.thost) HIPCHK(0, hipHostMalloc((void **)&r.thost, (2 * (size_t)P + 1) * sizeof(unsigned long long)));
+        ns3d_mig_scratch &w = ws[l];
+        w.totals = (unsigned long long *)r.tbuf;
+        w.dbase = w.totals + rows;
+        w.offs = w.dbase + P;
+        w.counts = (unsigned *)(w.offs + rows * nwg);
+        w.dest = (int *)(w.counts + rows * nwg);
+        w.code = w.dest + cap[l];
+        ns3d_mig_geom geo;
+        const int loc[3] = {m->nx, m->ny, m->nz};
+        for (int q = 0; q < 3; ++q) { geo.dims[q] = m->dims[q]; geo.n[q] = loc[q]; geo.inv[q] = 1.0 / (double)(loc[q] - 2); }
+        geo.me = r.rank; geo.P = P;
+        hipError_t e = ns3d_tracers::mig_count(compute(r), w, X[l], state[l], id[l], cap[l], geo);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "%s: count launch: %s", fn, hipGetErrorString(e)); }
+        HIPCHK(0, hipMemcpyAsync(r.thost, w.totals, rows * sizeof(unsigned long long), hipMemcpyDeviceToHost, compute(r)));
+    }
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        HIPCHK(0, hipStreamSynchronize(compute(r)));
+    }
+    std::vector<unsigned long long> arrivals(n, 0ull), leavers(n, 0ull);
+    for (int s = 0; s < n; ++s)
+        for (int d = 0; d < P; ++d) { arrivals[d] += m->loc[s].thost[d]; leavers[s] += m->loc[s].thost[d]; }
+    bool is_short = false;
+    long long moved = 0;
+    for (int l = 0; l < n; ++l) {
+        const unsigned long long room = m->loc[l].thost[P];
+        need_host[l] = arrivals[l] > room ? (long)(arrivals[l] - room) : 0;
+        is_short = is_short || need_host[l] > 0;
+        moved += (long long)leavers[l];
+    }
+    if (is_short) {
+        *moved_host = 0;
+        return fail(NS3D_ERR_STATE, "%s: a rank has fewer empty slots than arrivals (need_host has the shortfalls); nothing was moved", fn);
+    }
+    *moved_host = moved;
+    if (moved == 0) return NS3D_OK;
+    const size_t rec_bytes = NS3D_MIG_REC * sizeof(double);
+    std::vector<std::vector<Piece>> send(n, std::vector<Piece>(n)), recv(n, std::vector<Piece>(n));
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        int rc = grow_buffer(r, r.tsend, r.tsend_bytes, (size_t)leavers[l] * rec_bytes);
+        if (rc) return rc;
+        rc = grow_buffer(r, r.trecv, r.trecv_bytes, (size_t)arrivals[l] * rec_bytes);
+        if (rc) return rc;
+    }
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        ns3d_device_guard g(r.device);
+        unsigned long long *base = r.thost + P + 1, run = 0ull, from = 0ull;
+        for (int d = 0; d < P; ++d) {
+            base[d] = run;
+            send[l][d] = Piece{(char *)r.tsend + run * rec_bytes, (size_t)r.thost[d] * rec_bytes};
+            run += r.thost[d];
+            recv[l][d] = Piece{(char *)r.trecv + from * rec_bytes, (size_t)m->loc[d].thost[l] * rec_bytes};
+            from += m->loc[d].thost[l];
+        }
+        if (leavers[l] == 0) continue;
+        HIPCHK(0, hipMemcpyAsync(ws[l].dbase, base, (size_t)P * sizeof(unsigned long long), hipMemcpyHostToDevice, compute(r)));
+        hipError_t e = ns3d_tracers::mig_pack(compute(r), ws[l], (double *)r.tsend, X[l], state[l], id[l], U ? U[l] : nullptr, cap[l]);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "%s: pack launch: %s", fn, hipGetErrorString(e)); }
+    }
+    int rc = alltoall(m, send, recv);
+    if (rc) return rc;
+    for (int l = 0; l < n; ++l) {
+        MRank &r = m->loc[l];
+        if (arrivals[l] == 0) continue;
+        ns3d_device_guard g(r.device);
+        hipError_t e = ns3d_tracers::mig_insert(compute(r), ws[l], P, (const double *)r.trecv, (long)arrivals[l], X[l], state[l], id[l],
+                                                U ? U[l] : nullptr, cap[l]);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "%s: insert launch: %s", fn, hipGetErrorString(e)); }
+    }
+    return NS3D_OK;
+}
+
 } // namespace
 
-#define CHECK_M(m)                                                                                          \
+#define CHECK_M(m)                                                                                         \
     do {                                                                                                    \
         if (!(m)) return fail(NS3D_ERR_ARG, "%s: null ns3d_mgpu", __func__);                                \
     } while (0)
@@ -1679,6 +1840,10 @@ void ns3d_mgpu_destroy(ns3d_mgpu *m)
         if (r.cbuf) (void)hipFree(r.cbuf);
         if (r.bbuf) (void)hipFree(r.bbuf);
         if (r.wbuf) (void)hipFree(r.wbuf);
+        if (r.tbuf) (void)hipFree(r.tbuf);
+        if (r.tsend) (void)hipFree(r.tsend);
+        if (r.trecv) (void)hipFree(r.trecv);
+        if (r.thost) (void)hipHostFree(r.thost);
         if (r.ev_ready) (void)hipEventDestroy(r.ev_ready);
         if (r.ev_landed) (void)hipEventDestroy(r.ev_landed);
         if (r.ev_pass) (void)hipEventDestroy(r.ev_pass);
@@ -1812,9 +1977,31 @@ int ns3d_slab_residual(ns3d_mgpu *m, double *out)
     return m->esize == 8 ? deep_residual<double>(m, out) : deep_residual<float>(m, out);
 }
 
+// particles whose owner is another rank travel there (include/ns3d.h has the rule and the order)
+int ns3d_tracers_migrate_mgpu(ns3d_mgpu *m, double *const *X, unsigned char *const *state, long long *const *id, double *const *U,
+                              const long *cap, long long *moved_host, long *need_host)
+{
+    CHECK_M(m);
+    if (!X || !state || !id || !cap || !moved_host || !need_host) return fail(NS3D_ERR_ARG, "ns3d_tracers_migrate_mgpu: null argument");
+    if (m->rccl)
+        return fail(NS3D_ERR_STATE, "ns3d_tracers_migrate_mgpu: particles migrate in the one-process form only (peer copies between the "
+                                    "ranks of ns3d_mgpu_create); this grid is in the one-process-per-GPU (RCCL) form");
+    int rc = tracers_migrate(m, X, state, id, U, cap, moved_host, need_host);
+    return rc ? rc : finish_m(m);
+}
+
 } // extern "C"
 
 #define NS3D_MGPU_DEFINE(T, S)                                                                               \
+    extern "C" int ns3d_tracers_advance_mgpu_##S(ns3d_mgpu *m, double *const *X, unsigned char *const *state, double *const *U, \
+                                                 const long *cap, T *const *Vx, T *const *Vy, T *const *Vz, double cx, double cy, \
+                                                 double cz)                                                  \
+    {                                                                                                        \
+        CHECK_M(m);                                                                                          \
+        if (!X || !state || !cap || !Vx || !Vy || !Vz) return fail(NS3D_ERR_ARG, "ns3d_tracers_advance_mgpu: null argument"); \
+        int rc = tracers_advance_all<T>(m, X, state, U, cap, Vx, Vy, Vz, cx, cy, cz);                        \
+        return rc ? rc : finish_m(m);                                                                        \
+    }                                                                                                        \
     extern "C" int ns3d_update_halo_##S(ns3d_mgpu *m, T *const *fields, const int *extents, int nfields)     \
     {                                                                                                        \
         CHECK_M(m);                                                                                          \

@@ -236,9 +236,12 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     probes=… (default None): an (M,3) array of physical points at which u, v, w, p are sampled at the end of every step (four
     ns3d_sample calls; the series stay on the device and are read back ONCE, after the last step): info.probes gets u, v, w, p
     of shape (nt, M), NaN for a point outside the box.
-    Both are read-only with respect to the flow — every other result keeps its bits — and leave `one_call` in use.  ONE RANK
-    only: on more than one rank either keyword raises Ns3dError, because a particle that crosses a seam has to migrate to the
-    neighbouring rank and there is no ns3d_mgpu form of these calls yet.
+    Both are read-only with respect to the flow — every other result keeps its bits — and leave `one_call` in use.  As a number
+    or an array they run on ONE RANK only: on more than one rank either keyword then raises Ns3dError, because a particle that
+    crosses a seam has to migrate to the neighbouring rank.  For that, both keywords also take a READY OBJECT, used as it is:
+    tracers.MgpuTracers / tracers.MgpuProbes built on this run's mgpu.MgpuGrid (one-process form; every local rank's fields are
+    passed to them, particles migrate after each step, info.tracers is ordered by id and info.probes by point, so both compare
+    with a one-rank run) — or a ready tracers.Tracers / tracers.Probes on one rank.
     isosurface=… (default None: not one extra call, file or attribute): a triangle surface of the final state, after the last
     step's halo update (ns3d_isosurface, on the device, on every local rank's context; isosurface.extract).  A float q means the
     Q-criterion at level q, uncoloured; a dict gives `field` (Q, Wx, Wy, Wz, Pr or C), `level` and optionally `color`, a field of

@@ -668,6 +668,37 @@ def tracers_advance(X, state, Vx, Vy, Vz, cx, cy, cz, U=None, ctx=None):
                        *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), *_d(cx, cy, cz), nx, ny, nz)
 
 
+def _int3(v):
+    return None if v is None else (C.c_int * 3)(*(int(q) for q in v))
+
+
+def sample_at(A, X, out, state=None, stagger=(0, 0, 0), origin=None, ctx=None):
+    """ns3d_sample_at: `sample` for a rank of a decomposed grid — X holds GLOBAL index-space coordinates, A is the rank's local array
+    and origin = coords·(n−2) its first cell; the field is interpolated at X − origin, points outside the LOCAL array receive NaN.
+    origin=None: zeros, the bits of `sample`."""
+    n = out.numel() if isinstance(out, torch.Tensor) else 0
+    ex, ey, ez = A.shape
+    sx, sy, sz = (int(q) for q in stagger)
+    _ctx(ctx, A).call("sample_at", A, _chk_points(out, n, 1, torch.float64, "out", A), _chk_points(X, n, 3, torch.float64, "X", A),
+                      None if state is None else _chk_points(state, n, 1, torch.uint8, "state", A), C.c_long(n),
+                      _chk(A, None, "A"), ex, ey, ez, sx, sy, sz, _int3(origin))
+
+
+def tracers_advance_at(X, state, Vx, Vy, Vz, cx, cy, cz, U=None, origin=None, n_g=None, ctx=None):
+    """ns3d_tracers_advance_at: `tracers_advance` for a rank of a decomposed grid — X holds GLOBAL index-space coordinates, the
+    fields are the rank's local arrays, origin = coords·(n−2), n_g the global cell grid whose closed box decides who is alive; the
+    velocity is interpolated at X − origin.  origin / n_g None: zeros resp. the local grid, the bits of `tracers_advance`."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    n = state.numel() if isinstance(state, torch.Tensor) else 0
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if isinstance(t, torch.Tensor) and (t.dtype != Vx.dtype or t.device != Vx.device):
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("tracers_advance_at", Vx, _chk_points(X, n, 3, torch.float64, "X", Vx),
+                       _chk_points(state, n, 1, torch.uint8, "state", Vx),
+                       None if U is None else _chk_points(U, n, 3, torch.float64, "U", Vx), C.c_long(n),
+                       *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), *_d(cx, cy, cz), nx, ny, nz, _int3(origin), _int3(n_g))
+
+
 def isosurface(A, level, color=None, box=None, origin=None, tri=None, val=None, cap=0, ctx=None):
     """ns3d_isosurface: the triangles of the level set A = level by marching tetrahedra (include/ns3d.h has the definition; the same
     bits in every arithmetic mode), in index space.  A: any column-major array of extents ≥ 2 whose entries are nodes at integer

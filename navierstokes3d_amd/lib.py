@@ -106,6 +106,8 @@ DERIVED_SIGNATURES = {
     "sample": [_P] * 3 + [_L, _P] + [_I] * 6,
     "tracers_advance": [_P] * 3 + [_L] + [_P] * 3 + [_D] * 3 + [_I] * 3,
     "isosurface": [_P] * 2 + [_I] * 3 + [C.POINTER(_I)] * 2 + [_D] + [_P] * 2 + [C.c_longlong, C.POINTER(C.c_longlong)],
+    "sample_at": [_P] * 3 + [_L, _P] + [_I] * 6 + [C.POINTER(_I)],
+    "tracers_advance_at": [_P] * 3 + [_L] + [_P] * 3 + [_D] * 3 + [_I] * 3 + [C.POINTER(_I)] * 2,
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
@@ -146,6 +148,7 @@ MGPU_SYMBOLS = {
     "ns3d_slab_iterate": (_I, [_P, _I]),
     "ns3d_slab_plan": (_I, [_P]),
     "ns3d_slab_residual": (_I, [_P, C.POINTER(_D)]),
+    "ns3d_tracers_migrate_mgpu": (_I, [_P, _PP, _PP, _PP, _PP, C.POINTER(_L), C.POINTER(C.c_longlong), C.POINTER(_L)]),
 }
 MGPU_SIGNATURES = {   # typed (_f64/_f32), after the leading ns3d_mgpu*
     "update_halo": [_PP, C.POINTER(_I), _I],
@@ -157,6 +160,7 @@ MGPU_SIGNATURES = {   # typed (_f64/_f32), after the leading ns3d_mgpu*
                       C.POINTER(_I)],
     "poisson_direct_slab": [_PP, _PP, _PP, C.POINTER(PtParams)],
     "diagnostics_mgpu": [_PP] * 5 + [C.POINTER(DiagParams), C.POINTER(Diag), C.POINTER(Diag)],
+    "tracers_advance_mgpu": [_PP] * 3 + [C.POINTER(_L)] + [_PP] * 3 + [_D] * 3,
 }
 
 

@@ -292,6 +292,50 @@ class MultiGpu:
         return K.diag_record(glob), [K.diag_record(d) for d in loc]
 
 
+    # ---- tracers on a decomposed grid ----------------------------------------------------------------------------
+    def _slot_ptrs(self, lst, blocks, dtype, name, caps):
+        """one device pointer per local rank to a contiguous array of blocks·cap[l] elements (None for a rank without slots)"""
+        lst = _as_list(lst)
+        if len(lst) != self.nlocal:
+            raise L.Ns3dError("%s: expected one array per local rank (%d), got %d" % (name, self.nlocal, len(lst)))
+        out = []
+        for l, t in enumerate(lst):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+                raise L.Ns3dError("%s[%d] must be a contiguous %s CUDA/HIP tensor" % (name, l, dtype))
+            if t.device.index != self._devices[l] or t.numel() != blocks * caps[l]:
+                raise L.Ns3dError("%s[%d]: %d elements on %s, expected %d x %d on device %d"
+                                  % (name, l, t.numel(), t.device, blocks, caps[l], self._devices[l]))
+            out.append(t.data_ptr() if caps[l] else None)
+        return (C.c_void_p * self.nlocal)(*out)
+
+    def tracers_advance(self, X, state, Vx, Vy, Vz, cx, cy, cz, U=None):
+        """ns3d_tracers_advance_mgpu: kernels.tracers_advance_at on every local rank with its origin and the grid's n_g.  X, state,
+        U: per-rank lists of (3, cap) float64 / (cap,) uint8 slot arrays in GLOBAL index space; enqueues."""
+        self._follow_torch_streams()
+        caps = [int(s.numel()) for s in _as_list(state)]
+        ref = _as_list(Vx)[0]
+        L.check(self._typed("tracers_advance_mgpu", ref)(
+            self.handle, self._slot_ptrs(X, 3, torch.float64, "X", caps), self._slot_ptrs(state, 1, torch.uint8, "state", caps),
+            None if U is None else self._slot_ptrs(U, 3, torch.float64, "U", caps), (C.c_long * self.nlocal)(*caps),
+            self._ptrs([Vx]), self._ptrs([Vy]), self._ptrs([Vz]), C.c_double(cx), C.c_double(cy), C.c_double(cz)))
+
+    def tracers_migrate(self, X, state, ids, U=None):
+        """ns3d_tracers_migrate_mgpu: live particles whose owner is another rank travel there (ids: per-rank (cap,) int64, −1 = empty
+        slot).  Returns (moved, need): need is None when every rank had room; otherwise NOTHING was moved, moved is 0 and need[l] is
+        the number of empty slots local rank l lacks.  Blocks for the counts."""
+        self._follow_torch_streams()
+        caps = [int(s.numel()) for s in _as_list(state)]
+        moved, need = C.c_longlong(-1), (C.c_long * self.nlocal)()
+        rc = self.lib.ns3d_tracers_migrate_mgpu(
+            self.handle, self._slot_ptrs(X, 3, torch.float64, "X", caps), self._slot_ptrs(state, 1, torch.uint8, "state", caps),
+            self._slot_ptrs(ids, 1, torch.int64, "ids", caps), None if U is None else self._slot_ptrs(U, 3, torch.float64, "U", caps),
+            (C.c_long * self.nlocal)(*caps), C.byref(moved), need)
+        if rc == L.NS3D_ERR_STATE and any(need) and self.transport == "peer":
+            return 0, [int(q) for q in need]
+        L.check(rc)
+        return int(moved.value), None
+
+
 class MgpuGrid:
     """The driver-facing grid object (same surface as halo.ZSlabGrid) on top of a MultiGpu."""
 

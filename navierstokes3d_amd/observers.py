@@ -10,7 +10,7 @@ import numpy as np
 from . import isosurface as ISO
 from . import lib as L
 from .stats import RunningStats
-from .tracers import Probes, Tracers
+from .tracers import MgpuProbes, MgpuTracers, Probes, Tracers
 from .vis import save_frame_tracers, save_frame_vortex
 from .vortex import NAMES as _VORTEX_NAMES, VortexFields, save_bins as _save_vortex_bins
 
@@ -24,9 +24,14 @@ def check_options(grid, statistics, stats_every, vortex, tracers, probes, isosur
         raise L.Ns3dError("statistics = %r (None, or the first step to sample: an integer >= 1)" % (statistics,))
     if int(stats_every) != stats_every or stats_every < 1:
         raise L.Ns3dError("stats_every = %r (an integer >= 1)" % (stats_every,))
-    if P > 1 and (tracers is not None or probes is not None):
-        raise L.Ns3dError("tracers= / probes= run on one rank only (this grid has %d): particles that cross a seam between ranks "
-                          "would have to migrate, and ns3d_tracers_advance / ns3d_sample have no ns3d_mgpu form" % P)
+    for name, val, one, many in (("tracers", tracers, Tracers, MgpuTracers), ("probes", probes, Probes, MgpuProbes)):
+        if isinstance(val, many):
+            if val.grid is not grid:
+                raise L.Ns3dError("%s= is a %s of another grid than the run's" % (name, many.__name__))
+        elif val is not None and P > 1:
+            raise L.Ns3dError("%s= as a number or an array runs on one rank only (this grid has %d): particles that cross a seam "
+                              "between ranks have to migrate — build a tracers.MgpuTracers / tracers.MgpuProbes on the grid (the "
+                              "one-process form) and pass that object" % (name, P))
     if _iso_spec(isosurface) is not None and nlocal != P:
         raise L.Ns3dError("isosurface= needs every rank in this process (one rank, or a mgpu.MgpuGrid in the one-process form): "
                           "this process drives %d of %d ranks" % (nlocal, P))
@@ -105,7 +110,9 @@ class Observers:
         spacings, origin = (p.dx, p.dy, p.dz), (-p.lx / 2, -p.ly / 2, -p.lz / 2)    # the box's low corner in both scripts
         self.vort = VortexFields(self.shape, ctxs, spacings, dtype) if vortex else None
         self.trc = self.prb = None
-        if tracers is not None:
+        if isinstance(tracers, (Tracers, MgpuTracers)):
+            self.trc = tracers                      # a ready object is used as it is
+        elif tracers is not None:
             self.trc = Tracers(self.shape, ctxs[0], spacings, origin)
             if isinstance(tracers, (int, np.integer)) and not isinstance(tracers, bool):
                 if tracers < 0:
@@ -113,7 +120,9 @@ class Observers:
                 self.trc.seed_random(int(tracers), 0)
             else:
                 self.trc.seed_points(tracers)
-        if probes is not None:
+        if isinstance(probes, (Probes, MgpuProbes)):
+            self.prb = probes
+        elif probes is not None:
             self.prb = Probes(self.shape, ctxs[0], spacings, origin, probes, nt)
         self.iso = _IsoObserver(_iso_spec(isosurface), self.shape, ctxs, p, grid, self.vort, dtype) if isosurface is not None else None
 
@@ -127,10 +136,10 @@ class Observers:
         the step's final velocity field, then the probes sample the final state."""
         if self.running is not None and it >= self.first and (it - self.first) % self.every == 0:
             self.running.sample(fs)
-        if self.trc is not None:
-            self.trc.advance(fs[0], self.p.dt)
+        if self.trc is not None:            # the Mgpu objects take every local rank's fields, the one-rank objects the one rank's
+            self.trc.advance(fs if isinstance(self.trc, MgpuTracers) else fs[0], self.p.dt)
         if self.prb is not None:
-            self.prb.record(fs[0])
+            self.prb.record(fs if isinstance(self.prb, MgpuProbes) else fs[0])
 
     def frame(self, fs, save=None, vis=None):
         """The observers' files of a frame of the state in `fs`: `save` / `vis` number the dumps resp. the pictures, None where the
