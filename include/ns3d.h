@@ -48,9 +48,21 @@
  *        any call that grows a scratch buffer   the stream, before the old         as the call otherwise
  *        of the context (ping-pong, monitor,    buffer is freed
  *        isosurface) and ns3d_reserve_cus
+ *        ns3d_set_stream, ns3d_use_own_stream,  the stream the context LEAVES       (none)
+ *        ns3d_reserve_cus                       (when it differs from the new one)
  *    Everything else only enqueues.
- *  - One host thread per context (as in the reference: one thread per rank); contexts are not
- *    thread-safe.
+ *  - One host thread AT A TIME per context (as in the reference: one thread per rank): a context is not thread-safe, two
+ *    threads must not be inside calls on the same context together.  Calls on DIFFERENT contexts may run concurrently from
+ *    different host threads, on one device or several; such contexts share nothing a result depends on.  What the contexts of
+ *    a process do share is guarded inside the library: the planner's memory (the tile shapes timed on first use of a grid
+ *    are remembered per process, device, grid, element type, arithmetic build, pinned depth and CU mask, and answer the
+ *    look-ups of every context) and the eigenvector cache of ns3d_poisson_direct.  ns3d_last_error() is per THREAD: it
+ *    returns the message of the latest failed call made by the calling thread, on whichever context.
+ *    A cooperative launch (ns3d_set_persist_mode) beside other contexts' kernels may find compute units taken; it is then
+ *    voided and redone as described there, with the same result.
+ *    (tests/test_gpu_context_history.py runs one context through the entry points that keep state in it — every PT form, the
+ *    direct solve, monitor, isosurface, read-backs, whole steps — on seven grids, in both element types, between changes of
+ *    every knob and stream, in hostile and seeded orders; tests/test_gpu_host_threads.py runs four such contexts on four threads.)
  *  - Arithmetic modes: NS3D_STRICT reproduces the reference's operation order with correctly rounded division
  *    and no FMA contraction (bit-identical to the CPU oracle); NS3D_FAST uses reciprocal constants and FMA
  *    (≤1e-6 relative L2 at equal iteration counts).  In STRICT mode x/dx is evaluated as the correctly rounded
@@ -101,7 +113,13 @@ ns3d_ctx *ns3d_create(int device, int flags);
 void ns3d_destroy(ns3d_ctx *ctx);
 int ns3d_flags(const ns3d_ctx *ctx);
 /* Launch on an existing hipStream_t (e.g. PyTorch's current stream; NULL is HIP's null stream).  A new context
- * launches on a private non-blocking stream; ns3d_use_own_stream() returns to it. */
+ * launches on a private non-blocking stream; ns3d_use_own_stream() returns to it.  Both WAIT for the stream the context
+ * leaves (as does ns3d_reserve_cus): whatever an NS3D_ASYNC context queued there is complete before the context launches
+ * anywhere else, so its scratch, counters and read-back words are never used from two streams at once.  The stream being
+ * left must still exist (a host that destroys a stream moves its contexts off it first).  While either stream — the one left
+ * or the one moved to — is being captured there is no wait: a captured stream runs nothing, and a synchronisation beside the
+ * caller's capture would invalidate it; a host that moves an NS3D_ASYNC context into a capture has synchronised it before
+ * the capture began.  Naming the stream the context is already on costs nothing. */
 int ns3d_set_stream(ns3d_ctx *ctx, void *hip_stream);
 int ns3d_use_own_stream(ns3d_ctx *ctx);
 /* Leave `n_cus` compute units of the device OUT of this context's launches: the context gets a stream of its own created with a CU

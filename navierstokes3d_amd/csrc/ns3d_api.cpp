@@ -173,15 +173,36 @@ void ns3d_destroy(ns3d_ctx *c)
 
 int ns3d_flags(const ns3d_ctx *c) { return c ? c->flags : -1; }
 
+// A context waits for the stream it leaves.  What it remembers is ordered by the stream it launches on and by nothing else: the
+// ping-pong, monitor and isosurface scratch (freed when it grows, after a wait for c->stream and c->own_stream only), the key word
+// of the residual read-backs, k_pt_persist's exchange area and the pace counters (reset by fills on the launch's stream).  Work
+// of an NS3D_ASYNC context still queued on a stream the context no longer names would meet all of these unordered.  A stream that
+// is being captured runs nothing and is not waited for, and there is no wait either while the stream moved TO is being captured.
+static int leave_stream(ns3d_ctx *c, hipStream_t next)
+{
+    if (c->stream == next) return NS3D_OK;
+    ns3d_device_guard guard(c->device);
+    // neither end of the move may be under capture: a captured stream runs nothing, and a synchronisation made by the thread that
+    // is capturing `next` (a context following the caller's stream into the caller's capture) would invalidate that capture
+    for (hipStream_t q : {c->stream, next}) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(q, &cap) != hipSuccess) { (void)hipGetLastError(); continue; }
+        if (cap != hipStreamCaptureStatusNone) return NS3D_OK;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return NS3D_OK;
+}
 int ns3d_set_stream(ns3d_ctx *c, void *s)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_stream: null context");
+    if (const int rc = leave_stream(c, (hipStream_t)s)) return rc;
     c->stream = (hipStream_t)s;
     return NS3D_OK;
 }
 int ns3d_use_own_stream(ns3d_ctx *c)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_use_own_stream: null context");
+    if (const int rc = leave_stream(c, c->own_stream)) return rc;
     c->stream = c->own_stream;
     return NS3D_OK;
 }
@@ -224,6 +245,11 @@ int ns3d_reserve_cus(ns3d_ctx *c, int n)
         if (keep) mask[(size_t)(i / 32)] |= 1u << (i % 32);
     }
     HIPCHK(c, hipExtStreamCreateWithCUMask(&c->masked_stream, (uint32_t)words, mask.data()));
+    if (const int rc = leave_stream(c, c->masked_stream)) {
+        (void)hipStreamDestroy(c->masked_stream);
+        c->masked_stream = nullptr;
+        return rc;
+    }
     c->reserved_cus = n;
     c->stream = c->masked_stream;
     return NS3D_OK;

@@ -434,8 +434,17 @@ int ns3d_direct_basis(int m, double d, int kind, double **V, double **lam)
     eig1d_cached(m, d, kind, hV, hl);
     HIPCHK(0, hipMalloc((void **)V, hV.size() * sizeof(double)));
     HIPCHK(0, hipMalloc((void **)lam, hl.size() * sizeof(double)));
-    HIPCHK(0, hipMemcpy(*V, hV.data(), hV.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(0, hipMemcpy(*lam, hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
+    // Uploaded on a stream of this call's own, never by hipMemcpy on the legacy null stream: while ANY thread of the process is
+    // capturing a stream — thread-local mode included, and the contexts of other host threads capture their residual-check blocks
+    // (run_block_graph) — the runtime refuses every legacy-stream copy with hipErrorStreamCaptureImplicit
+    // (tests/test_gpu_host_threads.py::test_four_threads_each_with_a_context met it here).
+    hipStream_t up = nullptr;
+    HIPCHK(0, hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+    hipError_t e = hipMemcpyAsync(*V, hV.data(), hV.size() * sizeof(double), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipMemcpyAsync(*lam, hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);        // hV and hl are this call's own: complete before they go
+    (void)hipStreamDestroy(up);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "eigenbasis upload: %s", hipGetErrorString(e)); }
     return NS3D_OK;
 }
 

@@ -2435,13 +2435,14 @@ static bool apply_tile_window(SweepArgs<T> &a, int TX, int TY, int OV, int &ntx,
 // Workgroups of a kernel that one CU holds at a time (registers, LDS, wave slots), and the CUs of the current device.
 static int device_cus()
 {
-    static int cus = 0;
-    if (!cus) {
+    // initialised once, by one thread (contexts on different host threads launch concurrently)
+    static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else { (void)hipGetLastError(); cus = 256; }
-    }
+            return n;
+        (void)hipGetLastError();
+        return 256;
+    }();
     return cus;
 }
 static int workgroups_per_cu(const void *kernel, int threads)
