@@ -189,6 +189,15 @@ int ns3d_set_pt_pace(ns3d_ctx *ctx, int pace_z);
 int ns3d_last_pt_pace(const ns3d_ctx *ctx);
 int ns3d_set_pt_pace_test(ns3d_ctx *ctx, int extra_arrivals, int ticks);
 int ns3d_cached_graphs(const ns3d_ctx *ctx);      /* residual-check blocks this context holds as instantiated HIP graphs */
+/* Which advection ns3d_time_step runs in place of {X_o .= X; advect!}.  NS3D_ADVECT_REFERENCE (the default): ns3d_copy_advect, the
+ * reference's first-order semi-Lagrangian step.  NS3D_ADVECT_MACCORMACK: {ns3d_copy_advect(faithful = 0) into hat fields held in the
+ * context's scratch; ns3d_advect_correct; swap all four names} — the limited second-order scheme defined at ns3d_advect_mc, one rank;
+ * ns3d_time_step then requires p->faithful == 0 (NS3D_ERR_ARG otherwise, the fields untouched).  ns3d_advection returns the setting
+ * (-1 for a null context).  Nothing else reads the knob: the single calls are what their names say. */
+#define NS3D_ADVECT_REFERENCE 0
+#define NS3D_ADVECT_MACCORMACK 1
+int ns3d_set_advection(ns3d_ctx *ctx, int scheme);
+int ns3d_advection(const ns3d_ctx *ctx);
 
 /* Parameters of the fused pseudo-transient path (ns3d_pt_iterate / ns3d_pt_solve). */
 typedef struct ns3d_pt_params {
@@ -531,6 +540,47 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
     int ns3d_copy_advect_##S(ns3d_ctx *, T *Vx_new, const T *Vx, T *Vy_new, const T *Vy, T *Vz_new, const T *Vz, T *C_new, \
                              const T *C, double dt, double dx, double dy, double dz, int nx, int ny, int nz, \
                              int faithful);                                                                  \
+    /* Limited MacCormack advection (Selle et al. 2008), second order, built from backtrack! itself — NOT in the reference, an    \
+     * option beside ns3d_copy_advect, one rank.  All arithmetic is in T, like advect!.  For a field A with old values A_o the    \
+     * advected nodes and their velocities (vxc, vyc, vzc: averages of the OLD velocities) are advect!'s four branches with the   \
+     * third one corrected: Vx ix = 2…nx, Vy iy = 2…ny, Vz iz = 2…nz, C every cell.                                              \
+     *   stage 1   Â = backtrack!(Â, A_o, vxc, vyc, vzc, dt, …): what ns3d_copy_advect(…, faithful = 0) returns, complete          \
+     *   stage 2   back = backtrack! on the complete Â with (T)(−dt) in place of dt and the same vxc, vyc, vzc                    \
+     *             s = Â[ix,iy,iz] + h·(A_o[ix,iy,iz] − back),  h = (T)0.5  (this order; STRICT does not contract it)             \
+     *             lo, hi = the smallest and largest of the eight OLD values stage 1 interpolated between: with stage 1's own     \
+     *             ix1 = clamp(floor(ix − δx), 1, sx), ix2 = clamp(ix1 + 1, 1, sx) (likewise y, z) start from c = A_o[ix1,iy1,iz1] \
+     *             and visit (2,1,1), (1,2,1), (2,2,1), (1,1,2), (2,1,2), (1,2,2), (2,2,2): lo = c < lo ? c : lo, hi = c > hi ? c : hi \
+     *             A_new = s < lo ? lo : s;  A_new = A_new > hi ? hi : A_new   (comparisons: a NaN s stays NaN)                   \
+     * Entries outside the advected set receive Â's value (the current one).  No address outside the arrays is read: every index \
+     * is clamped as in backtrack!.  A field at rest keeps its values in every mode.  Stage 2 as NumPy, for one field on its     \
+     * advected nodes IX, IY, IZ (1-based index grids), arrays and scalars of dtype T, lerp(a, b, t) = b*t + a*(1 − t):            \
+     *   def departure(dt):                                                                                                       \
+     *       dd = [dt*vxc/dx, dt*vyc/dy, dt*vzc/dz]                                                                                \
+     *       i1 = [np.clip(np.floor(I − d).astype(np.int64), 1, s) for I, d, s in zip((IX, IY, IZ), dd, A_o.shape)]               \
+     *       i2 = [np.clip(i + 1, 1, s) for i, s in zip(i1, A_o.shape)]                                                           \
+     *       return i1, i2, [(d > 0).astype(T) − np.fmod(d, 1) for d in dd]                                                       \
+     *   (x1, y1, z1), (x2, y2, z2), _ = departure(dt);  o = lambda i, j, k: A_o[i − 1, j − 1, k − 1]                                \
+     *   lo = hi = o(x1, y1, z1)                                                                                                   \
+     *   for c in (o(x2,y1,z1), o(x1,y2,z1), o(x2,y2,z1), o(x1,y1,z2), o(x2,y1,z2), o(x1,y2,z2), o(x2,y2,z2)):                     \
+     *       lo = np.where(c < lo, c, lo);  hi = np.where(c > hi, c, hi)                                                          \
+     *   (x1, y1, z1), (x2, y2, z2), (wx, wy, wz) = departure(−dt);  a = lambda i, j, k: A_hat[i − 1, j − 1, k − 1]                  \
+     *   fz1 = lerp(lerp(a(x1,y1,z1), a(x2,y1,z1), wx), lerp(a(x1,y2,z1), a(x2,y2,z1), wx), wy)                                    \
+     *   fz2 = lerp(lerp(a(x1,y1,z2), a(x2,y1,z2), wx), lerp(a(x1,y2,z2), a(x2,y2,z2), wx), wy)                                    \
+     *   s = a(IX, IY, IZ) + h*(o(IX, IY, IZ) − lerp(fz1, fz2, wz))                                                                \
+     *   A_new = A_hat.copy();  r = np.where(s < lo, lo, s);  A_new[IX − 1, IY − 1, IZ − 1] = np.where(r > hi, hi, r)                \
+     * STRICT returns these bits (whichever division build the spacings select); FAST multiplies by reciprocals, may contract,   \
+     * and limits against the stencil ITS stage 1 chose.                                                                          \
+     * ns3d_advect_correct is stage 2 alone: X_hat is stage 1's complete result for the old field X, X_new receives the new field \
+     * (every entry).  ns3d_advect_mc runs stage 1 into the caller's X_hat buffers, then stage 2; afterwards the X_hat hold stage  \
+     * 1's complete result.  Both are enqueued on the context's stream without a read-back (they block only as every call does    \
+     * without NS3D_ASYNC).  NS3D_ERR_ARG, nothing written: a null context or pointer, a grid below 3×3×3, any two of the twelve   \
+     * arrays equal. */                                                                                                            \
+    int ns3d_advect_correct_##S(ns3d_ctx *, T *Vx_new, const T *Vx, const T *Vx_hat, T *Vy_new, const T *Vy, const T *Vy_hat,      \
+                                T *Vz_new, const T *Vz, const T *Vz_hat, T *C_new, const T *C, const T *C_hat, double dt,          \
+                                double dx, double dy, double dz, int nx, int ny, int nz);                                        \
+    int ns3d_advect_mc_##S(ns3d_ctx *, T *Vx_new, const T *Vx, T *Vx_hat, T *Vy_new, const T *Vy, T *Vy_hat, T *Vz_new,            \
+                           const T *Vz, T *Vz_hat, T *C_new, const T *C, T *C_hat, double dt, double dx, double dy, double dz,    \
+                           int nx, int ny, int nz);                                                                              \
     /* DIRECT solve of what the pseudo-transient loop multi.jl:458-471 / gpu.jl:126-137 iterates towards (an   \
      * option OUTSIDE parity: the reference stops at err < 1e-3, this solves the same discrete system to rounding): Pr's      \
      * interior becomes the solution of ∇²_h Pr = ρ/dt·∇V with the boundary cells of set_bc_Pr! (p->bc_kind, p->owns_outlet,  \

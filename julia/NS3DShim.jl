@@ -45,7 +45,7 @@ export stats_zeros, stats_reset!, stats_accumulate!, stats_finalize
 export vortex
 export sample, tracers_advance!
 export isosurface_count, isosurface
-export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
+export pt_solve!, pt_solve_slab!, maxabs, copy_advect!, advect_mc!, advect_correct!, predict_fused!, poisson_direct!, time_step!, reserve_cus!, StepFields, StepParams
 
 const libns3d = get(ENV, "NS3D_LIB", joinpath(@__DIR__, "..", "navierstokes3d_amd", "libns3d.so"))
 const NS3D_STRICT, NS3D_FAST, NS3D_ASYNC = Cint(0), Cint(1), Cint(2)
@@ -221,6 +221,30 @@ function copy_advect!(Vx_new, Vx, Vy_new, Vy, Vz_new, Vz, C_new, C, dt, dx, dy, 
                 (Ptr{Cvoid}, PF, PF, PF, PF, PF, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint, Cint),
                 _ctx(), ptr(Vx_new), ptr(Vx), ptr(Vy_new), ptr(Vy), ptr(Vz_new), ptr(Vz), ptr(C_new), ptr(C),
                 dt, dx, dy, dz, nx, ny, nz, faithful ? 1 : 0))
+end
+
+"""
+    advect_mc!(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat, dt, dx, dy, dz)
+    advect_correct!(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat, dt, dx, dy, dz)
+
+Optional, NOT the reference's scheme: limited MacCormack advection, second order, built from `backtrack!` (`ns3d_advect_mc_f64`;
+include/ns3d.h has the definition).  `advect_mc!` reads the CURRENT fields, leaves stage 1 — `copy_advect!(…; faithful = false)` — in
+the `*_hat` buffers and writes COMPLETE new fields into the `*_new` buffers; the caller swaps the names afterwards.
+`advect_correct!` is stage 2 alone, on `*_hat` buffers the caller filled with stage 1.  Twelve distinct arrays, one rank.
+"""
+function advect_mc!(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat, dt, dx, dy, dz)
+    nx, ny, nz = _cint3(C); _sync()
+    check(ccall((:ns3d_advect_mc_f64, libns3d), Cint,
+                (Ptr{Cvoid}, PF, PF, PF, PF, PF, PF, PF, PF, PF, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint),
+                _ctx(), ptr(Vx_new), ptr(Vx), ptr(Vx_hat), ptr(Vy_new), ptr(Vy), ptr(Vy_hat), ptr(Vz_new), ptr(Vz), ptr(Vz_hat),
+                ptr(C_new), ptr(C), ptr(C_hat), dt, dx, dy, dz, nx, ny, nz))
+end
+function advect_correct!(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat, dt, dx, dy, dz)
+    nx, ny, nz = _cint3(C); _sync()
+    check(ccall((:ns3d_advect_correct_f64, libns3d), Cint,
+                (Ptr{Cvoid}, PF, PF, PF, PF, PF, PF, PF, PF, PF, PF, PF, PF, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint),
+                _ctx(), ptr(Vx_new), ptr(Vx), ptr(Vx_hat), ptr(Vy_new), ptr(Vy), ptr(Vy_hat), ptr(Vz_new), ptr(Vz), ptr(Vz_hat),
+                ptr(C_new), ptr(C), ptr(C_hat), dt, dx, dy, dz, nx, ny, nz))
 end
 
 """

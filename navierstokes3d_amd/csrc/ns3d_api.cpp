@@ -164,6 +164,7 @@ void ns3d_destroy(ns3d_ctx *c)
     if (c->diag_dev) (void)hipFree(c->diag_dev);
     if (c->diag_host) (void)hipHostFree(c->diag_host);
     if (c->iso_dev) (void)hipFree(c->iso_dev);
+    if (c->mc_hat) (void)hipFree(c->mc_hat);
     if (c->key_dev) (void)hipFree(c->key_dev);
     if (c->key_host) (void)hipHostFree(c->key_host);
     if (c->masked_stream) { (void)hipStreamSynchronize(c->masked_stream); (void)hipStreamDestroy(c->masked_stream); }
@@ -331,6 +332,16 @@ int ns3d_set_pt_depth(ns3d_ctx *c, int depth)
     return NS3D_OK;
 }
 
+int ns3d_set_advection(ns3d_ctx *c, int scheme)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_advection: null context");
+    if (scheme != NS3D_ADVECT_REFERENCE && scheme != NS3D_ADVECT_MACCORMACK)
+        return fail(NS3D_ERR_ARG, "ns3d_set_advection: scheme %d (NS3D_ADVECT_REFERENCE | NS3D_ADVECT_MACCORMACK)", scheme);
+    c->advection = scheme;
+    return NS3D_OK;
+}
+int ns3d_advection(const ns3d_ctx *c) { return c ? c->advection : -1; }
+
 int ns3d_set_pt2_variant(ns3d_ctx *c, int v)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_pt2_variant: null context");
@@ -489,6 +500,18 @@ static int ensure_pingpong_d(ns3d_ctx *c, const ns3d_pt_params *p, T **buf)
     const int rc = ensure_scratch(c, c->pingpong_d, c->pingpong_d_bytes, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T));
     if (!rc) *buf = (T *)c->pingpong_d;
     return rc;
+}
+
+// the hat fields of ns3d_time_step's MacCormack advection: stage 1's Vx, Vy, Vz, C of an nx×ny×nz grid, one after the other
+template <class T>
+static int ensure_mc_hat(ns3d_ctx *c, int nx, int ny, int nz, T *hat[4])
+{
+    const size_t n[4] = {(size_t)(nx + 1) * ny * nz, (size_t)nx * (ny + 1) * nz, (size_t)nx * ny * (nz + 1), (size_t)nx * ny * nz};
+    const int rc = ensure_scratch(c, c->mc_hat, c->mc_hat_bytes, (n[0] + n[1] + n[2] + n[3]) * sizeof(T));
+    if (rc) return rc;
+    T *p = (T *)c->mc_hat;
+    for (int q = 0; q < 4; ++q) { hat[q] = p; p += n[q]; }
+    return NS3D_OK;
 }
 
 // ---- tile shape of the two-iteration sweep ------------------------------------------------------------------

@@ -240,6 +240,41 @@ extern "C" int NS3D_FN(copy_advect)(ns3d_ctx *c, T *Vx_new, const T *Vx, T *Vy_n
     return finish(c, DISPATCHG(c, dx, dy, dz, advect<T>(c->stream, Vx_new, Vx, Vy_new, Vy, Vz_new, Vz, C_new, C, dt, dx, dy, dz, nx, ny, nz,
                                                         (faithful ? 1 : 0) | 2, 0, 0)), "copy_advect");
 }
+// ns3d_advect_correct / ns3d_advect_mc: the checks both share, under the entry point's name
+static int advect_mc_check(const char *fn, const void *const (&a)[12], int nx, int ny, int nz)
+{
+    for (int q = 0; q < 12; ++q)
+        if (!a[q]) return fail(NS3D_ERR_ARG, "%s: null field pointer (argument %d)", fn, q);
+    if (nx < 3 || ny < 3 || nz < 3) return fail(NS3D_ERR_ARG, "%s: grid %dx%dx%d too small (need >= 3 per direction)", fn, nx, ny, nz);
+    for (int q = 0; q < 12; ++q)
+        for (int r = q + 1; r < 12; ++r)
+            if (a[q] == a[r]) return fail(NS3D_ERR_ARG, "%s: arguments %d and %d are the same array (twelve distinct arrays)", fn, q, r);
+    return NS3D_OK;
+}
+extern "C" int NS3D_FN(advect_correct)(ns3d_ctx *c, T *Vx_new, const T *Vx, const T *Vx_hat, T *Vy_new, const T *Vy, const T *Vy_hat,
+                                       T *Vz_new, const T *Vz, const T *Vz_hat, T *C_new, const T *C, const T *C_hat, double dt, double dx,
+                                       double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c);
+    const void *const a[12] = {Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat};
+    if (const int rc = advect_mc_check(__func__, a, nx, ny, nz)) return rc;
+    return finish(c, DISPATCHG(c, dx, dy, dz, advect_mc<T>(c->stream, Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C,
+                                                           C_hat, dt, dx, dy, dz, nx, ny, nz)), "advect_correct");
+}
+extern "C" int NS3D_FN(advect_mc)(ns3d_ctx *c, T *Vx_new, const T *Vx, T *Vx_hat, T *Vy_new, const T *Vy, T *Vy_hat, T *Vz_new, const T *Vz,
+                                  T *Vz_hat, T *C_new, const T *C, T *C_hat, double dt, double dx, double dy, double dz, int nx, int ny,
+                                  int nz)
+{
+    CHECK_CTX(c);
+    const void *const a[12] = {Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat};
+    if (const int rc = advect_mc_check(__func__, a, nx, ny, nz)) return rc;
+    // stage 1: ns3d_copy_advect(faithful = 0) into the hat buffers; stage 2 behind it on the same stream
+    hipError_t e = DISPATCHG(c, dx, dy, dz, advect<T>(c->stream, Vx_hat, Vx, Vy_hat, Vy, Vz_hat, Vz, C_hat, C, dt, dx, dy, dz, nx, ny, nz, 2, 0, 0));
+    if (e == hipSuccess)
+        e = DISPATCHG(c, dx, dy, dz, advect_mc<T>(c->stream, Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, C, C_hat, dt,
+                                                  dx, dy, dz, nx, ny, nz));
+    return finish(c, e, "advect_mc");
+}
 extern "C" int NS3D_FN(set_bc_Pr)(ns3d_ctx *c, T *Pr, int bc_kind, int owns_outlet, double outlet_val, double dz, int nz_arg, double g,
                                   double rho, int nx, int ny, int nz)
 {
@@ -396,6 +431,9 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
     if (p->write_stress && !(f->txx && f->tyy && f->tzz && f->txy && f->txz && f->tyz))
         return fail(NS3D_ERR_ARG, "ns3d_time_step: write_stress needs the six stress arrays");
     const int nx = p->nx, ny = p->ny, nz = p->nz;
+    const bool maccormack = c->advection == NS3D_ADVECT_MACCORMACK;
+    if (maccormack && p->faithful)
+        return fail(NS3D_ERR_ARG, "ns3d_time_step: NS3D_ADVECT_MACCORMACK advects Vz: it needs faithful == 0");
     const int was = c->flags;
     c->flags |= NS3D_ASYNC;
     int rc = NS3D_OK;
@@ -434,6 +472,15 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
         if ((rc = NS3D_FN(correct_V)(c, Vx, Vy, Vz, Pr, p->dt, p->rho, p->dx, p->dy, p->dz, nx, ny, nz))) break;    // :472 / :138
         if ((rc = cylinder())) break;                                                                               // :473 / :139
         if ((rc = NS3D_FN(set_bc_Vel)(c, Vx, Vy, Vz, p->script, p->script == NS3D_BC_MULTI ? p->owns_inlet : 0, p->vin, nx, ny, nz))) break;
+        if (maccormack) {       // ns3d_set_advection: stage 1 into the context's hat fields, stage 2 into the *_o buffers, all four names swap
+            T *hat[4];
+            if ((rc = ensure_mc_hat<T>(c, nx, ny, nz, hat))) break;
+            if ((rc = NS3D_FN(copy_advect)(c, hat[0], Vx, hat[1], Vy, hat[2], Vz, hat[3], C, p->dt, p->dx, p->dy, p->dz, nx, ny, nz, 0))) break;
+            if ((rc = NS3D_FN(advect_correct)(c, Vxo, Vx, hat[0], Vyo, Vy, hat[1], Vzo, Vz, hat[2], Co, C, hat[3], p->dt, p->dx, p->dy, p->dz, nx,
+                                              ny, nz))) break;
+            std::swap(Vx, Vxo); std::swap(Vy, Vyo); std::swap(Vz, Vzo); std::swap(C, Co);
+            break;
+        }
         // :475-476 / :141-142 in one pass: complete new fields into the *_o buffers, then the roles swap
         if ((rc = NS3D_FN(copy_advect)(c, Vxo, Vx, Vyo, Vy, p->faithful ? Vz : Vzo, Vz, Co, C, p->dt, p->dx, p->dy, p->dz, nx, ny, nz,
                                        p->faithful ? 1 : 0))) break;

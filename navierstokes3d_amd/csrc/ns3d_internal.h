@@ -53,6 +53,9 @@ struct ns3d_ctx {
     void (*direct_free)(void *) = nullptr;
     void *iso_dev = nullptr;                // ns3d_isosurface: segment counts, their scan and the total (grown lazily)
     size_t iso_bytes = 0;
+    int advection = 0;                      // ns3d_set_advection: what ns3d_time_step advects with (NS3D_ADVECT_*)
+    void *mc_hat = nullptr;                 // ns3d_time_step under NS3D_ADVECT_MACCORMACK: stage 1's four complete fields (grown lazily)
+    size_t mc_hat_bytes = 0;
     void clear_graphs()
     {
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.exec);

@@ -1426,6 +1426,238 @@ hipError_t advect(hipStream_t s, T *Vx, const T *Vx_o, T *Vy, const T *Vy_o, T *
     return hipGetLastError();
 }
 
+// ---- ns3d_advect_correct: stage 2 of the limited MacCormack advection (include/ns3d.h has the definition) -----------------------
+// Stage 1 is advect() above with the corrected third branch and write-through: Â, complete.  Stage 2, per node of a field's advected
+// set: the departure cell of stage 1 once more (adv_departure on the same operands: the FAST build picks the stencil its own stage 1
+// picked) for the hull of the eight OLD corners, the reverse back-track of Â with −dt (adv_departure + adv_lerp8 again), the
+// correction and the two comparisons of the limiter.  k_advect_mc is k_advect_win2's march: the same window of the four OLD fields
+// (AdvWin2, 153 KB) serves the staggered velocity averages, the forward corners and the node's own old value; a forward corner
+// outside the window comes from global memory, like there.  The reverse corners and the node's Â come from global memory: they lie
+// within a cell or two of the node, the planes a workgroup touches are the ones its neighbours in z and the lanes beside it
+// touch too, and a second window would not fit beside the first.  k_advect_mc_global (NS3D_ADVECT_GLOBAL=1) is one thread per node
+// with every operand from global memory; both go through mc_node, hence the same expression trees and the same bits.
+template <class T>
+__device__ __forceinline__ T mc_limit(T hat, T a_o, T back, const T (&c)[8])
+{
+    const T s = hat + (T)0.5 * (a_o - back);
+    T lo = c[0], hi = c[0];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) {               // corners (2,1,1), (1,2,1), (2,2,1), (1,1,2), (2,1,2), (1,2,2), (2,2,2)
+        lo = c[q] < lo ? c[q] : lo;
+        hi = c[q] > hi ? c[q] : hi;
+    }
+    const T r = s < lo ? lo : s;                // comparisons: a NaN s stays NaN
+    return r > hi ? hi : r;
+}
+// one node (ix, iy, iz) of the array `a` (extents sx, sy, sz): a_o its own old value, (vxc, vyc, vzc) advect!'s averages for it
+template <class T, bool WIN>
+__device__ __forceinline__ T mc_node(const AdvWin2<T> &w, int a, const T *__restrict__ A_o, const T *__restrict__ A_hat, T a_o, T vxc,
+                                     T vyc, T vzc, T dt, const Geo<T> &g, int ix, int iy, int iz, int sx, int sy, int sz)
+{
+    typedef AdvWin2<T> W;
+    const AdvDep<T> d = adv_departure<T>(vxc, vyc, vzc, dt, g, ix, iy, iz, sx, sy, sz, 0, 0);
+    T c[8];
+    if (WIN && adv_holds<T>(w, d)) {
+        const int base = a * (W::NSLOT * W::PLANE) + (d.j1 - (w.y0 - W::YLO)) * W::WX + (d.i1 - (w.x0 - W::XLO));
+        const int ex = d.i2 - d.i1, ey = (d.j2 - d.j1) * W::WX;
+        typename W::lds_ptr q1 = w.L + base + w.slot_off(d.k1), q2 = w.L + base + w.slot_off(d.k2);
+        c[0] = q1[0]; c[1] = q1[ex]; c[2] = q1[ey]; c[3] = q1[ey + ex];
+        c[4] = q2[0]; c[5] = q2[ex]; c[6] = q2[ey]; c[7] = q2[ey + ex];
+    } else {
+#define AO(i_, j_, k_) A_o[IX3((i_)-1, (j_)-1, (k_)-1, sx, sy)]
+        c[0] = AO(d.i1, d.j1, d.k1); c[1] = AO(d.i2, d.j1, d.k1); c[2] = AO(d.i1, d.j2, d.k1); c[3] = AO(d.i2, d.j2, d.k1);
+        c[4] = AO(d.i1, d.j1, d.k2); c[5] = AO(d.i2, d.j1, d.k2); c[6] = AO(d.i1, d.j2, d.k2); c[7] = AO(d.i2, d.j2, d.k2);
+#undef AO
+    }
+    const T back = adv_from_global<T>(A_hat, adv_departure<T>(vxc, vyc, vzc, -dt, g, ix, iy, iz, sx, sy, sz, 0, 0), sx, sy);
+    return mc_limit<T>(A_hat[IX3(ix - 1, iy - 1, iz - 1, sx, sy)], a_o, back, c);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_advect_mc_global(T *__restrict__ Vx, const T *__restrict__ Vx_o, const T *__restrict__ Vx_h,
+                                                          T *__restrict__ Vy, const T *__restrict__ Vy_o, const T *__restrict__ Vy_h,
+                                                          T *__restrict__ Vz, const T *__restrict__ Vz_o, const T *__restrict__ Vz_h,
+                                                          T *__restrict__ C, const T *__restrict__ C_o, const T *__restrict__ C_h, T dt,
+                                                          Geo<T> g, int nx, int ny, int nz)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int iy = blockIdx.y * blockDim.y + threadIdx.y + 1;
+    const int iz = blockIdx.z * blockDim.z + threadIdx.z + 1;
+    if (ix > nx + 1 || iy > ny + 1 || iz > nz + 1) return;
+    const AdvWin2<T> w{nullptr, 0, 0, 0};       // not read (WIN = false)
+#define VXO(i_, j_, k_) Vx_o[IX3((i_)-1, (j_)-1, (k_)-1, nx + 1, ny)]
+#define VYO(i_, j_, k_) Vy_o[IX3((i_)-1, (j_)-1, (k_)-1, nx, ny + 1)]
+#define VZO(i_, j_, k_) Vz_o[IX3((i_)-1, (j_)-1, (k_)-1, nx, ny)]
+    const bool cell = ix <= nx && iy <= ny && iz <= nz;
+    if (iy <= ny && iz <= nz) {                 // a node of Vx
+        const idx_t o = IX3(ix - 1, iy - 1, iz - 1, nx + 1, ny);
+        if (ix > 1 && ix <= nx) {
+            const T vxc = VXO(ix, iy, iz);
+            const T vyc = (T)0.25 * (((VYO(ix - 1, iy, iz) + VYO(ix - 1, iy + 1, iz)) + VYO(ix, iy, iz)) + VYO(ix, iy + 1, iz));
+            const T vzc = (T)0.25 * (((VZO(ix - 1, iy, iz) + VZO(ix - 1, iy, iz + 1)) + VZO(ix, iy, iz)) + VZO(ix, iy, iz + 1));
+            Vx[o] = mc_node<T, false>(w, 0, Vx_o, Vx_h, vxc, vxc, vyc, vzc, dt, g, ix, iy, iz, nx + 1, ny, nz);
+        } else Vx[o] = Vx_h[o];
+    }
+    if (ix <= nx && iz <= nz) {                 // a node of Vy
+        const idx_t o = IX3(ix - 1, iy - 1, iz - 1, nx, ny + 1);
+        if (iy > 1 && iy <= ny) {
+            const T vxc = (T)0.25 * (((VXO(ix, iy - 1, iz) + VXO(ix + 1, iy - 1, iz)) + VXO(ix, iy, iz)) + VXO(ix + 1, iy, iz));
+            const T vyc = VYO(ix, iy, iz);
+            const T vzc = (T)0.25 * (((VZO(ix, iy - 1, iz) + VZO(ix, iy - 1, iz + 1)) + VZO(ix, iy, iz)) + VZO(ix, iy, iz + 1));
+            Vy[o] = mc_node<T, false>(w, 1, Vy_o, Vy_h, vyc, vxc, vyc, vzc, dt, g, ix, iy, iz, nx, ny + 1, nz);
+        } else Vy[o] = Vy_h[o];
+    }
+    if (ix <= nx && iy <= ny) {                 // a node of Vz
+        const idx_t o = IX3(ix - 1, iy - 1, iz - 1, nx, ny);
+        if (iz > 1 && iz <= nz) {
+            const T vxc = (T)0.25 * (((VXO(ix, iy, iz - 1) + VXO(ix + 1, iy, iz - 1)) + VXO(ix, iy, iz)) + VXO(ix + 1, iy, iz));
+            const T vyc = (T)0.25 * (((VYO(ix, iy, iz - 1) + VYO(ix, iy + 1, iz - 1)) + VYO(ix, iy, iz)) + VYO(ix, iy + 1, iz));
+            const T vzc = VZO(ix, iy, iz);
+            Vz[o] = mc_node<T, false>(w, 2, Vz_o, Vz_h, vzc, vxc, vyc, vzc, dt, g, ix, iy, iz, nx, ny, nz + 1);
+        } else Vz[o] = Vz_h[o];
+    }
+    if (cell) {
+        const T vxc = (T)0.5 * (VXO(ix, iy, iz) + VXO(ix + 1, iy, iz));
+        const T vyc = (T)0.5 * (VYO(ix, iy, iz) + VYO(ix, iy + 1, iz));
+        const T vzc = (T)0.5 * (VZO(ix, iy, iz) + VZO(ix, iy, iz + 1));
+        const idx_t o = IX3(ix - 1, iy - 1, iz - 1, nx, ny);
+        C[o] = mc_node<T, false>(w, 3, C_o, C_h, C_o[o], vxc, vyc, vzc, dt, g, ix, iy, iz, nx, ny, nz);
+    }
+#undef VXO
+#undef VYO
+#undef VZO
+}
+
+template <class T>
+__global__ __launch_bounds__(1024) void k_advect_mc(T *__restrict__ Vx, const T *__restrict__ Vx_o, const T *__restrict__ Vx_h,
+                                                    T *__restrict__ Vy, const T *__restrict__ Vy_o, const T *__restrict__ Vy_h,
+                                                    T *__restrict__ Vz, const T *__restrict__ Vz_o, const T *__restrict__ Vz_h,
+                                                    T *__restrict__ C, const T *__restrict__ C_o, const T *__restrict__ C_h, T dt, Geo<T> g,
+                                                    int nx, int ny, int nz, int kz)
+{
+    typedef AdvWin2<T> W;
+    extern __shared__ __align__(16) unsigned char advect_lds_raw[];
+    T *L = reinterpret_cast<T *>(advect_lds_raw);
+    const int tid = threadIdx.y * W::TX + threadIdx.x;
+    const int x0 = blockIdx.x * W::TX + 1, y0 = blockIdx.y * W::TY + 1;
+    const int zb = blockIdx.z * kz + 1, ze = min(zb + kz, nz + 1);          // planes iz ∈ [zb, ze), iz ≤ nz
+    const int ix = x0 + threadIdx.x, iy = y0 + threadIdx.y;
+    const T *const src[4] = {Vx_o, Vy_o, Vz_o, C_o};
+    const int sxs[4] = {nx + 1, nx, nx, nx}, sys[4] = {ny, ny + 1, ny, ny}, szs[4] = {nz, nz, nz + 1, nz};
+    // the window of the OLD fields is filled and advanced exactly as in k_advect_win2
+    unsigned fbase[4][2];
+    idx_t fplane[4];
+    int q[2];
+    bool has[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        q[h] = tid + h * 1024;
+        has[h] = q[h] < W::PLANE;
+        const int qq = has[h] ? q[h] : 0;
+        const int gi = x0 - W::XLO + qq % W::WX, gj = y0 - W::YLO + qq / W::WX;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int ci = min(max(gi, 1), sxs[a]), cj = min(max(gj, 1), sys[a]);
+            fbase[a][h] = (unsigned)(ci - 1) + (unsigned)sxs[a] * (unsigned)(cj - 1);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) fplane[a] = (idx_t)sxs[a] * sys[a];
+    auto fetch = [&](int plane, T (&v)[4][2]) {            // plane: 1-based, may lie outside the arrays
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const T *__restrict__ pl = src[a] + fplane[a] * (min(max(plane, 1), szs[a]) - 1);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) v[a][h] = has[h] ? pl[fbase[a][h]] : (T)0;
+        }
+    };
+    auto publish = [&](int plane, const T (&v)[4][2]) {
+        const int slot = plane & (W::NSLOT - 1);            // plane ≥ 0
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (has[h]) L[(a * W::NSLOT + slot) * W::PLANE + q[h]] = v[a][h];
+    };
+    {
+        T v[4][2];
+        for (int pl = zb - 1; pl <= zb + 1; ++pl) { fetch(pl, v); publish(pl, v); }
+    }
+    __syncthreads();
+    W w{(typename W::lds_ptr)L, x0, y0, zb};
+    const bool in = ix <= nx && iy <= ny;
+    const int cix = min(ix, nx), ciy = min(iy, ny);
+    const unsigned oVx = (unsigned)(cix - 1) + (unsigned)(nx + 1) * (unsigned)(ciy - 1), oVy = (unsigned)(cix - 1) + (unsigned)nx * (unsigned)(ciy - 1);
+    const unsigned oC = oVy;                                // C and Vz: rows of nx like Vy's
+    const idx_t pVx = (idx_t)(nx + 1) * ny, pVy = (idx_t)nx * (ny + 1), pC = (idx_t)nx * ny;
+#define VXO(i_, j_, k_) w.get(0, (i_), (j_), (k_))
+#define VYO(i_, j_, k_) w.get(1, (i_), (j_), (k_))
+#define VZO(i_, j_, k_) w.get(2, (i_), (j_), (k_))
+    for (int iz = zb; iz < ze; ++iz) {
+        T nxt[4][2];
+        fetch(iz + 2, nxt);                                 // in flight behind this plane's arithmetic
+        w.set_plane(iz);
+        if (in) {
+            const idx_t bVx = pVx * (iz - 1), bVy = pVy * (iz - 1), bC = pC * (iz - 1);
+            const T vx000 = VXO(ix, iy, iz), vx100 = VXO(ix + 1, iy, iz), vy000 = VYO(ix, iy, iz), vy010 = VYO(ix, iy + 1, iz);
+            const T vz000 = VZO(ix, iy, iz), vz001 = VZO(ix, iy, iz + 1);
+            if (ix > 1) { // multi.jl:218-223
+                const T vyc = (T)0.25 * (((VYO(ix - 1, iy, iz) + VYO(ix - 1, iy + 1, iz)) + vy000) + vy010);
+                const T vzc = (T)0.25 * (((VZO(ix - 1, iy, iz) + VZO(ix - 1, iy, iz + 1)) + vz000) + vz001);
+                (Vx + bVx)[oVx] = mc_node<T, true>(w, 0, Vx_o, Vx_h, vx000, vx000, vyc, vzc, dt, g, ix, iy, iz, nx + 1, ny, nz);
+            } else (Vx + bVx)[oVx] = (Vx_h + bVx)[oVx];
+            if (iy > 1) { // multi.jl:224-229
+                const T vxc = (T)0.25 * (((VXO(ix, iy - 1, iz) + VXO(ix + 1, iy - 1, iz)) + vx000) + vx100);
+                const T vzc = (T)0.25 * (((VZO(ix, iy - 1, iz) + VZO(ix, iy - 1, iz + 1)) + vz000) + vz001);
+                (Vy + bVy)[oVy] = mc_node<T, true>(w, 1, Vy_o, Vy_h, vy000, vxc, vy000, vzc, dt, g, ix, iy, iz, nx, ny + 1, nz);
+            } else (Vy + bVy)[oVy] = (Vy_h + bVy)[oVy];
+            if (iz > 1) { // multi.jl:230-235 with the third branch corrected: Vz
+                const T vxc = (T)0.25 * (((VXO(ix, iy, iz - 1) + VXO(ix + 1, iy, iz - 1)) + vx000) + vx100);
+                const T vyc = (T)0.25 * (((VYO(ix, iy, iz - 1) + VYO(ix, iy + 1, iz - 1)) + vy000) + vy010);
+                (Vz + bC)[oC] = mc_node<T, true>(w, 2, Vz_o, Vz_h, vz000, vxc, vyc, vz000, dt, g, ix, iy, iz, nx, ny, nz + 1);
+            } else (Vz + bC)[oC] = (Vz_h + bC)[oC];
+            { // multi.jl:236-241
+                const T vxc = (T)0.5 * (vx000 + vx100), vyc = (T)0.5 * (vy000 + vy010), vzc = (T)0.5 * (vz000 + vz001);
+                (C + bC)[oC] = mc_node<T, true>(w, 3, C_o, C_h, w.get(3, ix, iy, iz), vxc, vyc, vzc, dt, g, ix, iy, iz, nx, ny, nz);
+            }
+            // the far faces of the staggered arrays are outside the advected sets
+            if (ix == nx) (Vx + bVx)[oVx + 1] = (Vx_h + bVx)[oVx + 1];
+            if (iy == ny) (Vy + bVy)[oVy + nx] = (Vy_h + bVy)[oVy + nx];
+            if (iz == nz) (Vz + bC + pC)[oC] = (Vz_h + bC + pC)[oC];
+        }
+        publish(iz + 2, nxt);
+        __syncthreads();
+    }
+#undef VXO
+#undef VYO
+#undef VZO
+}
+
+// Vx, Vy, Vz, C ← stage 2 from the old fields *_o and stage 1's complete result *_h; twelve distinct arrays.  The launch is shaped
+// like advect()'s: the same tile, the same planes per workgroup on small grids, NS3D_ADVECT_GLOBAL=1 for the global gather.
+template <class T>
+hipError_t advect_mc(hipStream_t s, T *Vx, const T *Vx_o, const T *Vx_h, T *Vy, const T *Vy_o, const T *Vy_h, T *Vz, const T *Vz_o,
+                     const T *Vz_h, T *C, const T *C_o, const T *C_h, double dt, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    const char *glob = std::getenv("NS3D_ADVECT_GLOBAL");       // read per call, like advect()
+    if (glob && *glob == '1') {
+        hipLaunchKernelGGL(k_advect_mc_global<T>, grid3(nx + 1, ny + 1, nz + 1, BLK3), BLK3, 0, s, Vx, Vx_o, Vx_h, Vy, Vy_o, Vy_h, Vz, Vz_o,
+                           Vz_h, C, C_o, C_h, (T)dt, make_geo<T>(dx, dy, dz), nx, ny, nz);
+        return hipGetLastError();
+    }
+    typedef AdvWin2<T> W;
+    const size_t lds = (size_t)4 * W::NSLOT * W::PLANE * sizeof(T);
+    hipError_t ea = hipFuncSetAttribute((const void *)k_advect_mc<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return ea;
+    static const int kz_env = std::getenv("NS3D_ADVECT_KZ") ? std::atoi(std::getenv("NS3D_ADVECT_KZ")) : 0;
+    const int kz = kz_env > 0 ? kz_env : window_kz(((nx + W::TX - 1) / W::TX) * ((ny + W::TY - 1) / W::TY), nz, nz >= 128 ? 64 : 32);
+    const dim3 blk(W::TX, W::TY, 1);
+    const dim3 grd((unsigned)((nx + W::TX - 1) / W::TX), (unsigned)((ny + W::TY - 1) / W::TY), (unsigned)((nz + kz - 1) / kz));
+    hipLaunchKernelGGL(k_advect_mc<T>, grd, blk, lds, s, Vx, Vx_o, Vx_h, Vy, Vy_o, Vy_h, Vz, Vz_o, Vz_h, C, C_o, C_h, (T)dt,
+                       make_geo<T>(dx, dy, dz), nx, ny, nz, kz);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // A[2:end-1,2:end-1,2:end-1] packed (what gather! receives per rank, multi.jl:399-403): one thread per inner cell
 // ---------------------------------------------------------------------------------------------------------
@@ -4520,6 +4752,8 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
     template hipError_t bc_fused<T>(hipStream_t, int, int, T *, T *, T *, int, int, int, int, double, double, double, int); \
     template hipError_t advect<T>(hipStream_t, T *, const T *, T *, const T *, T *, const T *, T *,          \
                                   const T *, double, double, double, double, int, int, int, int, int, int);  \
+    template hipError_t advect_mc<T>(hipStream_t, T *, const T *, const T *, T *, const T *, const T *, T *, const T *, const T *, T *, \
+                                     const T *, const T *, double, double, double, double, int, int, int);   \
     template hipError_t pt_sweep<T>(hipStream_t, int, const T *, T *, T *, const T *, const ns3d_pt_params &,\
                                     int, int);                                                               \
     template hipError_t pt_persist<T>(hipStream_t, const T *, T *, const T *, T *, const T *, const ns3d_pt_params &, int, ns3d_persist_state *, \

@@ -170,6 +170,11 @@ hipError_t emit(hipStream_t, const T *A, const T *B, const ns3d_iso_geom &, doub
     template <class T>                                                                                       \
     hipError_t advect(hipStream_t, T *, const T *, T *, const T *, T *, const T *, T *, const T *, double,   \
                       double, double, double, int, int, int, int, int koff, int nzg);                        \
+    /* stage 2 of the limited MacCormack advection: new fields from the old ones (*_o) and stage 1's complete result (*_h) */ \
+    template <class T>                                                                                       \
+    hipError_t advect_mc(hipStream_t, T *Vx, const T *Vx_o, const T *Vx_h, T *Vy, const T *Vy_o, const T *Vy_h, T *Vz, \
+                         const T *Vz_o, const T *Vz_h, T *C, const T *C_o, const T *C_h, double dt, double dx, double dy, \
+                         double dz, int nx, int ny, int nz);                                                  \
     template <class T>                                                                                       \
     hipError_t pt_sweep(hipStream_t, int variant, const T *, T *, T *, const T *, const ns3d_pt_params &,    \
                         int k0, int k1);                                                                     \

@@ -193,7 +193,7 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
-                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None):
+                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None, advection="reference"):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -254,7 +254,13 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     variable-length gather across processes is not provided).  A rank reads its arrays as the step leaves them, halo cells
     included: :477 does not update C's halo, so next to a seam a surface of C, or coloured by it, is that of the rank's own copy.
     do_save adds out_iso_%04d.ply per saved frame (same directory
-    and counter as the .bin files).  `one_call` stays in use; read-only: every other result keeps its bits."""
+    and counter as the .bin files).  `one_call` stays in use; read-only: every other result keeps its bits.
+    advection="maccormack" (default "reference": not one extra call; OUTSIDE the reference): :475-476 run as the limited MacCormack
+    scheme (ns3d_advect_mc: second order where the reference's backtrack! is first order; include/ns3d.h has the definition) — with
+    `one_call` inside ns3d_time_step (Context.set_advection), otherwise as one advect_mc call per step; the same bits either way.  It
+    advects Vz, so it needs faithful=False, and it runs on one rank: anything else raises Ns3dError before the first step.  Every
+    observer keyword keeps working."""
+    _check_advection(advection)
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -266,6 +272,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     watch = dict(statistics=statistics, stats_every=stats_every, vortex=vortex, tracers=tracers, probes=probes, isosurface=isosurface)
     check_options(grid, **watch)
     P, dims, mg, root = grid.P, tuple(grid.dims), grid.mg, grid.is_root()
+    maccormack = _check_advection(advection, faithful, P)
     # the contexts of the ns3d_mgpu's ranks (their devices), or this rank's own
     ctxs = list(grid.contexts) if grid.contexts is not None else [K.Context(device, mode, async_=True)]
     ps = [multi_params(nx, dims=dims, coords=c3, **shape) for c3 in grid.local_coords]
@@ -347,6 +354,11 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     step_params = None
     if fused and one_call and P == 1 and mg is None and not diagnostics:
         step_params = _step_params(L.NS3D_BC_MULTI, p, niter, faithful, pressure)
+    hats = None
+    if maccormack and step_params is not None:
+        ctxs[0].set_advection("maccormack")                     # ns3d_time_step advects with it; back to the default after the loop
+    elif maccormack:
+        hats = _alloc_hats(fs[0], ctxs[0])
     for it in range(1, nt + 1):                                                               # :446
         if step_params is not None:                             # :449-477 (ns3d_time_step swaps the names in fs[0] like the swaps below)
             step_params.write_stress = 1 if it == nt else 0     # the stress arrays as the reference leaves them after its last step
@@ -422,6 +434,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             for f, c in zip(fs, ctxs):
                 if wide_advect_halo and P > 1:
                     break
+                if maccormack:  # :475-476 as the limited MacCormack scheme (one rank): stage 1 into the hat buffers, stage 2, the roles swap
+                    _advect_mc_swap(f, hats, p, c)
+                    continue
                 if fused:       # :475-476 in one pass (ns3d_copy_advect): complete new fields into the *_o buffers, then the roles swap
                     _copy_advect_swap(f, p, faithful, c)
                     continue
@@ -435,6 +450,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             _print_step(it, errs if fused or pressure != "direct" else [], p.nchk, info.diag[-1] if monitor else None)
         obs.end_step(it, fs)
         frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
+    if maccormack and step_params is not None:
+        ctxs[0].set_advection("reference")
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
             K.copy(f.Vz_o, f.Vz, ctx=c)     # the one copy of :475 the swaps skipped (Vz is never advected): same final state
@@ -471,6 +488,37 @@ def _copy_advect_swap(f, p, faithful, ctx):
         f.Vz, f.Vz_o = f.Vz_o, f.Vz
 
 
+def _check_advection(advection, faithful=False, P=1):
+    """the `advection` keyword of both drivers → whether the MacCormack scheme runs; raises before anything is allocated or advanced"""
+    if advection not in ("reference", "maccormack"):
+        raise L.Ns3dError("advection = %r (\"reference\" | \"maccormack\")" % (advection,))
+    if advection == "reference":
+        return False
+    if faithful:
+        raise L.Ns3dError("advection=\"maccormack\" advects Vz: it needs faithful=False")
+    if P != 1:
+        raise L.Ns3dError("advection=\"maccormack\" runs on one rank (this grid has %d): the hat fields of its first stage would need "
+                          "a halo exchange between the stages" % P)
+    return True
+
+
+def _alloc_hats(f, ctx):
+    """buffers for stage 1 of the MacCormack advection (Vx, Vy, Vz, C) when the step runs call by call"""
+    hats = tuple(K.zeros(tuple(a.shape), a.dtype, a.device) for a in (f.Vx, f.Vy, f.Vz, f.C))
+    ctx.after_torch_fill()
+    return hats
+
+
+def _advect_mc_swap(f, hats, p, ctx):
+    """{X_o .= X; advect!} (multi.jl:475-476 / gpu.jl:141-142) replaced by the limited MacCormack advection: ns3d_advect_mc reads the
+    current fields, leaves stage 1 in `hats` and writes COMPLETE new fields into the *_o buffers, then all four names swap."""
+    K.advect_mc(f.Vx_o, f.Vx, hats[0], f.Vy_o, f.Vy, hats[1], f.Vz_o, f.Vz, hats[2], f.C_o, f.C, hats[3], p.dt, p.dx, p.dy, p.dz, ctx=ctx)
+    f.Vx, f.Vx_o = f.Vx_o, f.Vx
+    f.Vy, f.Vy_o = f.Vy_o, f.Vy
+    f.Vz, f.Vz_o = f.Vz_o, f.Vz
+    f.C, f.C_o = f.C_o, f.C
+
+
 def gpu_initial_fields(p):
     """gpu.jl:62-63,85-88: LinRange cell centres, 1/7-power-law Vx profile, hydrostatic Pr (host setup)."""
     nx, ny, nz = p.nx, p.ny, p.nz
@@ -499,7 +547,8 @@ def _save_mat(path, f, p, step0):
 
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
-          diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None):
+          diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None,
+          advection="reference"):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -515,7 +564,9 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     tracers / probes: as in run_navierstokes3D, advanced resp. sampled after :142; do_save adds out_save/out_tracers_%04d.bin beside
     each MAT file (numbered 0, 1, … in the order the MAT files are written), do_vis 3D_NavierStokes_tracers_%04d.png per frame.
     isosurface: as in run_navierstokes3D, of the final state → info.isosurface; do_save adds out_save/out_iso_%04d.ply beside each
-    MAT file (numbered like the tracer dumps)."""
+    MAT file (numbered like the tracer dumps).
+    advection: as in run_navierstokes3D, in place of :141-142; "maccormack" needs faithful=False."""
+    maccormack = _check_advection(advection, faithful)
     if device is None:
         device = torch.cuda.current_device()
     p = gpu_params(nx)
@@ -562,6 +613,11 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     step_params = None
     if fused and one_call and not diagnostics:
         step_params = _step_params(L.NS3D_BC_GPU, p, niter, faithful, pressure)
+    hats = None
+    if maccormack and step_params is not None:
+        ctx.set_advection("maccormack")                     # ns3d_time_step advects with it (the context is this run's own)
+    elif maccormack:
+        hats = _alloc_hats(f, ctx)
     for it in range(1, nt + 1):                                                               # :119
         if step_params is not None:                         # :121-142 (ns3d_time_step swaps the names in f like the swaps below)
             step_params.write_stress = 1 if it == nt else 0
@@ -604,7 +660,9 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             K.set_bc_Vel_gpu(f.Vx, f.Vy, f.Vz, ctx=ctx)                                       # :140
             if monitor:
                 info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
-            if fused:
+            if maccormack:
+                _advect_mc_swap(f, hats, p, ctx)                                              # :141-142 as the limited MacCormack scheme
+            elif fused:
                 _copy_advect_swap(f, p, faithful, ctx)                                        # :141-142 in one pass
             else:
                 K.copy(f.Vx_o, f.Vx, ctx=ctx); K.copy(f.Vy_o, f.Vy, ctx=ctx)                  # :141

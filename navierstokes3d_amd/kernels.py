@@ -196,6 +196,17 @@ class Context:
         (<= 0: the default bound)."""
         L.check(self.lib.ns3d_set_pt_pace_test(self.handle, int(extra_arrivals), int(ticks)))
 
+    def set_advection(self, scheme):
+        """What ns3d_time_step advects with: "reference" (ns3d_copy_advect, the default) or "maccormack" (the limited second-order
+        scheme of advect_mc; the step then needs faithful = 0).  The single calls do not read it."""
+        codes = {"reference": L.NS3D_ADVECT_REFERENCE, "maccormack": L.NS3D_ADVECT_MACCORMACK}
+        if scheme not in codes:
+            raise L.Ns3dError("advection = %r (\"reference\" | \"maccormack\")" % (scheme,))
+        L.check(self.lib.ns3d_set_advection(self.handle, codes[scheme]))
+
+    def advection(self):
+        return {L.NS3D_ADVECT_REFERENCE: "reference", L.NS3D_ADVECT_MACCORMACK: "maccormack"}[int(self.lib.ns3d_advection(self.handle))]
+
     def set_pt_depth(self, depth):
         """PT iterations per pass over memory in pt_iterate / pt_solve: 0 automatic, 1…4 forced (5: float32 fields only)."""
         L.check(self.lib.ns3d_set_pt_depth(self.handle, int(depth)))
@@ -399,6 +410,29 @@ def copy_advect(Vx_new, Vx, Vy_new, Vy, Vz_new, Vz, C_new, Cf, dt, dx, dy, dz, f
                        _chk(Vz_new, (nx, ny, nz + 1), "Vz_new"), _chk(Vz, (nx, ny, nz + 1), "Vz"),
                        _chk(C_new, (nx, ny, nz), "C_new"), _chk(Cf, None, "C"), *_d(dt, dx, dy, dz), nx, ny, nz,
                        1 if faithful else 0)
+
+
+def _mc_args(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, Cf, C_hat):
+    nx, ny, nz = Cf.shape
+    out = []
+    for shape, name, trio in (((nx + 1, ny, nz), "Vx", (Vx_new, Vx, Vx_hat)), ((nx, ny + 1, nz), "Vy", (Vy_new, Vy, Vy_hat)),
+                              ((nx, ny, nz + 1), "Vz", (Vz_new, Vz, Vz_hat)), ((nx, ny, nz), "C", (C_new, Cf, C_hat))):
+        out += [_chk(t, shape, name + tag) for t, tag in zip(trio, ("_new", "", "_hat"))]
+    return out, (nx, ny, nz)
+
+
+def advect_correct(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, Cf, C_hat, dt, dx, dy, dz, ctx=None):
+    """Stage 2 of the limited MacCormack advection (ns3d_advect_correct; include/ns3d.h has the definition): the *_hat arrays hold
+    copy_advect(…, faithful=False) of the current fields, the *_new arrays receive the complete new fields.  Twelve distinct arrays."""
+    args, n = _mc_args(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, Cf, C_hat)
+    _ctx(ctx, Cf).call("advect_correct", Cf, *args, *_d(dt, dx, dy, dz), *n)
+
+
+def advect_mc(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, Cf, C_hat, dt, dx, dy, dz, ctx=None):
+    """Limited MacCormack advection, second order (ns3d_advect_mc): stage 1 — copy_advect(…, faithful=False) — into the *_hat
+    arrays, then stage 2 into the *_new arrays; the caller swaps the roles of X_new and X afterwards, like after copy_advect."""
+    args, n = _mc_args(Vx_new, Vx, Vx_hat, Vy_new, Vy, Vy_hat, Vz_new, Vz, Vz_hat, C_new, Cf, C_hat)
+    _ctx(ctx, Cf).call("advect_mc", Cf, *args, *_d(dt, dx, dy, dz), *n)
 
 
 # ---- the reference's host sequences, one library call each ----------------------------------------------

@@ -11,6 +11,7 @@ NS3D_ERR_ARG, NS3D_ERR_HIP, NS3D_ERR_STATE, NS3D_ERR_RCCL = 1, 2, 3, 4
 NS3D_UNIQUE_ID_BYTES = 128
 NS3D_STRICT, NS3D_FAST, NS3D_ASYNC, NS3D_IEEE_DIV = 0x0, 0x1, 0x2, 0x4
 NS3D_BC_MULTI, NS3D_BC_GPU = 0, 1
+NS3D_ADVECT_REFERENCE, NS3D_ADVECT_MACCORMACK = 0, 1
 
 
 class Ns3dError(RuntimeError):
@@ -108,12 +109,15 @@ DERIVED_SIGNATURES = {
     "isosurface": [_P] * 2 + [_I] * 3 + [C.POINTER(_I)] * 2 + [_D] + [_P] * 2 + [C.c_longlong, C.POINTER(C.c_longlong)],
     "sample_at": [_P] * 3 + [_L, _P] + [_I] * 6 + [C.POINTER(_I)],
     "tracers_advance_at": [_P] * 3 + [_L] + [_P] * 3 + [_D] * 3 + [_I] * 3 + [C.POINTER(_I)] * 2,
+    # the limited MacCormack advection, beside the reference's advect / copy_advect above
+    "advect_correct": [_P] * 12 + [_D] * 4 + [_I] * 3,
+    "advect_mc": [_P] * 12 + [_D] * 4 + [_I] * 3,
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
                    "ns3d_set_pt2_variant", "ns3d_set_ptn_variant", "ns3d_set_pt_depth", "ns3d_set_graph_mode", "ns3d_set_autotune", "ns3d_last_pt2_variant", "ns3d_last_ptn_variant", "ns3d_last_pt_depth",
                    "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
-                   "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test",
+                   "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test", "ns3d_set_advection", "ns3d_advection",
                    "ns3d_stats_reset", "ns3d_stats_finalize"]
 NS3D_STATS_SLOTS = 11
 
@@ -221,6 +225,10 @@ def load():
     lib.ns3d_last_pt_pace.restype = _I
     lib.ns3d_set_pt_pace_test.argtypes = [_P, _I, _I]
     lib.ns3d_set_pt_pace_test.restype = _I
+    lib.ns3d_set_advection.argtypes = [_P, _I]
+    lib.ns3d_set_advection.restype = _I
+    lib.ns3d_advection.argtypes = [_P]
+    lib.ns3d_advection.restype = _I
     lib.ns3d_cached_graphs.argtypes = [_P]
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
