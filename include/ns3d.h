@@ -108,7 +108,8 @@ const char *ns3d_last_error(void);
 /* Context = device + stream + scratch.  Replaces @init_parallel_stencil (gpu.jl:4-8).
  * Device arrays need only the alignment of their element type (8 bytes for _f64 arrays, 4 for _f32, 1 for the tracers' uint8 state):
  * a view into a larger buffer is a valid argument.  A call neither loads from nor stores to addresses outside the arrays passed
- * to it and the context's own scratch (tests/test_gpu_footprint.py runs every entry point in guarded arenas at that alignment). */
+ * to it and the context's own scratch (tests/test_gpu_footprint.py runs every single-rank entry point in guarded arenas at that
+ * alignment, tests/test_gpu_footprint_mgpu.py the ns3d_mgpu entry points with all ranks' arrays in one arena). */
 ns3d_ctx *ns3d_create(int device, int flags);
 void ns3d_destroy(ns3d_ctx *ctx);
 int ns3d_flags(const ns3d_ctx *ctx);

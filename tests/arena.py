@@ -12,9 +12,10 @@ nothing outside the arrays it was given.  Tensors that PyTorch allocates one by 
   - every gap is at least one plane plus one row of the largest array of the call, then widened until the next array starts at an
     ODD element offset from the 512-byte-aligned start of the buffer: float64 arrays are 8-byte aligned, float32 arrays 4-byte
     aligned, uint8 arrays sit on an odd byte, and none of them any better;
-  - guards hold a quiet NaN with a fixed payload (GUARD: one bit pattern per element width, one fixed byte for uint8) and are
-    compared as integers after the call.  The NaN is a second check: an out-of-bounds LOAD whose value reaches an output through
-    arithmetic (x·0, a late select) poisons that output, which the caller's bit comparison of the outputs then catches.
+  - guards hold a quiet NaN with a fixed payload (GUARD: one bit pattern per element width, one fixed byte for uint8, one large
+    positive word for int64 — the tracers' id arrays hold −1 and particle numbers, never that) and are compared as integers after
+    the call.  The NaN is a second check: an out-of-bounds LOAD whose value reaches an output through arithmetic (x·0, a late
+    select) poisons that output, which the caller's bit comparison of the outputs then catches.
 
 check() names the array, the side and the first and last dirtied offsets as signed distances from the array (−1 = the element just
 before its first, +1 = the element just behind its last), in elements and in planes / rows / elements of that array, so that a failure
@@ -31,10 +32,11 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-GUARD = {torch.float64: 0x7FF8_0000_DEAD_BEEF, torch.float32: 0x7FC0_BEEF, torch.uint8: 0xA5}
-_INT = {torch.float64: torch.int64, torch.float32: torch.int32, torch.uint8: torch.uint8}
-_NPINT = {torch.float64: np.int64, torch.float32: np.int32, torch.uint8: np.uint8}
-_TORCH = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8}
+GUARD = {torch.float64: 0x7FF8_0000_DEAD_BEEF, torch.float32: 0x7FC0_BEEF, torch.uint8: 0xA5, torch.int64: 0x5AA5_0000_DEAD_BEEF}
+_INT = {torch.float64: torch.int64, torch.float32: torch.int32, torch.uint8: torch.uint8, torch.int64: torch.int64}
+_NPINT = {torch.float64: np.int64, torch.float32: np.int32, torch.uint8: np.uint8, torch.int64: np.int64}
+_TORCH = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8,
+          np.dtype(np.int64): torch.int64}
 MIN_GAP = 64                                    # elements; what a call without a column-major array gets (never the case in the suite)
 
 Slot = namedtuple("Slot", "name dtype offset numel shape colmajor output")
@@ -112,7 +114,7 @@ class Arena:
         out = []
         for dt, buf in self.buf.items():
             host = buf.view(_INT[dt]).cpu().numpy().view(_NPINT[dt])
-            want = _NPINT[dt](GUARD[dt])                                    # both NaN patterns are positive as signed integers
+            want = _NPINT[dt](GUARD[dt])                                    # every guard pattern is positive as a signed integer
             slots = sorted((s for s in self.slots.values() if s.dtype == dt), key=lambda s: s.offset)
             for q, s in enumerate(slots):
                 row, plane = (s.shape[0], s.shape[0] * s.shape[1]) if s.colmajor else (0, 0)

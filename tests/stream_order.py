@@ -16,7 +16,19 @@ positions inside the box, states in {0, 1}: a call that reads it computes a wron
 
 The expected bits are those of the same call on the null stream with the real inputs and a synchronisation after it; the same run of
 the decoy tells a failure what it is looking at.  Nothing here imports torch at module level: the pure parts are tested on the host
-(tests/test_stream_order_host.py)."""
+(tests/test_stream_order_host.py).
+
+The multi-rank half (RankCase, expected_ranks, measured_ranks; tests/test_gpu_stream_order_mgpu.py) runs the same five steps on the P
+virtual ranks of one MultiGpu: every array exists once per rank, every rank has a decoy set of its own seed, and the delay and the
+late copy-in go on the stream each LATE rank computes on — all ranks, or one rank alone, so that its neighbours are on time and only
+the wait for the late sender's "ready" event keeps them from pulling the decoy's planes.  Two stream set-ups:
+  "follow"  own_streams=False, the call made inside `with torch.cuda.stream(S)`: every rank computes on S;
+  "own"     own_streams=True: rank l computes on mg._own[l].  In this set-up MultiGpu._follow_torch_streams synchronises PyTorch's
+            CURRENT stream on the host before every call, so the delay and the copy-in must go on mg._own[l], never on the current
+            stream: a delay enqueued there would simply be waited for, and the run would prove nothing.
+The canary copies the late ranks' arrays on a stream that shares a hardware queue with none of the late ranks' streams — and, when
+it is taken after a call that only enqueues, with none of the on-time ranks' either: those wait for the late rank's events by then
+(independent_of_all); the verdict is taken rank by rank with the rank in the message (verdict_ranks)."""
 import math
 from types import SimpleNamespace
 
@@ -24,7 +36,8 @@ import numpy as np
 
 # Target length of the delay per measured call, in milliseconds: four times the smallest value of 5, 10, 20, … at which every canary
 # of test_gpu_stream_order.py saw the decoy in three consecutive runs of the module on the MI355X (profiles/stream_order_delay.txt),
-# capped at DELAY_CAP_MS.  Measured: 5 ms passed three times, so 4 × 5.
+# capped at DELAY_CAP_MS.  Measured: 5 ms passed three times, so 4 × 5.  test_gpu_stream_order_mgpu.py is measured by the same rule
+# and uses the same constant: the larger of the two modules' values (both measurements are in the profile).
 DELAY_MS = 20.0
 DELAY_CAP_MS = 200.0
 DELAY_BYTES = 64 << 20          # the scratch tensor of the delay's in-place adds
@@ -163,6 +176,80 @@ def verdict(what, got, want, decoy_want, canary, dec, result=None, want_result=N
             early = decoy_result is not None and same_result(result, decoy_result)
             out.append("%s: returned %r, expected %r%s" % (what, result, want_result,
                                                            " — equals the decoy run: the inputs were read early" if early else ""))
+    return out
+
+
+# ---- the multi-rank pure parts -----------------------------------------------------------------------------------------------------
+RANK_SEED = 1009                # rank l's decoy set is drawn from seed + RANK_SEED·(l + 1): no two ranks share a decoy
+
+
+def topo_of(topo):
+    """(dims or P, (nx, ny, nz)) → (dims or None for z-slabs, P, local grid)"""
+    d, n = topo
+    n = tuple(int(q) for q in n)
+    if isinstance(d, (tuple, list)):
+        d = tuple(int(q) for q in d)
+        return d, d[0] * d[1] * d[2], n
+    return None, int(d), n
+
+
+def late_sets(P, setup):
+    """The sets of late ranks of one case.  "follow": all ranks (they share the stream).  "own": all ranks, then single ranks — rank
+    0, rank P−1 and for P = 3 the middle one: the others are on time and would pull early but for the sender's "ready" event.
+    More than three ranks with streams of their own leave no hardware queue (four here) for the canary when ALL are late: the lower
+    and the upper half are late in turn instead."""
+    P = int(P)
+    allr = frozenset(range(P))
+    if setup == "follow" or P == 1:
+        return [allr]
+    if setup != "own":
+        raise ValueError("late_sets: set-up %r" % (setup,))
+    sets = [allr] if P <= 3 else [frozenset(range(P // 2)), frozenset(range(P // 2, P))]
+    singles = [0, P - 1] + ([1] if P == 3 else [])
+    return sets + [frozenset([l]) for l in singles]
+
+
+class RankCase:
+    """name; topo (dims or P, local grid); arrays [(name, [real host array per rank], role)]; call(hip, mg, t) → host result, t[name]
+    the list of device arrays in local-rank order; blocking: the call blocks (canary before it); setup(mg): settings the case needs
+    on every MultiGpu it runs on; seed: of the decoys.  real[l] / decoy[l]: {name: array} of rank l."""
+
+    def __init__(self, name, topo, arrays, call, blocking=False, setup=None, seed=0):
+        self.name, self.topo, self.call, self.blocking, self.setup, self.seed = name, topo, call, bool(blocking), setup, seed
+        self.dims, self.P, self.n = topo_of(topo)
+        self.arrays = [(n, [np.asarray(a) for a in per_rank], role) for n, per_rank, role in arrays]
+        assert all(len(per_rank) == self.P for _, per_rank, _ in self.arrays), (name, "one array per rank")
+        self.names = [n for n, _, _ in self.arrays]
+        self.real, self.decoy = [], []
+        for l in range(self.P):
+            mine = self.rank_arrays(l)
+            dec = decoy_set(mine, seed + RANK_SEED * (l + 1))
+            bad = check_decoy(mine, dec)
+            assert not bad, (name, l, bad)
+            self.real.append({n: a for n, a, _ in mine})
+            self.decoy.append(dec)
+        for n in self.names:                    # … and no rank's decoy is another rank's
+            for l in range(self.P):
+                for k in range(l):
+                    assert not (self.decoy[l][n].size and bits_same(self.decoy[l][n], self.decoy[k][n])), (name, n, l, k)
+
+    def rank_arrays(self, l):
+        return [(n, per_rank[l], role) for n, per_rank, role in self.arrays]
+
+
+def verdict_ranks(what, got, want, decoy_want, canary, decoys, late, result=None, want_result=None, decoy_result=None):
+    """verdict() rank by rank.  got / want / decoy_want / decoys: one {name: array} per rank; canary: {rank: {name: array}} of the
+    LATE ranks.  Every late rank's canary is judged before anything else: one that does not hold the decoy ends the judgement.  The
+    host result belongs to no rank: it is judged once."""
+    out = []
+    for l in sorted(late):
+        out += verdict("%s, rank %d" % (what, l), {}, {}, None, canary[l], decoys[l])
+    if out:
+        return out
+    for l in range(len(want)):
+        out += verdict("%s, rank %d" % (what, l), got[l], want[l], None if decoy_want is None else decoy_want[l], {}, {})
+    if want_result is not None or result is not None:
+        out += verdict(what, {}, {}, None, {}, {}, result, want_result, decoy_result)
     return out
 
 
@@ -340,3 +427,163 @@ def measured(hip, case, ctx, S, delay, variant="reader", delay_stream=None, read
     D.synchronize()
     S.synchronize()
     return r, {n: download(hip, res[n]) for n in names}, {n: download(hip, can[n]) for n in names}
+
+
+# ---- the multi-rank device side ----------------------------------------------------------------------------------------------------
+def independent_of_all(busy, delay, avoid=(), tries=16):
+    """independent_stream for several busy streams: a torch stream that shares a hardware queue with NONE of them (each is asked
+    in turn, as independent_stream asks one)."""
+    import torch
+    distinct = []
+    for b in busy:
+        if b.cuda_stream not in {d.cuda_stream for d in distinct}:
+            distinct.append(b)
+    seen = {b.cuda_stream for b in distinct} | {a.cuda_stream for a in avoid}
+    for _ in range(tries):
+        X = torch.cuda.Stream(0)
+        if X.cuda_stream in seen:
+            continue
+        seen.add(X.cuda_stream)
+        free = True
+        for b in distinct:
+            delay.enqueue(b, delay.n_probe)
+            eb, ex = torch.cuda.Event(), torch.cuda.Event()
+            eb.record(b)
+            ex.record(X)
+            ex.synchronize()
+            free = not eb.query()
+            b.synchronize()
+            if not free:
+                break
+        if free:
+            return X
+    raise AssertionError("no stream independent of the %d busy ones among %d candidates" % (len(distinct), tries))
+
+
+def grid_on(hip, case, setup, async_=True):
+    """(MultiGpu of the case's topology, [the torch stream rank l computes on], the stream to make the call under or None) for the
+    set-up "follow" — every rank follows PyTorch's current stream, which is a new non-default stream S while the call is made — or
+    "own" — own_streams=True, rank l on mg._own[l]."""
+    import torch
+    from navierstokes3d_amd.mgpu import MultiGpu
+    torch.cuda.synchronize()
+    mg = MultiGpu.create([0] * case.P, *case.n, "strict", async_=async_, dims=case.dims, own_streams=(setup == "own"))
+    if case.setup:
+        case.setup(mg)
+    if setup == "own":
+        return mg, list(mg._own), None
+    if setup != "follow":
+        raise ValueError(setup)
+    S = torch.cuda.Stream(0)
+    return mg, [S] * case.P, S
+
+
+def _call(hip, case, mg, t, under):
+    import contextlib
+    import torch
+    with (torch.cuda.stream(under) if under is not None else contextlib.nullcontext()):
+        return case.call(hip, mg, t)
+
+
+def upload_ranks(hip, case, host):
+    return {n: [upload(hip, host[l][n]) for l in range(case.P)] for n in case.names}
+
+
+def sync_run_ranks(hip, case, mg, host):
+    """the call as the value tests make it — inputs uploaded, torch.cuda.synchronize(), the call, mg.sync() — with host[l] as rank
+    l's arrays: (result, [{name: array} per rank])"""
+    import torch
+    t = upload_ranks(hip, case, host)
+    torch.cuda.synchronize()
+    r = case.call(hip, mg, t)
+    mg.sync()
+    torch.cuda.synchronize()
+    return r, [{n: download(hip, t[n][l]) for n in case.names} for l in range(case.P)]
+
+
+def expected_ranks(hip, case, own):
+    """(result, arrays per rank) of the real sets and of the decoy sets on a fresh MultiGpu of the case's topology"""
+    mg, _, _ = grid_on(hip, case, "own" if own else "follow")
+    want = sync_run_ranks(hip, case, mg, case.real)
+    dwant = sync_run_ranks(hip, case, mg, case.decoy)
+    mg.sync()
+    mg.close()
+    return want, dwant
+
+
+def warm_up_ranks(hip, case, mg, under=None):
+    """the same call once on scratch copies, synchronised: lazy buffers (which synchronise every rank when they grow), modules and
+    plans exist before the measured call"""
+    import torch
+    t = upload_ranks(hip, case, case.real)
+    torch.cuda.synchronize()
+    _call(hip, case, mg, t, under)
+    mg.sync()
+    torch.cuda.synchronize()
+
+
+def measured_ranks(hip, case, mg, streams, delay, late, variant="reader", under=None, delay_streams=None, overwrite=True):
+    """Steps 1-5 of the module docstring on the ranks of `mg`.  streams[l]: the torch stream rank l computes on; late: the ranks whose
+    inputs arrive behind the delay (the others' are copied in on their own stream at once); under: the stream the call is made
+    under (set-up "follow"); delay_streams {rank: stream}: where a late rank's delay and copy-in go instead of streams[l] (the
+    negative controls).  Returns (result, [arrays read per rank], {late rank: canary})."""
+    import torch
+    P, names = case.P, case.names
+    late = sorted(late)
+    t = upload_ranks(hip, case, case.decoy)
+    real_d, dec_d = upload_ranks(hip, case, case.real), upload_ranks(hip, case, case.decoy)
+    res = {n: [torch.empty_like(x) for x in t[n]] for n in names}
+    can = {n: {l: torch.empty_like(t[n][l]) for l in late} for n in names}
+    D = [streams[l] if not (delay_streams and l in delay_streams) else delay_streams[l] for l in range(P)]
+    # The canary's stream: behind none of the delays.  Taken AFTER a call that only enqueues, it must not queue up behind an on-time
+    # rank either: that rank's stream is by then waiting for the late neighbour's events, that is for the delay
+    busy = [D[l] for l in late] + ([] if case.blocking else list(streams))
+    S2 = independent_of_all(busy, delay, avoid=list(streams) + D)
+    torch.cuda.synchronize()                # the uploads (null stream) are done; from here on no stream waits for another
+
+    def canary():
+        with torch.cuda.stream(S2):
+            for n in names:
+                for l in late:
+                    can[n][l].copy_(t[n][l])
+
+    delayed = set()
+    for l in late:
+        if D[l].cuda_stream not in delayed:
+            delayed.add(D[l].cuda_stream)
+            delay.enqueue(D[l])
+    for l in range(P):
+        with torch.cuda.stream(D[l]):
+            for n in names:
+                t[n][l].copy_(real_d[n][l])
+    if case.blocking:
+        canary()
+    r = _call(hip, case, mg, t, under)
+    if not case.blocking:
+        canary()
+    if variant == "reader":
+        for l in range(P):
+            with torch.cuda.stream(streams[l]):
+                for n in names:
+                    res[n][l].copy_(t[n][l])
+        if overwrite:                       # every rank has read before any rank overwrites only in stream order: that is the point
+            for l in range(P):
+                with torch.cuda.stream(streams[l]):
+                    for n in names:
+                        t[n][l].copy_(dec_d[n][l])
+        for s in streams:
+            s.synchronize()
+    elif variant in ("sync", "return"):     # "return": a MultiGpu without NS3D_ASYNC — the call itself has waited
+        if variant == "sync":
+            mg.sync()
+        with torch.cuda.stream(S2):
+            for n in names:
+                for l in range(P):
+                    res[n][l].copy_(t[n][l])
+    else:
+        raise ValueError(variant)
+    S2.synchronize()
+    for s in D + list(streams):
+        s.synchronize()
+    got = [{n: download(hip, res[n][l]) for n in names} for l in range(P)]
+    return r, got, {l: {n: download(hip, can[n][l]) for n in names} for l in late}

@@ -7,7 +7,7 @@ import torch
 import arena as AR
 from util import rnd
 
-ESZ = {torch.float64: 8, torch.float32: 4, torch.uint8: 1}
+ESZ = {torch.float64: 8, torch.float32: 4, torch.uint8: 1, torch.int64: 8}
 
 
 def sample_arrays():
@@ -105,6 +105,40 @@ def test_layout_on_cpu_tensors():
 def test_reports_on_cpu_tensors():
     arrays = sample_arrays()
     check_reports(AR.Arena(arrays, "cpu"), arrays)
+
+
+def int64_arrays():
+    """the tracers' migration: per-rank id arrays (−1 = empty slot) beside positions and states"""
+    ids = [np.concatenate([np.arange(7, dtype=np.int64) * 3, np.full(4, -1, dtype=np.int64)]), np.array([5, -1, 2**40], dtype=np.int64)]
+    return [("ids@0", ids[0], True), ("ids@1", ids[1], True), ("X@0", np.full((3, 11), 0.5), True), ("state@0", np.ones(11, dtype=np.uint8), True),
+            ("Vx", rnd(1, (8, 5, 4)), False)]
+
+
+def test_int64_slot():
+    """an int64 array is a slot like the others: odd element offset, 8-byte alignment and no better, its values back unchanged, a guard
+    word that is no NaN business but one fixed integer, compared as an integer; the other element types keep their guards"""
+    assert AR.GUARD[torch.int64] == 0x5AA5_0000_DEAD_BEEF and 0 < AR.GUARD[torch.int64] < 2**63
+    assert AR.GUARD[torch.float64] == 0x7FF8_0000_DEAD_BEEF and AR.GUARD[torch.float32] == 0x7FC0_BEEF and AR.GUARD[torch.uint8] == 0xA5
+    arrays = int64_arrays()
+    ar = AR.Arena(arrays, "cpu")
+    check_layout(ar, arrays)
+    assert ar.t["ids@0"].dtype == torch.int64 and ar.get("ids@1").tolist() == [5, -1, 2**40]
+    assert set(ar.buf) == {torch.int64, torch.float64, torch.uint8}                       # a buffer of its own: not mixed with the float64 arrays
+    words = ar.buf[torch.int64].numpy()
+    s0, s1 = ar.slots["ids@0"], ar.slots["ids@1"]
+    assert (words[:s0.offset] == AR.GUARD[torch.int64]).all() and (words[s1.offset + s1.numel:] == AR.GUARD[torch.int64]).all()
+    assert ar.check() == []
+    # a stray id just behind rank 0's array, a −1 (an "empty slot") just before rank 1's: both found, each against its array
+    ar.buf[torch.int64][s0.offset + s0.numel] = 12
+    ar.buf[torch.int64][s1.offset - 1] = -1
+    found = sorted(ar.check())
+    assert [(f.array, f.side, f.first, f.last, f.count) for f in found] == [("ids@0", "behind", 1, 1, 1), ("ids@1", "before", -1, -1, 1)]
+    with pytest.raises(AssertionError, match="ids@0"):
+        ar.assert_clean("migrate")
+    ar.buf[torch.int64][s0.offset + s0.numel] = AR.GUARD[torch.int64]
+    ar.buf[torch.int64][s1.offset - 1] = AR.GUARD[torch.int64]
+    ar.t["ids@0"][3] = -1                                                                # an in-bounds write is not a finding
+    assert ar.check() == [] and ar.get("ids@0")[3] == -1
 
 
 def test_fresh_arena_is_all_guard_outside_the_arrays():

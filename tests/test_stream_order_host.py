@@ -129,6 +129,96 @@ def test_verdict_judges_the_canary_first():
     assert len(msgs) == 1 and "returned 9.0, expected 1.5" in msgs[0] and "read early" not in msgs[0]
 
 
+# ---- the multi-rank half ------------------------------------------------------------------------------------------------------------
+def test_late_sets():
+    f = frozenset
+    assert SO.late_sets(2, "follow") == [f({0, 1})] and SO.late_sets(8, "follow") == [f(range(8))]
+    assert SO.late_sets(2, "own") == [f({0, 1}), f({0}), f({1})]
+    assert SO.late_sets(3, "own") == [f({0, 1, 2}), f({0}), f({2}), f({1})]                 # P = 3: the middle rank too
+    assert SO.late_sets(4, "own") == [f({0, 1}), f({2, 3}), f({0}), f({3})]                 # no queue left for a canary if all four are late
+    assert SO.late_sets(1, "own") == [f({0})]
+    for P in (2, 3, 4):
+        for setup in ("follow", "own"):
+            sets = SO.late_sets(P, setup)
+            assert set().union(*sets) == set(range(P)) and all(s and s <= set(range(P)) for s in sets)       # every rank is late in some run
+    with pytest.raises(ValueError):
+        SO.late_sets(2, "masked")
+
+
+def test_topo_of():
+    assert SO.topo_of((3, (13, 9, 7))) == (None, 3, (13, 9, 7))
+    assert SO.topo_of(((2, 2, 1), [11, 8, 6])) == ((2, 2, 1), 4, (11, 8, 6))
+
+
+def _rank_case(P=3, grid=(6, 5, 4)):
+    host = [fields(*grid, ["c", "vz"], 100 * (r + 1)) for r in range(P)]
+    arrays = [("c", [h[0] for h in host], "field"), ("vz", [h[1] for h in host], "field"),
+              ("state", [np.ones(9 + r, dtype=np.uint8) for r in range(P)], "state")]
+    return SO.RankCase("case", (P, grid), arrays, lambda hip, mg, t: None)
+
+
+def test_rank_case_draws_a_decoy_per_rank():
+    case = _rank_case()
+    assert case.P == 3 and case.dims is None and case.names == ["c", "vz", "state"] and len(case.real) == len(case.decoy) == 3
+    for l in range(3):
+        assert SO.check_decoy(case.rank_arrays(l), case.decoy[l]) == []
+        assert case.decoy[l]["state"].shape == (9 + l,)                                   # a rank's arrays have its own shapes
+        for k in range(l):
+            assert not SO.bits_same(case.decoy[l]["c"], case.decoy[k]["c"]) and not SO.bits_same(case.decoy[l]["vz"], case.decoy[k]["vz"])
+            assert not SO.bits_same(case.decoy[l]["c"], case.real[k]["c"])
+    again = _rank_case()
+    assert all(SO.bits_same(again.decoy[l][n], case.decoy[l][n]) for l in range(3) for n in case.names)
+    with pytest.raises(AssertionError):
+        SO.RankCase("short", (3, (6, 5, 4)), [("c", [rnd(1, (6, 5, 4))] * 2, "field")], None)      # two arrays for three ranks
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_every_case_of_the_multi_rank_table_builds(dt):
+    """RankCase construction (check_decoy empty for every rank: asserted by the constructor) for every row of the table"""
+    import mgpu_cases as MC
+    rows = MC.table(dt)
+    assert {f for f, _ in rows} == {"update_halo", "update_halo_twice", "gather", "slab", "pt_solve_slab", "advect_wide", "advect_wide_twice",
+                                    "poisson_direct", "diagnostics", "tracers_advance", "chain"}
+    for family, spec in rows:
+        case = spec.rank_case()
+        assert case.P == len(case.real) >= 2 and spec.outputs <= set(case.names), spec.name
+        assert all(a.dtype in (MC.NP[dt], np.float64, np.uint8) for l in range(case.P) for a in case.real[l].values()), spec.name
+        for l in range(case.P):
+            assert SO.check_decoy(case.rank_arrays(l), case.decoy[l]) == [], (spec.name, l)
+    assert len({spec.name for _, spec in rows}) == len(rows)
+    # the halo mask of update_halo: nothing on the staggers without a halo, the outermost layer of the sides with a neighbour
+    spec = [s for f, s in rows if f == "update_halo" and s.topo == (3, (13, 9, 7))][0]
+    assert not MC.halo_layers(spec, "s", 1).any() and not MC.halo_layers(spec, "i", 1).any()
+    m = MC.halo_layers(spec, "vz", 1)
+    assert m.shape == (13, 9, 8) and m[:, :, 0].all() and m[:, :, 7].all() and not m[:, :, 1:7].any()
+    assert not MC.halo_layers(spec, "c", 0)[:, :, 0].any() and MC.halo_layers(spec, "c", 0)[:, :, 6].all()
+    assert not MC.halo_layers(spec, "c", 2)[:, :, 6].any()
+    mig = MC.tracers_migrate_case()
+    assert mig.reference[4] > 200 and mig.reference[5] == [0, 0] and mig.arrays[2][1][0].dtype == np.int64
+
+
+def test_verdict_ranks_names_the_rank():
+    case = _rank_case(2)
+    want = [{"c": rnd(11 + l, (6, 5, 4))} for l in range(2)]
+    dwant = [{"c": rnd(21 + l, (6, 5, 4))} for l in range(2)]
+    dec = [{"c": case.decoy[l]["c"]} for l in range(2)]
+    good = {l: dec[l] for l in range(2)}
+    assert SO.verdict_ranks("case", want, want, dwant, good, dec, {0, 1}, (3, [1.0]), (3, [1.0]), (4, [2.0])) == []
+    # rank 1's canary saw the real input: nothing else is judged
+    msgs = SO.verdict_ranks("case", dwant, want, dwant, {0: dec[0], 1: {"c": case.real[1]["c"]}}, dec, {0, 1})
+    assert len(msgs) == 1 and "case, rank 1: delay too short: the case proves nothing" in msgs[0]
+    # only the late ranks have a canary
+    assert SO.verdict_ranks("case", want, want, dwant, {1: dec[1]}, dec, {1}) == []
+    # rank 0 holds the decoy run's bits, rank 1 a mixture (a neighbour's decoy plane in its halo)
+    mixed = want[1]["c"].copy(order="F")
+    mixed[:, :, 0] = dwant[1]["c"][:, :, 0]
+    msgs = SO.verdict_ranks("case", [dwant[0], {"c": mixed}], want, dwant, good, dec, {0, 1}, (3, [1.0]), (3, [1.0]))
+    assert len(msgs) == 2 and msgs[0].startswith("case, rank 0: c equals the decoy run") and msgs[1].startswith("case, rank 1: c neither")
+    assert "(30 of 120 entries" in msgs[1]
+    msgs = SO.verdict_ranks("case", want, want, dwant, good, dec, {0}, (4, [2.0]), (3, [1.0]), (4, [2.0]))
+    assert len(msgs) == 1 and msgs[0].startswith("case: returned") and "read early" in msgs[0]
+
+
 def test_the_harness_imports_no_gpu_module():
     import ast
     import os
