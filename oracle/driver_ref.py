@@ -183,15 +183,51 @@ def advect_wide_z(ranks, p, faithful):
         update_halo_3d(ranks, n, (ranks[0]["C"].shape[0], ranks[0]["C"].shape[1], nz), (1, 1, P))
 
 
+def _maccormack(advection, faithful, P=1):
+    """the `advection` keyword of both drivers → None ("reference") or the function computing the limited MacCormack advection
+    (include/ns3d.h at ns3d_advect_mc).  Its NumPy statement is tests/advect_mc_ref.py::advect_mc, imported only here, when the scheme
+    is asked for: this package does not depend on tests/ otherwise."""
+    if advection not in ("reference", "maccormack"):
+        raise ValueError("advection = %r (\"reference\" | \"maccormack\")" % (advection,))
+    if advection == "reference":
+        return None
+    if faithful:
+        raise ValueError("advection=\"maccormack\" advects Vz: it needs faithful=False")
+    if P != 1:
+        raise ValueError("advection=\"maccormack\" is defined on one rank (this grid has %d)" % P)
+    import importlib.util
+    import os
+    import sys
+    if "advect_mc_ref" not in sys.modules:          # the suite has tests/ on its path and the module loaded; anyone else gets it by file
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "advect_mc_ref.py")
+        spec = importlib.util.spec_from_file_location("advect_mc_ref", path)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules["advect_mc_ref"] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules["advect_mc_ref"].advect_mc
+
+
+def advect_mc_step(f, p, advect_mc):
+    """{X_o .= X; advect!} replaced by the limited MacCormack advection: complete new fields from the current ones, then all four
+    names swap — X holds the new field and X_o the one it was computed from"""
+    old = [f.Vx, f.Vy, f.Vz, f.C]
+    new, _ = advect_mc(old, p.dt, p.dx, p.dy, p.dz)
+    for n, a, b in zip(("Vx", "Vy", "Vz", "C"), old, new):
+        f[n + "_o"], f[n] = a, np.asfortranarray(b)
+
+
 def run_navierstokes3D_ref(nx=63, nt=1, dims_z=1, dtype=np.float64, faithful=True, niter_cap=None,
-                           record=None, shape=None, dims=None, pressure="pt", wide_advect_halo=False):
+                           record=None, shape=None, dims=None, pressure="pt", wide_advect_halo=False, advection="reference"):
     """multi.jl:287-536 without vis/save.  Returns (C_v,Pr_v,Vx_v,Vy_v,Vz_v, info) where info holds the
-    per-step PT iteration counts and err histories, and the final local states."""
+    per-step PT iteration counts and err histories, and the final local states.
+    advection="maccormack" (outside the reference; faithful=False, one rank — anything else raises ValueError): :475-476 are replaced
+    by the definition of ns3d_advect_mc."""
     p = multi_params(nx, dims_z, dtype, dims=dims, **(shape or {}))
     nx, ny, nz = p.nx, p.ny, p.nz
     niter = p.niter if niter_cap is None else min(p.niter, niter_cap)
     dims = p.dims
     P = dims[0] * dims[1] * dims[2]
+    advect_mc = _maccormack(advection, faithful, P)
     update_halo_z = lambda rks, name, _nz: update_halo_3d(rks, name, (nx, ny, nz), dims)      # noqa: F841 (shadows the z-only form)
     gather_z = lambda rks, name: gather_3d(rks, name, dims)                                     # noqa: F841
     ranks = []
@@ -279,7 +315,9 @@ def run_navierstokes3D_ref(nx=63, nt=1, dims_z=1, dtype=np.float64, faithful=Tru
             K.set_bc_Vel(f.Vx, f.Vy, f.Vz, 0, f.owns_inlet, p.vin)
         for n in ("Vx", "Vy", "Vz"):                                                       # :167
             update_halo_z(ranks, n, nz)
-        if wide_advect_halo and P > 1:
+        if advect_mc is not None:
+            advect_mc_step(ranks[0], p, advect_mc)
+        elif wide_advect_halo and P > 1:
             advect_wide_z(ranks, p, faithful)
         else:
             for f in ranks:                                                                # :475-476
@@ -344,8 +382,10 @@ def gpu_initial_fields(p):
     return Vx, Pr
 
 
-def runme_ref(nx=255, nt=1, dtype=np.float64, faithful=True, niter_cap=None, pressure="pt"):
-    """gpu.jl:12-173 without vis/save; returns the final local fields + per-step PT info."""
+def runme_ref(nx=255, nt=1, dtype=np.float64, faithful=True, niter_cap=None, pressure="pt", advection="reference"):
+    """gpu.jl:12-173 without vis/save; returns the final local fields + per-step PT info.
+    advection: as in run_navierstokes3D_ref, in place of :141-142."""
+    advect_mc = _maccormack(advection, faithful)
     p = gpu_params(nx, dtype)
     nx, ny, nz = p.nx, p.ny, p.nz
     f = _alloc_multi(Obj(nx=nx, ny=ny, nz=nz, dtype=dtype))
@@ -373,6 +413,9 @@ def runme_ref(nx=255, nt=1, dtype=np.float64, faithful=True, niter_cap=None, pre
         K.set_cylinder_local(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.lx, p.ly, p.lz,
                              p.dx, p.dy, p.dz)                                             # :139
         K.set_bc_Vel(f.Vx, f.Vy, f.Vz, 1)                                                  # :140
+        if advect_mc is not None:
+            advect_mc_step(f, p, advect_mc)
+            continue
         K.copy(f.Vx_o, f.Vx); K.copy(f.Vy_o, f.Vy); K.copy(f.Vz_o, f.Vz); K.copy(f.C_o, f.C)   # :141
         K.advect(f.Vx, f.Vx_o, f.Vy, f.Vy_o, f.Vz, f.Vz_o, f.C, f.C_o, p.dt, p.dx, p.dy, p.dz, faithful)  # :142
     return f, info

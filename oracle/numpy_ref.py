@@ -156,12 +156,20 @@ def _lerp(a, b, t):                                                 # multi.jl:2
     return b * t + a * (1 - t)
 
 
+def clamp_floor(t, hi):
+    """clamp(floor(Int, t), 1, hi) of multi.jl:192-194 with the clamp applied BEFORE the conversion, as oracle/ns3d_oracle.c's clampf
+    and the kernels apply it: the same integer wherever the conversion is defined, hi for +huge and +Inf, 1 for −huge, −Inf and NaN.
+    (`.astype(int64)` of a value beyond ±2^63 is undefined — x86 gives −2^63 for either sign, and a clamp behind it picks 1 for +huge,
+    the wrong end; a run that follows gpu.jl into its instability at a small grid has such departure points.)"""
+    with np.errstate(invalid="ignore"):
+        f = np.floor(t)
+        return np.where(f >= 1, np.minimum(f, hi), 1).astype(np.int64)
+
+
 def _backtrack(A, A_o, vxc, vyc, vzc, dt, dx, dy, dz, IX, IY, IZ):  # multi.jl:190-205 (1-based index grids)
     sx, sy, sz = A.shape
     ddx, ddy, ddz = dt * vxc / dx, dt * vyc / dy, dt * vzc / dz
-    ix1 = np.clip(np.floor(IX - ddx).astype(np.int64), 1, sx)
-    iy1 = np.clip(np.floor(IY - ddy).astype(np.int64), 1, sy)
-    iz1 = np.clip(np.floor(IZ - ddz).astype(np.int64), 1, sz)
+    ix1, iy1, iz1 = clamp_floor(IX - ddx, sx), clamp_floor(IY - ddy, sy), clamp_floor(IZ - ddz, sz)
     ix2, iy2, iz2 = np.clip(ix1 + 1, 1, sx), np.clip(iy1 + 1, 1, sy), np.clip(iz1 + 1, 1, sz)
     wx = (ddx > 0).astype(A.dtype) - np.fmod(ddx, 1)
     wy = (ddy > 0).astype(A.dtype) - np.fmod(ddy, 1)

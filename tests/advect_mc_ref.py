@@ -58,7 +58,7 @@ def departure(shape, vxc, vyc, vzc, dt, dx, dy, dz, IX, IY, IZ):
     T = vxc.dtype.type
     dd = [dt * vxc / dx, dt * vyc / dy, dt * vzc / dz]
     with np.errstate(invalid="ignore"):
-        i1 = [np.clip(np.floor(I.astype(T) - d).astype(np.int64), 1, s) for I, d, s in zip((IX, IY, IZ), dd, shape)]
+        i1 = [NR.clamp_floor(I.astype(T) - d, s) for I, d, s in zip((IX, IY, IZ), dd, shape)]     # clamped before the conversion
         i2 = [np.clip(i + 1, 1, s) for i, s in zip(i1, shape)]
         w = [(d > 0).astype(T) - np.fmod(d, 1) for d in dd]
     return i1, i2, w

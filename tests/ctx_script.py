@@ -24,6 +24,13 @@ Every PT op starts by resetting the four tile knobs to automatic (STRICT) or pin
 name says; graph mode, persist mode, pacing, autotune, CU reservation and stream stay as the script left them unless the op names
 them.  The ops leave their own settings behind: that is the history the next op meets.
 
+ADVECTION KNOB (ns3d_set_advection).  It is remembered state that CHANGES a result, that of ns3d_time_step and of nothing else
+(include/ns3d.h: "Nothing else reads the knob"), so it is part of a time step's NAME: every time_step op pins the scheme it names
+at its start — time_step_*_mc_* the MacCormack scheme, the others the reference's — and leaves it behind.  Every other op must be
+indifferent to it, the single calls advect_mc and copy_advect + advect_correct included: set_advection(0 | 1) are setting ops.
+The ops of the MacCormack step and its single calls are MC_OPS, a list of their own beside VALUE_OPS (the scripts "of all value
+ops" keep their composition); mc_ops(mode) are those of a mode, seeded_script(…, ops=…) shuffles any list.
+
 Grids — the smallest at which each piece of state exists:
     A  24×15×15    HIP-graph blocks                      E  131×66×37   LDS GEMM of the direct solve
     B  63×38×38    k_pt_persist, 64×2×2 workgroups       F  70×35×12    direct-solve products on both GEMM kernels
@@ -300,38 +307,78 @@ STEP_SHAPES = {"Pr": "c", "dPrdtau": "i", "divV": "c", "Vx": "vx", "Vy": "vy", "
                "C_o": "c", "txx": "c", "tyy": "c", "tzz": "c", "txy": "s", "txz": "s", "tyz": "s"}
 
 
-def _op_time_step(script, pressure):
-    """one ns3d_time_step from the driver's own initial state at A's size, parameters from the drivers' StepParams builder"""
+def _op_time_step(script, pressure, maccormack=False, g="A", dt="f64"):
+    """one ns3d_time_step from the driver's own initial state at the size of grid g (multi_params / gpu_params of its nx),
+    parameters from the drivers' StepParams builder.  The op pins the advection knob it names — maccormack: the MacCormack scheme
+    with faithful = 0, whose stage-1 fields live in the context's hat scratch (16× as large on B as on A; half as large in f32);
+    otherwise the reference's with faithful = 1 — and leaves it behind.  A MacCormack op also returns which buffer each of the
+    eight swapped names ends on: the arrays are compared by buffer, and a swap left out moves no data."""
+    grid = GRIDS[g]
+
     def params():
         from navierstokes3d_amd.params import gpu_params, multi_params
-        p = multi_params(24) if script == "multi" else gpu_params(24)
-        assert (p.nx, p.ny, p.nz) == GRIDS["A"]
+        p = multi_params(grid[0]) if script == "multi" else gpu_params(grid[0])
+        assert (p.nx, p.ny, p.nz) == grid
         return p
 
     def inputs(name):
         from navierstokes3d_amd import driver as Dr
         p = params()
-        host = {k: np.zeros(SHAPES[kind](*GRIDS["A"]), dtype=np.float64, order="F") for k, kind in STEP_SHAPES.items()}
+        host = {k: np.zeros(SHAPES[kind](*grid), dtype=NP[dt], order="F") for k, kind in STEP_SHAPES.items()}
         if script == "multi":
             host["Vy"][0, :, :] = p.vin
         else:
             Vx0, Pr0 = Dr.gpu_initial_fields(p)
-            host["Vx"], host["Pr"] = np.asfortranarray(Vx0), np.asfortranarray(Pr0)
+            host["Vx"], host["Pr"] = np.asfortranarray(Vx0.astype(NP[dt])), np.asfortranarray(Pr0.astype(NP[dt]))
         return host
 
     def call(hip, ctx, inp):
         from navierstokes3d_amd import driver as Dr, lib as L
         p = params()
+        ctx.set_advection("maccormack" if maccormack else "reference")
         names = list(STEP_SHAPES)
         f = SimpleNamespace(**dict(zip(names, _upload(hip, ctx, inp, names))))
         held = {n: getattr(f, n) for n in names}                 # by buffer: the step swaps the roles of X and X_o
         if script == "multi":
             hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly, p.lz,
                              p.dx, p.dy, p.dz, ctx=ctx)
-        sp = Dr._step_params(L.NS3D_BC_MULTI if script == "multi" else L.NS3D_BC_GPU, p, p.niter, True, "direct" if pressure else "pt")
+        sp = Dr._step_params(L.NS3D_BC_MULTI if script == "multi" else L.NS3D_BC_GPU, p, p.niter, not maccormack, "direct" if pressure else "pt")
         it, errs = hip.time_step(f, sp, ctx=ctx)
-        return [("iterations, err history", _scalars(it, *errs))] + _download(hip, ctx, [("buffer " + n, held[n]) for n in names])
-    return Op("time_step_%s_pressure%d:A:f64" % (script, pressure), call, inputs)
+        out = [("iterations, err history", _scalars(it, *errs))] + _download(hip, ctx, [("buffer " + n, held[n]) for n in names])
+        if maccormack:
+            swapped = ("Vx", "Vy", "Vz", "C", "Vx_o", "Vy_o", "Vz_o", "C_o")
+            out.append(("the buffer each of %s ends on" % ", ".join(swapped),
+                        _scalars(*[names.index(next(k for k in names if held[k] is getattr(f, n))) for n in swapped])))
+        return out
+    return Op("time_step_%s%s_pressure%d:%s:%s" % (script, "_mc" if maccormack else "", pressure, g, dt), call, inputs)
+
+
+MC_NAMES = ("Vx", "Vy", "Vz", "C")
+
+
+def _op_advect_mc(dt, two_calls):
+    """the single calls of the MacCormack scheme on A — ns3d_advect_mc, or ns3d_copy_advect(faithful = 0) into the hat arrays followed
+    by ns3d_advect_correct —, outputs and hat arrays over a fill: neither reads the advection knob, whatever a script left it at"""
+    grid = GRIDS["A"]
+
+    def inputs(name):
+        return dict(zip((n + "_o" for n in MC_NAMES), fields(*grid, ["vx", "vy", "vz", "c"], seed_of(name), NP[dt])))
+
+    def call(hip, ctx, inp):
+        g = _geom(grid)
+        old_names = [n + "_o" for n in MC_NAMES]
+        o = _upload(hip, ctx, inp, old_names)
+        n = _upload(hip, ctx, {k: np.full_like(a, 333.0) for k, a in inp.items()}, old_names)
+        h = _upload(hip, ctx, {k: np.full_like(a, 222.0) for k, a in inp.items()}, old_names)
+        trios = [t for trio in zip(n, o, h) for t in trio]
+        if two_calls:
+            hip.copy_advect(h[0], o[0], h[1], o[1], h[2], o[2], h[3], o[3], g["dt"], g["dx"], g["dy"], g["dz"], False, ctx=ctx)
+            hip.advect_correct(*trios, g["dt"], g["dx"], g["dy"], g["dz"], ctx=ctx)
+        else:
+            hip.advect_mc(*trios, g["dt"], g["dx"], g["dy"], g["dz"], ctx=ctx)
+        return _download(hip, ctx, list(zip(MC_NAMES, n)) + list(zip((k + "_hat" for k in MC_NAMES), h)) +
+                         list(zip((k + " unchanged" for k in old_names), o)))
+    return Op("%s:A:%s" % ("copy_advect+advect_correct" if two_calls else "advect_mc", dt), call, inputs, fast=True)
 
 
 def _op_advect(dt):
@@ -385,13 +432,23 @@ def _build_value_ops():
 
 
 VALUE_OPS = _build_value_ops()
-OPS = {op.name: op for op in VALUE_OPS}
-assert len(OPS) == len(VALUE_OPS)
+# the MacCormack step — both scripts and both pressure solves on A, the grid B whose hat is 16× A's, one float32 step (multi.jl's
+# script: tests/test_advect_mc_host.py::test_float32_steps_that_stay_finite) — and the scheme's single calls in both element types
+MC_OPS = [_op_time_step(s, pr, True) for s in ("multi", "gpu") for pr in (0, 1)] + \
+         [_op_time_step("multi", 0, True, "B"), _op_time_step("multi", 0, True, "A", "f32")] + \
+         [_op_advect_mc(dt, two) for two in (False, True) for dt in ("f64", "f32")]
+OPS = {op.name: op for op in VALUE_OPS + MC_OPS}
+assert len(OPS) == len(VALUE_OPS) + len(MC_OPS)
 
 
 def value_ops(mode):
     """the value ops of a context of `mode`: all of them in STRICT, those that also exist in FAST otherwise"""
     return [op for op in VALUE_OPS if op.fast or mode != "fast"]
+
+
+def mc_ops(mode):
+    """MC_OPS of a context of `mode`: in FAST the single calls only"""
+    return [op for op in MC_OPS if op.fast or mode != "fast"]
 
 
 # ---- setting ops ------------------------------------------------------------------------------------------------------------------
@@ -420,14 +477,15 @@ SETTING_OPS += [_setting("set_graph_mode(%d)" % v, lambda c, v=v: c.set_graph_mo
 SETTING_OPS += [_setting("set_persist_mode(%d)" % v, lambda c, v=v: c.set_persist_mode(v)) for v in (-1, 0, 1)]
 SETTING_OPS += [_setting("set_pt_pace(%d)" % v, lambda c, v=v: c.set_pt_pace(v)) for v in (-1, 0, 8, 16)]
 SETTING_OPS += [_setting("set_pt_depth(0) and variant resets", _reset_tiles)]
+SETTING_OPS += [_setting("set_advection(%d)" % v, lambda c, v=v: c.set_advection(("reference", "maccormack")[v])) for v in (0, 1)]
 
 
 # ---- scripts ----------------------------------------------------------------------------------------------------------------------
-def seeded_script(seed, mode, settings=True):
-    """a permutation of all value ops of `mode` drawn from `seed`, with one setting op (drawn likewise) in front of every second
-    value op when `settings` is set"""
+def seeded_script(seed, mode, settings=True, ops=None):
+    """a permutation of all value ops of `mode` (or of `ops`) drawn from `seed`, with one setting op (drawn likewise) in front of
+    every second value op when `settings` is set"""
     rng = random.Random(seed)
-    vals = list(value_ops(mode))
+    vals = list(value_ops(mode) if ops is None else ops)
     rng.shuffle(vals)
     out = []
     for q, op in enumerate(vals):
@@ -472,6 +530,19 @@ def hostile_script():
                  "time_step_gpu_pressure1:A:f64"):
         s += [o("pt_solve_graph:A:f64"), o(name), o("pt_solve_persist:B:f64")]
     s += [o("advect:A:f64"), o("advect:A:f32"), o("predict_fused:A:f64"), o("predict_fused:A:f32"), o("set_pt_pace(-1)")]
+    # 9. the MacCormack step and its hat scratch.  A graph captured on A; the step on A, whose first use allocates the hat; on B: the
+    #    hat grows, which frees the old buffer and wipes the graphs; the graph solve on A, captured again; the step on A again, a
+    #    smaller grid in the larger buffer with another split; in float32, another split again; the reference step, which turns the
+    #    knob off; the knob left ON in front of ops that must not read it; the step on the context's own stream and then on a side
+    #    stream — the hat was last written on the stream just left —; the step with CUs reserved
+    mc = "time_step_multi_mc_pressure0:A:f64"
+    s += [o("set_graph_mode(1)"), o("pt_solve_graph:A:f64"), o(mc), o("time_step_multi_mc_pressure0:B:f64"), o("pt_solve_graph:A:f64"), o(mc),
+          o("time_step_multi_mc_pressure0:A:f32"), o("time_step_multi_pressure0:A:f64"),
+          o("set_advection(1)"), o("advect:A:f64"), o("advect_mc:A:f64"), o("advect_mc:A:f32"), o("copy_advect+advect_correct:A:f64"),
+          o("copy_advect+advect_correct:A:f32"), o("predict_fused:A:f64"), o("pt_solve_graph:A:f64"),
+          o("use_own_stream()"), o(mc), o("time_step_gpu_mc_pressure0:A:f64"), o("use_torch_stream(side_stream)"), o(mc),
+          o("time_step_multi_mc_pressure1:A:f64"), o("reserve_cus(32)"), o(mc), o("time_step_gpu_mc_pressure1:A:f64"), o("reserve_cus(0)"),
+          o("use_torch_stream()"), o(mc), o("set_advection(0)"), o("set_graph_mode(-1)")]
     return s
 
 
@@ -479,7 +550,7 @@ OPS["pt_sweepn4_v2900_pace16:C:f64"] = _op_pt_sweepn("C", "f64", 4, 2900, 16)   
 SMALL_OPS = ["pt_iterate:A:f64", "pt_solve_graph:A:f64", "pt_iterate:B:f64", "pt_solve_persist:B:f64", "pt_iterate_depth3:C:f64",
              "pt_sweepn4_v2900_pace8:C:f64", "pt_solve_graph:C:f64"]                  # the A-, B- and C-sized ops of the memory and churn tests
 ONE_OF_EACH_KIND = ["pt_iterate:A:f64", "pt_sweepn4_v2900_pace8:C:f64", "pt_solve_graph:A:f64", "pt_solve_persist:B:f64", "advect:A:f64",
-                    "predict_fused:A:f64"]
+                    "predict_fused:A:f64", "time_step_multi_mc_pressure0:A:f64"]
 
 
 # ---- running and comparing --------------------------------------------------------------------------------------------------------

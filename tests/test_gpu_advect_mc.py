@@ -1,6 +1,7 @@
 """ns3d_advect_mc / ns3d_advect_correct (limited MacCormack advection) on the device, the knob of ns3d_time_step and the drivers'
 `advection` keyword.  STRICT is compared bit for bit with tests/advect_mc_ref.py (whose limiter engages in all three ways on these
-inputs: tests/test_advect_mc_host.py); FAST with the enclosure of tests/advect_mc_pairs.py."""
+inputs: tests/test_advect_mc_host.py); FAST with the enclosure of tests/advect_mc_pairs.py; whole runs with oracle/driver_ref.py.
+Stream order: tests/test_gpu_stream_order.py::test_advect_mc, on every kind of stream."""
 import ctypes as C
 import functools
 import itertools
@@ -12,9 +13,8 @@ import torch
 import advect_mc_pairs as MP
 import advect_mc_ref as MC
 import pair_cases as PC
-import stream_order as SO
 from arena import Arena
-from test_advect_mc_host import CFLS, GRIDS, KINDS, check_blob, seeded
+from test_advect_mc_host import CFLS, GRIDS, KINDS, check_blob, ref_run, seeded
 from util import bits_equal, first_bit_difference, fields, geometry, rnd
 
 pytestmark = pytest.mark.gpu
@@ -312,6 +312,186 @@ def test_what_maccormack_refuses(hip):
     ctx.close()
 
 
+# ---- the whole step against its CPU statement (oracle/driver_ref.py with advection=…, tests/test_advect_mc_host.py::ref_run) -----------
+STATE = FIELD_NAMES + ("Vx_o", "Vy_o", "Vz_o", "C_o", "dPrdtau", "divV", "txx", "tyy", "tzz", "txy", "txz", "tyz")
+RUNME_CAP = 200                      # niter_cap of the runme cases, as in test_runme_with_maccormack above
+
+
+def device_run(hip, script, nt, advection, one_call, mode="strict", dtype=torch.float64, pressure="pt"):
+    """({name: host array} of the full local state, info) of run_navierstokes3D ("multi") or runme ("gpu") at nx = 24, faithful=False"""
+    from navierstokes3d_amd.driver import run_navierstokes3D, runme
+    kw = dict(nx=24, nt=nt, mode=mode, faithful=False, advection=advection, one_call=one_call, dtype=dtype, pressure=pressure)
+    if script == "multi":
+        info = run_navierstokes3D(return_info=True, **kw)[-1]
+        f = info.fields
+    else:
+        f, info = runme(niter_cap=RUNME_CAP, **kw)
+    assert tuple(f.C.shape) == (24, 15, 15)
+    return {n: hip.to_numpy(getattr(f, n)) for n in STATE}, info
+
+
+def cpu_run(script, nt, advection, dtype=np.float64, pressure="pt"):
+    _, info, f = ref_run(script, nt, advection, False, dtype, pressure, RUNME_CAP if script == "gpu" else None)
+    return f, info
+
+
+def assert_state(got, want, what, names=STATE):
+    for n in names:
+        assert bits_equal(got[n], want[n]), (what, n, first_bit_difference(got[n], want[n]))
+
+
+NT = {"multi": 3, "gpu": 2}
+
+
+@pytest.mark.parametrize("one_call", [True, False], ids=["one_call", "call_by_call"])
+@pytest.mark.parametrize("advection", ["maccormack", "reference"])
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_driver_equals_the_oracle_driver(hip, oracle, script, advection, one_call):
+    """run_navierstokes3D(nx=24, nt=3) and runme(nx=24, nt=2), faithful=False, STRICT, fp64, on one rank, in both forms of the step and
+    with both schemes, against run_navierstokes3D_ref / runme_ref with the same options: C, Pr, Vx, Vy, Vz — and the previous fields,
+    dPrdτ, divV and the six stresses, all as full local arrays — bit for bit, iteration counts and error histories equal.  (With the
+    reference scheme this is also the suite's one-rank comparison of faithful=False with the oracle driver.)"""
+    got, info = device_run(hip, script, NT[script], advection, one_call)
+    want, winfo = cpu_run(script, NT[script], advection)
+    assert info.iters == winfo.iters and len(info.iters) == NT[script], (info.iters, winfo.iters)
+    assert [list(e) for e in info.errs] == [list(e) for e in winfo.errs], (info.errs, winfo.errs)
+    assert_state(got, want, (script, advection, one_call))
+    assert info.ctx.advection() == "reference" or script == "gpu"      # run_navierstokes3D puts the default back; runme's context is its own
+
+
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_driver_with_direct_pressure_and_maccormack(hip, script):
+    """pressure="direct": the two solves differ in summation order, so the comparison with the oracle driver of the same options
+    is that of tests/test_gpu_direct.py — its helper, its norm, its bar 1e-9 — while the two forms of the device's step, which go
+    through the same entry points, agree bit for bit whatever the bar.
+    multi.jl's script is held to the bar at nx = 36 (36×22×22, three steps: the size that test uses), not at 24: at nx = 24 the
+    reference's outlet test `xve_g == lx/2` is false in floating point (App. B10), the pressure problem is the singular all-Neumann
+    one, and the helper's first assertion — the residual of the direct solution below 1e-8 — fails in the ORACLE's own run, with
+    either scheme (3.0e-4 and 7.5e-4 in steps 2 and 3).  The bit comparison of the two forms runs at 24 for both scripts."""
+    from test_gpu_direct import _direct_driver_against_the_oracle_driver
+    _direct_driver_against_the_oracle_driver(hip, script, 36 if script == "multi" else 24, NT[script], faithful=False, advection="maccormack")
+    one, i1 = device_run(hip, script, NT[script], "maccormack", True, pressure="direct")
+    seq, i2 = device_run(hip, script, NT[script], "maccormack", False, pressure="direct")
+    assert i1.iters == i2.iters == [0] * NT[script] and i1.errs == i2.errs
+    assert_state(one, seq, (script, "direct"))
+
+
+def test_fast_step_is_the_call_sequence(hip):
+    """FAST: ns3d_time_step with the knob on and the step call by call go through the same entry points — the same bits.  No
+    comparison with the CPU here: the limiter's comparisons may fall the other way on FAST's values."""
+    one, i1 = device_run(hip, "multi", 3, "maccormack", True, mode="fast")
+    seq, i2 = device_run(hip, "multi", 3, "maccormack", False, mode="fast")
+    assert i1.iters == i2.iters and i1.errs == i2.errs
+    assert_state(one, seq, "fast")
+    assert all(np.isfinite(a).all() for a in one.values()) and one["C"].min() >= 0.0 and one["C"].max() <= 1.0
+
+
+def test_float32_step_is_the_call_sequence(hip, oracle):
+    """fp32, STRICT, multi.jl's script, three steps — the largest nt ≤ 3 at which the oracle driver's float32 fields are all finite
+    (tests/test_advect_mc_host.py::test_float32_steps_that_stay_finite; gpu.jl's script does not get through one step in float32 and
+    is left to the single-call tests): the one-call form equals the call-by-call form, finite, and both equal the oracle driver."""
+    one, i1 = device_run(hip, "multi", 3, "maccormack", True, dtype=torch.float32)
+    seq, i2 = device_run(hip, "multi", 3, "maccormack", False, dtype=torch.float32)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in one.values())
+    assert i1.iters == i2.iters and i1.errs == i2.errs
+    assert_state(one, seq, "float32")
+    want, winfo = cpu_run("multi", 3, "maccormack", np.float32)
+    assert all(np.isfinite(want[n]).all() for n in FIELD_NAMES)
+    assert i1.iters == winfo.iters
+    assert_state(one, want, "float32 against the oracle driver", FIELD_NAMES)
+
+
+def _ieee_steps(hip, nt, one_call):
+    """nt steps of multi.jl's script at 24×15×15 on a STRICT context with NS3D_IEEE_DIV (the drivers have no keyword for it): as
+    ns3d_time_step with the knob on, or call by call with the driver's own helpers"""
+    from navierstokes3d_amd import driver as Dr, lib as L
+    from navierstokes3d_amd.params import multi_params
+    p = multi_params(24)
+    ctx = hip.Context(0, "strict", async_=True, ieee_div=True)
+    f = Dr._alloc(p.nx, p.ny, p.nz, torch.float64, torch.device("cuda", 0))
+    f.Vy[0, :, :] = p.vin
+    torch.cuda.synchronize()
+    cyl = (p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly, p.lz, p.dx, p.dy, p.dz)
+    hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)
+    sp = Dr._step_params(L.NS3D_BC_MULTI, p, p.niter, False, "pt")
+    pt = hip.pt_params(f.Pr, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, L.NS3D_BC_MULTI, p.owns_outlet, 0.0, p.g)
+    hats = None
+    if one_call:
+        ctx.set_advection("maccormack")
+    else:
+        hats = Dr._alloc_hats(f, ctx)
+    record = []
+    for it in range(1, nt + 1):
+        if one_call:
+            sp.write_stress = 1 if it == nt else 0
+            record.append(hip.time_step(f, sp, ctx=ctx))
+            continue
+        if it == nt:
+            hip.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)
+        Dr._predict_swap(f, p, ctx)
+        hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)
+        hip.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=ctx)
+        record.append(hip.pt_solve(f.Pr, f.dPrdtau, f.divV, pt, p.eps, p.niter, p.nchk, p.ly * p.ly, p.psc, ctx=ctx))
+        hip.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=ctx)
+        hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)
+        hip.set_bc_Vel_multi(f.Vx, f.Vy, f.Vz, p.owns_inlet, p.vin, ctx=ctx)
+        Dr._advect_mc_swap(f, hats, p, ctx)
+    ctx.sync()
+    out = {n: hip.to_numpy(getattr(f, n)) for n in STATE}
+    ctx.close()
+    return out, [it for it, _ in record], [list(e) for _, e in record]
+
+
+def test_ieee_div_step_is_the_call_sequence_and_the_oracle_driver(hip, oracle):
+    """NS3D_IEEE_DIV: the one-call step equals the call-by-call step, and both equal the CPU statement — its divisions are IEEE's"""
+    one, it1, e1 = _ieee_steps(hip, 3, True)
+    seq, it2, e2 = _ieee_steps(hip, 3, False)
+    assert it1 == it2 and e1 == e2
+    assert_state(one, seq, "ieee_div")
+    want, winfo = cpu_run("multi", 3, "maccormack")
+    assert it1 == winfo.iters and e1 == [list(e) for e in winfo.errs]
+    assert_state(one, want, "ieee_div against the oracle driver")
+
+
+def _knob_step(hip, ctx, before=lambda: None):
+    """one ns3d_time_step of multi.jl's script at 24×15×15 on ctx AS ITS KNOB STANDS, `before` called right in front of it"""
+    from navierstokes3d_amd import driver as Dr, lib as L
+    from navierstokes3d_amd.params import multi_params
+    p = multi_params(24)
+    f = Dr._alloc(p.nx, p.ny, p.nz, torch.float64, torch.device("cuda", 0))
+    f.Vy[0, :, :] = p.vin
+    torch.cuda.synchronize()
+    hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly, p.lz, p.dx, p.dy,
+                     p.dz, ctx=ctx)
+    sp = Dr._step_params(L.NS3D_BC_MULTI, p, p.niter, False, "pt")
+    sp.write_stress = 1
+    before()
+    hip.time_step(f, sp, ctx=ctx)
+    ctx.sync()
+    return {n: hip.to_numpy(getattr(f, n)) for n in STATE}
+
+
+def test_the_knob_belongs_to_its_context(hip, oracle):
+    """Two contexts, one with each scheme, set in both orders and stepped in both orders with the other's knob touched last: each
+    advects with its OWN scheme — the CPU statement's bits of one step — and creating or closing a context changes nothing."""
+    want = {a: cpu_run("multi", 1, a)[0] for a in ("maccormack", "reference")}
+    assert not bits_equal(want["maccormack"]["Vx"], want["reference"]["Vx"])
+    mc, ref = hip.Context(0, "strict", async_=True), hip.Context(0, "strict", async_=True)
+    mc.set_advection("maccormack")
+    ref.set_advection("reference")                                   # the last call of the process says "reference"
+    assert_state(_knob_step(hip, mc), want["maccormack"], "the MacCormack context, the other one set last")
+    assert_state(_knob_step(hip, ref), want["reference"], "the reference context")
+    mc.set_advection("maccormack")                                   # the last call of the process says "maccormack"
+    assert_state(_knob_step(hip, ref), want["reference"], "the reference context, the other one set last")
+    assert_state(_knob_step(hip, mc, before=lambda: ref.set_advection("reference")), want["maccormack"], "set on the other one right before the step")
+    fresh = hip.Context(0, "strict")                                 # a new context starts with the default and leaves the others alone
+    assert fresh.advection() == "reference" and mc.advection() == "maccormack"
+    fresh.set_advection("maccormack")
+    fresh.close()
+    assert_state(_knob_step(hip, ref), want["reference"], "after another context came and went")
+    mc.close(); ref.close()
+
+
 # ---- the harnesses ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", FORMS)
 def test_in_a_guarded_arena(hip, form, monkeypatch):
@@ -331,25 +511,6 @@ def test_in_a_guarded_arena(hip, form, monkeypatch):
     assert_bits([A.get(n) for n in HAT], want_hat, "hat in the arena")
     assert_bits([A.get(n) for n in OLD], old, "inputs in the arena")
     ctx.close()
-
-
-@pytest.fixture(scope="module")
-def delay(hip):
-    return SO.Delay()
-
-
-@pytest.mark.parametrize("form", FORMS)
-def test_stream_order_on_a_pinned_stream(hip, delay, form, monkeypatch):
-    """late inputs, an early reader and an overwrite behind the call, on a torch stream the context is pinned to"""
-    from test_gpu_stream_order import run_cases
-    select(form, monkeypatch)
-    grid = (70, 6, 7)
-    old, dt, g = seeded(grid, 2.7, np.float64)
-    arrays = [(n, np.full_like(a, 777.0), "field") for n, a in zip(NEW + HAT, old + old)] + [(n, a, "field") for n, a in zip(OLD, old)]
-    case = SO.Case("advect_mc %s %s" % (GID(grid), form), arrays,
-                   lambda hip, ctx, t: hip.advect_mc(*interleave([t[n] for n in NEW], [t[n] for n in OLD], [t[n] for n in HAT]), dt, g["dx"],
-                                                     g["dy"], g["dz"], ctx=ctx))
-    run_cases(hip, [case], "torch", delay)
 
 
 def test_blob_on_the_device(hip):

@@ -24,11 +24,14 @@ def test_one_context_through_the_hostile_order(hip):
     """graphs → ping-pong growth → graphs again; persist → CUs reserved → persist → released; paced C, D, C at another pace, C in
     fp32 on the same counters; direct solve E, F, E; 19 graph solves past the cache's wipe, another stream, the 19 again; G with
     autotune on (its first planned use, when this test is the first of the process to run G: it stands first in the module), off,
-    on; time_step between two pt_solve calls on one key word; fp32 and fp64 alternating on one grid"""
+    on; time_step between two pt_solve calls on one key word; fp32 and fp64 alternating on one grid; the MacCormack step: its hat
+    scratch allocated on A between two graph solves, grown on B (the graphs go), A again in the larger buffer, float32, the knob
+    off, the knob left on in front of the single calls, the own stream and then a side stream, CUs reserved"""
     script = CS.hostile_script()
     results, ctx = _run_compared(hip, script, "strict")
-    assert len(results) == sum(op.value for op in script) == 55
-    assert {op.name for op in script if op.value} >= {op.name for op in CS.value_ops("strict")}
+    assert len(results) == sum(op.value for op in script) == 76
+    assert {op.name for op in script if op.value} >= {op.name for op in CS.value_ops("strict") + CS.mc_ops("strict")}
+    assert ctx.advection() == "reference", "the script's last word on the knob"
     assert ctx.persist_faults() == 0
     ctx.close()
 
@@ -79,6 +82,62 @@ def test_references_reach_the_paths_their_ops_are_named_for(hip):
     iso = dict(CS.reference(CS.OPS["isosurface:AE:f64"], "strict"))
     assert iso["A: triangle counts"][0] == iso["A: triangle counts"][1] > 100 and iso["E: triangle counts"][0] > iso["A: triangle counts"][0]
     assert (iso["E: tri"] >= 0).all()
+
+
+def test_maccormack_references_reach_what_their_ops_are_named_for(hip):
+    """On fresh contexts: every MacCormack op's outputs are finite and moved, its inputs are unchanged; the steps iterate, swap all
+    eight names, keep C in [0, 1] and differ from the reference step of the same script and solve; the two forms of the single call
+    agree with each other on equal inputs — and the hat scratch grows from A to B, which wipes the graphs, and not again for A."""
+    swapped = list(range(8))
+    for op in CS.MC_OPS:
+        res = dict(CS.reference(op, "strict"))
+        inp = op.inputs()
+        for label, a in res.items():
+            assert np.isfinite(a).all(), (op.name, label)
+            if label.endswith(" unchanged"):
+                assert np.array_equal(a, inp[label[:-len(" unchanged")]]), (op.name, label)
+        if op.name.startswith("time_step"):
+            rec = res["iterations, err history"]
+            assert len(rec) >= 2 and (rec[0] > 0 or "pressure1" in op.name), (op.name, rec)
+            names = list(CS.STEP_SHAPES)
+            ends = [names[int(q)] for q in next(v for k, v in res.items() if k.startswith("the buffer each of"))]
+            assert ends == ["Vx", "Vy", "Vz", "C_o", "Vx_o", "Vy_o", "Vz_o", "C"], (op.name, ends)     # V: two swaps; C: one
+            new_c = res["buffer C_o"]
+            assert new_c.min() >= 0.0 and new_c.max() <= 1.0 and np.abs(res["buffer Vx"]).max() > 0, op.name
+            twin = op.name.replace("_mc_", "_")
+            if twin in CS.OPS:
+                assert not np.array_equal(dict(CS.reference(CS.OPS[twin], "strict"))["buffer Vx"], res["buffer Vx"]), op.name
+        else:
+            for n in CS.MC_NAMES:
+                assert not np.array_equal(res[n], inp[n + "_o"]) and not np.array_equal(res[n + "_hat"], res[n]), (op.name, n)
+    ctx = CS.make_context(hip, "strict")
+    CS.gpu_execute(CS.OPS["set_graph_mode(1)"], ctx)
+    CS.gpu_execute(CS.OPS["pt_solve_graph:A:f64"], ctx)
+    held = int(ctx.lib.ns3d_cached_graphs(ctx.handle))
+    assert held >= 1
+    CS.gpu_execute(CS.OPS["time_step_multi_mc_pressure0:A:f64"], ctx)
+    assert int(ctx.lib.ns3d_cached_graphs(ctx.handle)) >= held, "the hat's first allocation frees nothing"
+    CS.gpu_execute(CS.OPS["time_step_multi_mc_pressure0:B:f64"], ctx)
+    after_b = int(ctx.lib.ns3d_cached_graphs(ctx.handle))
+    assert after_b == 0, "the hat grew behind the step's solve: the old buffer was freed and every graph went with it"
+    CS.gpu_execute(CS.OPS["pt_solve_graph:A:f64"], ctx)
+    CS.gpu_execute(CS.OPS["time_step_multi_mc_pressure0:A:f32"], ctx)
+    assert int(ctx.lib.ns3d_cached_graphs(ctx.handle)) >= max(1, after_b), "a smaller hat fits the buffer: nothing is freed, no graph goes"
+    ctx.close()
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("mode", ["strict", "ieee", "fast"])
+def test_maccormack_ops_through_seeded_orders(hip, mode, seed):
+    """the MacCormack ops of the mode among its A- to F-sized value ops, in a seeded order with setting ops between them — the
+    advection knob's among them — on one context: every op returns its reference, so no op but a named time step reads the knob
+    and no step reads anything but its own"""
+    ops = [op for op in CS.value_ops(mode) if ":G:" not in op.name] + CS.mc_ops(mode)
+    script = CS.seeded_script(seed, mode, ops=ops)
+    assert sum(op.value for op in script) == len(ops) == (40 if mode != "fast" else 20)
+    results, ctx = _run_compared(hip, script, mode)
+    assert ctx.persist_faults() == 0
+    ctx.close()
 
 
 @pytest.mark.parametrize("seed", SEEDS)

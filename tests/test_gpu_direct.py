@@ -180,17 +180,18 @@ def test_driver_with_direct_pressure_at_the_reference_grid(hip, script):
     _direct_driver_against_the_oracle_driver(hip, script, 255, 2, levels)
 
 
-def _direct_driver_against_the_oracle_driver(hip, script, nx, nt, levels=None):
+def _direct_driver_against_the_oracle_driver(hip, script, nx, nt, levels=None, **options):
+    """options: keywords both the product drivers and the oracle drivers take (faithful, advection), passed to both"""
     from navierstokes3d_amd.driver import run_navierstokes3D, runme
     from oracle.driver_ref import run_navierstokes3D_ref, runme_ref
     if script == "multi":
-        out = run_navierstokes3D(nx=nx, nt=nt, mode="strict", pressure="direct", return_info=True)
-        ref = run_navierstokes3D_ref(nx=nx, nt=nt, pressure="direct")
+        out = run_navierstokes3D(nx=nx, nt=nt, mode="strict", pressure="direct", return_info=True, **options)
+        ref = run_navierstokes3D_ref(nx=nx, nt=nt, pressure="direct", **options)
         info, rinfo = out[-1], ref[-1]
         pairs = list(zip(("C", "Pr", "Vx", "Vy", "Vz"), out[:5], ref[:5]))
     else:
-        f, info = runme(nx=nx, nt=nt, mode="strict", pressure="direct")
-        rf, rinfo = runme_ref(nx=nx, nt=nt, pressure="direct")
+        f, info = runme(nx=nx, nt=nt, mode="strict", pressure="direct", **options)
+        rf, rinfo = runme_ref(nx=nx, nt=nt, pressure="direct", **options)
         pairs = [(n, hip.to_numpy(getattr(f, n)), rf[n]) for n in ("C", "Pr", "Vx", "Vy", "Vz")]
     assert info.iters == rinfo.iters == [0] * len(info.iters)
     print("direct-solve err per step:", [e[0] for e in info.errs])

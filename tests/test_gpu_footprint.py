@@ -528,9 +528,20 @@ STEP_SHAPES = {"Pr": "c", "dPrdtau": "i", "divV": "c", "Vx": "vx", "Vy": "vy", "
                "C_o": "c", "txx": "c", "tyy": "c", "tzz": "c", "txy": "s", "txz": "s", "tyz": "s"}
 
 
-def _two_steps_on(hip, script, dt, mode, in_arena):
+MC_GPU_NITER = 200
+
+
+def mc_niter(script, advection, p):
+    """The iteration limit of the step: the script's own — but 200 for gpu.jl's script with the MacCormack scheme.  Its PT loop
+    diverges at 24×15×15; after two steps of 750 iterations |V| is of order 1e267, which STRICT still holds and FAST's rounding puts
+    over float64's range (NaN in every field, and a comparison of NaNs could not see a guard's NaN); with 200 it is of order 1e67."""
+    return MC_GPU_NITER if (script, advection) == ("gpu", "maccormack") else p.niter
+
+
+def _two_steps_on(hip, script, dt, mode, in_arena, advection="reference"):
     """_two_steps of test_gpu_invariance.py with the seventeen arrays of ns3d_step_fields on plain tensors or in an arena, in either
-    element type and mode: the same initial state, two ns3d_time_step calls, write_stress on the second"""
+    element type and mode: the same initial state, two ns3d_time_step calls, write_stress on the second.  advection="maccormack":
+    the knob on and faithful = 0 (the stage-1 fields are the context's own scratch, not part of the arena)"""
     from navierstokes3d_amd import driver as Dr, lib as L
     from navierstokes3d_amd.params import gpu_params, multi_params
     p = multi_params(24) if script == "multi" else gpu_params(24)
@@ -545,9 +556,11 @@ def _two_steps_on(hip, script, dt, mode, in_arena):
     ar = AR.Arena([(k, a, True) for k, a in host.items()], "cuda") if in_arena else None
     f = SimpleNamespace(**(ar.t if in_arena else {k: hip.from_numpy(a) for k, a in host.items()}))
     ctx = hip.Context(0, mode, async_=True)
+    ctx.set_advection(advection)
     common = dict(nx=p.nx, ny=p.ny, nz=p.nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau, damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz,
-                  eps=p.eps, niter=p.niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy,
-                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=1, pressure=0, write_stress=0)
+                  eps=p.eps, niter=mc_niter(script, advection, p), nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy,
+                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=0 if advection == "maccormack" else 1, pressure=0,
+                  write_stress=0)
     torch.cuda.synchronize()
     if script == "multi":
         hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly, p.lz,
@@ -565,30 +578,43 @@ def _two_steps_on(hip, script, dt, mode, in_arena):
     got = SimpleNamespace(steps=out, fields={k: hip.to_numpy(getattr(f, k)) for k in STEP_SHAPES})
     ctx.close()
     if in_arena:
-        ar.assert_clean("time_step %s %s %s" % (script, dt, mode))
+        ar.assert_clean("time_step %s %s %s %s" % (script, dt, mode, advection))
     return got
 
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("script", ["multi", "gpu"])
-def test_time_step(hip, script, mode, dt="f64"):
+def test_time_step(hip, oracle, script, mode, dt="f64", advection="reference"):
     """All seventeen arrays of ns3d_step_fields in the arena: guards intact, and the iteration counts, residual histories and every
     array equal the run on plain arrays — which in STRICT is _two_steps of test_gpu_invariance.py itself.  float64 only: in float32
     both scripts leave the finite range within two steps at 24×15×15 — in the oracle's arithmetic as well (run_navierstokes3D_ref and
-    runme_ref with nx=24, dtype=float32 return NaN in all five fields) — and a comparison of NaNs could not see a guard's NaN."""
-    got = _two_steps_on(hip, script, dt, mode, True)
-    want = _two_steps_on(hip, script, dt, mode, False)
+    runme_ref with nx=24, dtype=float32 return NaN in all five fields) — and a comparison of NaNs could not see a guard's NaN.
+    With the MacCormack scheme (faithful = 0) the STRICT run also equals the oracle driver's two steps with advection="maccormack"
+    (tests/test_advect_mc_host.py::ref_run), all seventeen arrays, iteration counts and residual histories."""
+    got = _two_steps_on(hip, script, dt, mode, True, advection)
+    want = _two_steps_on(hip, script, dt, mode, False, advection)
     assert all(it > 0 and len(errs) > 0 for it, errs in want.steps)
     assert np.abs(want.fields["Vx"]).max() > 0 and np.abs(want.fields["Pr"]).max() > 0 and np.abs(want.fields["txx"]).max() > 0
     assert all(np.isfinite(a).all() for a in want.fields.values())
     wants = [want]
     if (dt, mode) == ("f64", "strict"):
         from test_gpu_invariance import _two_steps
-        wants.append(_two_steps(hip, script, 0))
+        wants.append(_two_steps(hip, script, 0, advection))
+        if advection == "maccormack":
+            from test_advect_mc_host import ref_run
+            _, info, f = ref_run(script, 2, "maccormack", niter_cap=MC_GPU_NITER if script == "gpu" else None)
+            wants.append(SimpleNamespace(steps=[(it, list(e)) for it, e in zip(info.iters, info.errs)], fields={k: f[k] for k in STEP_SHAPES}))
     for w in wants:
         assert _same_result(got.steps, w.steps), (got.steps, w.steps)
         for k, a in w.fields.items():
             assert _exact(got.fields[k], a), (script, dt, mode, k, first_bit_difference(got.fields[k], a))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_time_step_maccormack(hip, oracle, script, mode):
+    """test_time_step over the other value of its `advection` parameter (a test of its own: the existing cases keep their names)"""
+    test_time_step(hip, oracle, script, mode, advection="maccormack")
 
 
 # ---- 8. derived fields ---------------------------------------------------------------------------------------------------------------------

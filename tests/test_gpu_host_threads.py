@@ -38,6 +38,7 @@ SCRIPT_SECONDS = {"all value ops, strict": 0.30, "all value ops, fast": 0.13, "p
 LIMIT_FLOOR_SECONDS = 30.0
 THREAD_MODES = ["strict", "strict", "ieee", "fast"]
 THREAD_SEEDS = [21, 22, 23, 24]
+MC_THREADS = (0, 2)                   # the threads whose scripts carry the MacCormack ops (tests/ctx_script.py MC_OPS); the others leave the knob off
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -201,16 +202,23 @@ def test_last_error_belongs_to_the_calling_thread(hip):
 def test_four_threads_each_with_a_context(hip, two_threads_first, streams):
     """four contexts — two strict, one strict with NS3D_IEEE_DIV, one fast — each on its own thread through a different seeded
     order of all its value ops, started together.  own: every context on its own non-blocking stream; shared: all four on
-    PyTorch's default stream."""
-    _warm_references({m: [op.name for op in CS.value_ops(m)] for m in set(THREAD_MODES)})
-    scripts = [CS.seeded_script(seed, mode, settings=False) for seed, mode in zip(THREAD_SEEDS, THREAD_MODES)]
-    assert [len(s) for s in scripts] == [32, 32, 32, 18]
+    PyTorch's default stream.
+    The first and the third thread's scripts also carry the MacCormack ops (their six time steps turn the advection knob on, their
+    hat scratch is allocated and grown beside the other threads' work); the second and the fourth leave the knob off throughout and
+    run the reference steps and the reference advection on the same grid A: the knob is one context's, not the process's."""
+    mc_modes = {THREAD_MODES[q] for q in MC_THREADS}
+    _warm_references({m: [op.name for op in CS.value_ops(m) + (CS.mc_ops(m) if m in mc_modes else [])] for m in set(THREAD_MODES)})
+    scripts = [CS.seeded_script(seed, mode, settings=False, ops=CS.value_ops(mode) + (CS.mc_ops(mode) if q in MC_THREADS else []))
+               for q, (seed, mode) in enumerate(zip(THREAD_SEEDS, THREAD_MODES))]
+    assert [len(s) for s in scripts] == [42, 32, 42, 18]
+    assert all(any("_mc_" in op.name for op in s) == (q in MC_THREADS) for q, s in enumerate(scripts))
+    assert sum(op.name.startswith("time_step") for op in scripts[1]) == 4 and sum(op.name.startswith("advect:A") for op in scripts[3]) == 2
     b = _barrier(4, SCRIPT_SECONDS["all value ops, strict"])
     coop = CoopGuard(sum(m != "fast" for m in THREAD_MODES))
     done = run_threads([_script_worker(hip, m, s, b, streams == "own", guard=coop.guard(m == "fast")) for m, s in zip(THREAD_MODES, scripts)],
                        SCRIPT_SECONDS["all value ops, strict"])
     _compare_all(done, THREAD_MODES)
-    assert [len(d[1]) for d in done] == [32, 32, 32, 18]
+    assert [len(d[1]) for d in done] == [42, 32, 42, 18]
 
 
 def _g2_op(dt="f64"):

@@ -242,8 +242,9 @@ def test_pt_persist_on_a_reserved_context(hip, grid, dtype):
 
 
 # ---- A5: a whole time step ----------------------------------------------------------------------------------------------
-def _two_steps(hip, script, reserve):
-    """two ns3d_time_step calls on 24×15×15 from the driver's own initial state, on a context with `reserve` CUs left out"""
+def _two_steps(hip, script, reserve, advection="reference"):
+    """two ns3d_time_step calls on 24×15×15 from the driver's own initial state, on a context with `reserve` CUs left out;
+    advection="maccormack": the knob on and faithful = 0"""
     import torch
     from navierstokes3d_amd import driver as Dr, lib as L
     from navierstokes3d_amd.params import gpu_params, multi_params
@@ -253,9 +254,12 @@ def _two_steps(hip, script, reserve):
     f = Dr._alloc(nx, ny, nz, torch.float64, torch.device("cuda", 0))
     ctx = hip.Context(0, "strict", async_=True)
     ctx.reserve_cus(reserve)
+    ctx.set_advection(advection)
+    niter = 200 if (script, advection) == ("gpu", "maccormack") else p.niter        # test_gpu_footprint.mc_niter says why
     common = dict(nx=nx, ny=ny, nz=nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau, damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz,
-                  eps=p.eps, niter=p.niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy,
-                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=1, pressure=0, write_stress=0)
+                  eps=p.eps, niter=niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy,
+                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=0 if advection == "maccormack" else 1, pressure=0,
+                  write_stress=0)
     if script == "multi":
         f.Vy[0, :, :] = p.vin                                                                        # multi.jl:369
         torch.cuda.synchronize()
@@ -280,19 +284,26 @@ def _two_steps(hip, script, reserve):
 
 
 @pytest.mark.parametrize("script", ["multi", "gpu"])
-def test_time_step_on_a_reserved_context(hip, script):
-    """ns3d_time_step — predictor, PT solve, correction, advection, the boundary rules — 24×15×15, two steps, both scripts:
-    iteration counts, residual histories and all seventeen arrays of a reserved context equal the unreserved context's."""
-    want = _two_steps(hip, script, 0)
+def test_time_step_on_a_reserved_context(hip, script, advection="reference"):
+    """ns3d_time_step — predictor, PT solve, correction, advection (the reference's or the MacCormack scheme, whose two stages meet
+    in the context's hat scratch), the boundary rules — 24×15×15, two steps, both scripts: iteration counts, residual histories and
+    all seventeen arrays of a reserved context equal the unreserved context's."""
+    want = _two_steps(hip, script, 0, advection)
     assert all(it > 0 and len(errs) > 0 for it, errs in want.steps)
     assert np.abs(want.fields["Vx"]).max() > 0 and np.abs(want.fields["Pr"]).max() > 0 and np.abs(want.fields["txx"]).max() > 0
     for res in (64, _half()):
-        got = _two_steps(hip, script, res)
+        got = _two_steps(hip, script, res, advection)
         assert len(got.steps) == len(want.steps)
         for (it, errs), (wit, werrs) in zip(got.steps, want.steps):
             assert it == wit and np.array_equal(errs, werrs, equal_nan=True), (res, it, wit)
         for n, w in want.fields.items():
             assert np.array_equal(got.fields[n], w, equal_nan=True), (res, n)
+
+
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_time_step_on_a_reserved_context_maccormack(hip, script):
+    """the test above over the other value of its `advection` parameter (a test of its own: the existing cases keep their names)"""
+    test_time_step_on_a_reserved_context(hip, script, "maccormack")
 
 
 # ---- A6: the environment preset ------------------------------------------------------------------------------------------

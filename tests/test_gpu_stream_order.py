@@ -171,6 +171,48 @@ def test_advect(hip, delay, entry, dt, mode, form, kind, monkeypatch):
     run_cases(hip, [_advect_cases(entry, grid, cfl, dt) for grid in GRIDS for cfl in (0.9, 2.7)], kind, delay, mode)
 
 
+MC_NEW, MC_OLD, MC_HAT = ("Vx_new", "Vy_new", "Vz_new", "C_new"), ("Vx", "Vy", "Vz", "C"), ("Vx_hat", "Vy_hat", "Vz_hat", "C_hat")
+
+
+def _mc_cases(entry, grid, cfl, dt):
+    """the limited MacCormack advection: "advect_mc" — one call, outputs and hat arrays over a fill; "chain" — copy_advect(faithful=0)
+    into the hat arrays, then advect_correct, whose hat inputs are what the first call has only just enqueued; "correct" —
+    advect_correct alone, its hat inputs (stage 1 of the old fields, tests/advect_mc_ref.py) arriving late with the old fields"""
+    import advect_mc_ref as MC
+    g = geometry(*grid)
+    step = cfl * min(g["dx"], g["dy"], g["dz"])
+    old = fields(*grid, ["vx", "vy", "vz", "c"], 41, NP[dt])
+    hat = MC.stage1(old, step, g["dx"], g["dy"], g["dz"]) if entry == "correct" else [np.full_like(a, 555.0) for a in old]
+    arrays = [(n, np.full_like(a, 777.0), "field") for n, a in zip(MC_NEW, old)] + [(n, a, "field") for n, a in zip(MC_OLD, old)] + \
+             [(n, a, "field") for n, a in zip(MC_HAT, hat)]
+    trios = lambda t: [t[n] for trio in zip(MC_NEW, MC_OLD, MC_HAT) for n in trio]
+
+    def call(hip, ctx, t):
+        if entry == "chain":
+            hip.copy_advect(t["Vx_hat"], t["Vx"], t["Vy_hat"], t["Vy"], t["Vz_hat"], t["Vz"], t["C_hat"], t["C"], step, g["dx"], g["dy"], g["dz"],
+                            False, ctx=ctx)
+        getattr(hip, "advect_mc" if entry == "advect_mc" else "advect_correct")(*trios(t), step, g["dx"], g["dy"], g["dz"], ctx=ctx)
+    return SO.Case("%s %s cfl %g %s" % (entry, GID(grid), cfl, dt), arrays, call)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("form", ["windowed", "global"])
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("entry", ["advect_mc", "chain", "correct"])
+def test_advect_mc(hip, delay, entry, dt, form, kind, monkeypatch):
+    """late inputs, an early reader and an overwrite behind the call(s) on every kind of stream; 70×6×7 at cfl 2.7 (departures up to
+    three cells away, clamped at the thin walls) and 24×15×15 at cfl 0.9"""
+    if form == "global":
+        monkeypatch.setenv("NS3D_ADVECT_GLOBAL", "1")
+    else:
+        monkeypatch.delenv("NS3D_ADVECT_GLOBAL", raising=False)
+    cases = [_mc_cases(entry, (70, 6, 7), 2.7, dt), _mc_cases(entry, (24, 15, 15), 0.9, dt)]
+    if entry == "correct":
+        for c in cases:                  # the late hat inputs are what they claim to be: another field than the old one
+            assert not any(np.array_equal(c.real[h], c.real[o]) for h, o in zip(MC_HAT, MC_OLD))
+    run_cases(hip, cases, kind, delay)
+
+
 # ---- 3. the observers: vortex, sample, tracers_advance, the statistics --------------------------------------------------------------
 def _vortex_case(grid, dt):
     import vortex_ref as VR
@@ -407,9 +449,10 @@ def test_shared_read_backs(hip, delay, dt, kind):
 
 
 # ---- 5b. a whole time step in one call ------------------------------------------------------------------------------------------------
-def _step_case(script, pressure):
+def _step_case(script, pressure, advection="reference"):
     """two ns3d_time_step calls from the driver's own initial state at 24×15×15 (tests/test_gpu_footprint.py::_two_steps_on), fp64;
-    the decoy is a gentle flow (magnitude 1e-2), so that a step taken on it stays finite"""
+    the decoy is a gentle flow (magnitude 1e-2), so that a step taken on it stays finite.  advection="maccormack": the knob on (on
+    every context the case runs on) and faithful = 0; the second step's stage 1 refills the hat scratch the first step's stage 2 read"""
     from navierstokes3d_amd import driver as Dr, lib as L
     from navierstokes3d_amd.params import gpu_params, multi_params
     from test_gpu_footprint import STEP_SHAPES
@@ -425,9 +468,11 @@ def _step_case(script, pressure):
         host["Vx"], host["Pr"] = np.asfortranarray(Vx0), np.asfortranarray(Pr0)
     common = dict(nx=p.nx, ny=p.ny, nz=p.nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau, damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz,
                   eps=p.eps, niter=p.niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy,
-                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=1, pressure=pressure, write_stress=0)
+                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=0 if advection == "maccormack" else 1, pressure=pressure,
+                  write_stress=0)
 
     def call(hip, ctx, t):
+        assert ctx.advection() == advection
         f = SimpleNamespace(**t)
         if script == "multi":
             hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly, p.lz,
@@ -441,21 +486,34 @@ def _step_case(script, pressure):
             sp.write_stress = 1 if step == 2 else 0
             out.append(hip.time_step(f, sp, ctx=ctx))
         return out
-    return SO.Case("time_step %s pressure %d" % (script, pressure), [(k, a, ("field", 1e-2)) for k, a in host.items()], call, blocking=True)
+    return SO.Case("time_step %s pressure %d%s" % (script, pressure, "" if advection == "reference" else " " + advection),
+                   [(k, a, ("field", 1e-2)) for k, a in host.items()], call, blocking=True, setup=lambda ctx: ctx.set_advection(advection))
 
 
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("pressure", [0, 1])
 @pytest.mark.parametrize("script", ["multi", "gpu"])
-def test_time_step(hip, delay, script, pressure, kind):
+def test_time_step(hip, delay, script, pressure, kind, advection="reference"):
     """Two steps, every array of ns3d_step_fields (the arrays are compared by buffer: the step swaps roles, the same way in every
     run), iteration counts and residual histories.  pressure 1 reads its one residual back through the shared key word behind the
     rest of the step; the second step's start must not disturb it."""
-    case = _step_case(script, pressure)
+    case = _step_case(script, pressure, advection)
     (want_r, want), _ = SO.expected(hip, case)
     assert all(len(errs) > 0 for _, errs in want_r) and (pressure == 1 or all(it > 0 for it, _ in want_r)), want_r
     assert all(np.isfinite(a).all() for a in want.values()) and np.abs(want["Pr"]).max() > 0
     run_cases(hip, [case], kind, delay)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("pressure", [0, 1])
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_time_step_maccormack(hip, delay, script, pressure, kind):
+    """test_time_step over the other value of its `advection` parameter (a test of its own: the existing cases keep their names).
+    The scheme is another one: the expected bits differ from the reference step's."""
+    test_time_step(hip, delay, script, pressure, kind, "maccormack")
+    (_, mc), _ = SO.expected(hip, _step_case(script, pressure, "maccormack"))
+    (_, ref), _ = SO.expected(hip, _step_case(script, pressure))
+    assert not np.array_equal(mc["Vx"], ref["Vx"])
 
 
 # ---- 5c. the lazy paths INSIDE the window: a cold context, nothing warmed up on it ----------------------------------------------------------
