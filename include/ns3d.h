@@ -31,6 +31,7 @@
  *        ns3d_max_abs, ns3d_residual_max        the value it returns               (none)
  *        ns3d_diagnostics                       the record it returns              (none)
  *        ns3d_selftest_exact_div                the count it returns               (none)
+ *        ns3d_solid_momentum                    the sums and counts it returns     (none)
  *        ns3d_isosurface                        the triangle count                 no: tri / val are enqueued behind the count
  *        ns3d_tracers_migrate_mgpu              the counts of leavers and empty    no: pack, exchange and insert are enqueued behind them
  *                                               slots of every rank
@@ -47,7 +48,8 @@
  *                                               replaces its plan (a new grid)
  *        any call that grows a scratch buffer   the stream, before the old         as the call otherwise
  *        of the context (ping-pong, monitor,    buffer is freed
- *        isosurface) and ns3d_reserve_cus
+ *        isosurface, voxelizer) and
+ *        ns3d_reserve_cus
  *        ns3d_set_stream, ns3d_use_own_stream,  the stream the context LEAVES       (none)
  *        ns3d_reserve_cus                       (when it differs from the new one)
  *    Everything else only enqueues.
@@ -199,6 +201,12 @@ int ns3d_cached_graphs(const ns3d_ctx *ctx);      /* residual-check blocks this 
 #define NS3D_ADVECT_MACCORMACK 1
 int ns3d_set_advection(ns3d_ctx *ctx, int scheme);
 int ns3d_advection(const ns3d_ctx *ctx);
+/* What ns3d_time_step masks with.  NULL (the default): set_cylinder! with the scalars of ns3d_step_params.  A mask (device memory, the
+ * bytes ns3d_voxelize writes for the grid the step is called on; the caller keeps it alive): ns3d_set_solid with it in place of BOTH
+ * set_cylinder! calls of the step, in either script; the cylinder scalars of ns3d_step_params are then ignored.  ns3d_obstacle returns
+ * the setting (NULL for a null context).  Nothing else reads the knob: the single calls are what their names say. */
+int ns3d_set_obstacle(ns3d_ctx *ctx, const unsigned char *mask);
+const unsigned char *ns3d_obstacle(const ns3d_ctx *ctx);
 
 /* Parameters of the fused pseudo-transient path (ns3d_pt_iterate / ns3d_pt_solve). */
 typedef struct ns3d_pt_params {
@@ -306,6 +314,52 @@ int ns3d_stats_reset(ns3d_ctx *, double *S, int nx, int ny, int nz);
  * division is the plain IEEE quotient; product and subtraction are not contracted in STRICT.  wsum is the sum of the weights
  * accumulated so far.  NS3D_ERR_ARG: null context / S / mean, a grid below 3×3×3, wsum not finite or not greater than 0. */
 int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, double *rs, int nx, int ny, int nz);
+
+/* Obstacles from triangle meshes: the way back from a closed triangle surface (what ns3d_isosurface emits) to the four staggered
+ * masks of set_cylinder!, made on the device.  The masking method needs no more than the analytic test replaced by a stored one.
+ * THE MASK is one unsigned char per point of set_cylinder!'s thread range (nx+1, ny+1, nz+1), column-major, x fastest:
+ *   bit 0  C   cell centre (i+.5, j+.5, k+.5)   valid for i<nx, j<ny, k<nz        bit 1  Vx  (i, j+.5, k+.5)   valid for j<ny, k<nz
+ *   bit 2  Vy  (i+.5, j, k+.5)                  valid for i<nx, k<nz              bit 3  Vz  (i+.5, j+.5, k)   valid for i<nx, j<ny
+ * Positions are in the index space of ns3d_sample: the cell grid occupies [0,nx] x [0,ny] x [0,nz].  Bits at invalid points and bits
+ * 4-7 are always 0; one call writes the mask completely.
+ * ns3d_voxelize: tri holds 9 doubles per triangle (x0,y0,z0,x1,y1,z1,x2,y2,z2), fp64 whatever the fields are.  origin (may be NULL:
+ * zeros) is three ints: the sample point of local (i,j,k) is (double)(i+origin_x) + s, likewise in y and z, s = 0 or 0.5 — exact, so
+ * the ranks of a decomposed grid, each with origin[q] = co[q]*(n[q]-2), compute identical bits at the entries they duplicate.  The
+ * mesh must be closed; orientation is not used; an open mesh gives a well-defined but meaningless mask.
+ * A sample point is INSIDE if a ray from it towards -x crosses the surface an odd number of times.  Every decision is a stated fp64
+ * comparison and nothing is contracted, in any build: STRICT, NS3D_IEEE_DIV and FAST contexts return the same bytes.  For a row
+ * r = (y, z) and a triangle (a, b, c) as stored:
+ *   side(p, q, r) on the yz-projections: if (q.y, q.z) < (p.y, p.z) lexicographically, it is -side(q, p, r).  Otherwise dy = q.y-p.y,
+ *     dz = q.z-p.z, E = dy*(r.z-p.z) - dz*(r.y-p.y); +1 if E > 0, -1 if E < 0, and if E == 0 the tie dz>0 ? -1 : dz<0 ? +1 : dy>0 ? +1 : 0
+ *     (the sign of E at r + (eps, eps^2)).  An edge shared by two triangles is evaluated from the same ordered end points by both: a
+ *     point on the edge belongs to exactly one of them.
+ *   the triangle COVERS r when its nine coordinates are finite, min y <= r.y <= max y and min z <= r.z <= max z over its vertices (by
+ *     comparisons), and side(a,b,r) == side(b,c,r) == side(c,a,r) != 0.
+ *   CROSSING: u = b-a, v = c-a, n = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x),
+ *     xs = a.x - (n.y*(y - a.y) + n.z*(z - a.z))/n.x with a plain IEEE quotient; the triangle is ignored for this row if n.x == 0 or xs
+ *     is not finite.
+ *   FLIP: for a sample family with x positions (i + origin_x) + s, 0 <= i < ext: t = xs - (double)(origin_x + s),
+ *     i0 = t <= 0 ? 0 : t >= ext ? ext : (int)ceil(t); every sample i >= i0 flips (a sample exactly on the surface counts as beyond it).
+ *   A bit is the parity of the flips of all triangles.
+ * Row families (with an origin the rows are (j+origin_y ..., k+origin_z ...)): (j+.5, k+.5) serves bit 0 with s = .5, ext = nx and bit 1
+ * with s = 0, ext = nx+1 (one cover test, two flips); (j, k+.5) serves bit 2 and (j+.5, k) bit 3, both with s = .5, ext = nx.
+ * For an axis-parallel box with faces on sample points the set is half-open: lo <= p < hi in every direction.  In general a sample on
+ * the surface is decided as the point (x + d, y + eps, z + eps^2) with d >> eps: first along +x, then +y, then +z.
+ * As NumPy, for the rows Y, Z (1, R) of a family and the triangles' coordinate columns ax ... cz (T, 1), all float64:
+ *   def side(py, pz, qy, qz):
+ *       sw = (qy < py) | ((qy == py) & (qz < pz));  ay, az, by, bz = where(sw, qy, py), where(sw, qz, pz), where(sw, py, qy), where(sw, pz, qz)
+ *       dy, dz = by - ay, bz - az;  E = dy*(Z - az) - dz*(Y - ay)
+ *       s = where(E > 0, 1, where(E < 0, -1, where(dz > 0, -1, where(dz < 0, 1, where(dy > 0, 1, 0)))));  return where(sw, -s, s)
+ *   cover = finite & (miny <= Y) & (Y <= maxy) & (minz <= Z) & (Z <= maxz) & (s1 == s2) & (s2 == s3) & (s1 != 0)
+ *   xs = ax - (n_y*(Y - ay) + n_z*(Z - az))/n_x;  hit = cover & (n_x != 0) & isfinite(xs);  t = xs - (origin_x + s)
+ *   i0 = where(t <= 0, 0, where(t >= ext, ext, ceil(t)));  bit[i, row] = (number of hits of the row with i0 <= i) & 1
+ * (tests/solid_ref.py is this statement.)  Two calls on the same input return the same bytes, and permuting the triangles changes
+ * nothing: each covered (triangle, row) XORs one bit into a packed bit plane of the context's scratch — four planes of (ny+1)(nz+1)
+ * rows x ceil((nx+2)/32) words, grown lazily and zeroed on the context's stream — and a prefix parity along x makes the bytes.  The
+ * call only enqueues (it blocks as every call does without NS3D_ASYNC).  n_tri == 0 writes an all-zero mask.
+ * NS3D_ERR_ARG, with nothing written: a null context, a null mask, a null tri with n_tri > 0, n_tri < 0, a grid below 3x3x3, a negative
+ * origin entry. */
+int ns3d_voxelize(ns3d_ctx *, unsigned char *mask, const double *tri, long long n_tri, int nx, int ny, int nz, const int *origin);
 
 #define NS3D_DECL(T, S)                                                                                     \
     /* One sample: per cell and slot S = S + weight·term, term = u, v, w, p, u·u, v·v, w·w, u·v, u·w, v·w, p·p evaluated in   \
@@ -496,6 +550,19 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
     int ns3d_set_cylinder_local_##S(ns3d_ctx *, T *C, T *Vx, T *Vy, T *Vz, double a2, double b2, double ox,  \
                                     double oy, double sinb, double cosb, double lx, double ly, double lz,    \
                                     double dx, double dy, double dz, int nx, int ny, int nz);                \
+    /* What set_cylinder! stores, with the flags read from a mask (ns3d_voxelize above): where bit 0 is set C = 1, bit 1 Vx = 0, bit 2      \
+     * Vy = 0, bit 3 Vz = 0; everything else is untouched.  Bits at invalid points are ignored, not trusted: no address outside the      \
+     * arrays is touched whatever the bytes hold.  C may be NULL.  Enqueued on the context's stream, no read-back.  NS3D_ERR_ARG: a null   \
+     * context, velocity or mask. */                                                                                                    \
+    int ns3d_set_solid_##S(ns3d_ctx *, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, int nx, int ny, int nz);                    \
+    /* The monitor's mom[q] / n_masked[q] for a mask: the sum and the number of the OWNED nodes of Vx (Vy, Vz) whose mask bit is set —   \
+     * what the next ns3d_set_solid removes.  The owned ranges are those of ns3d_diagnostics; seam_lo / seam_hi (three ints each) may be \
+     * NULL: no seams.  Values are converted to double on load and reduced in fp64 in the monitor's fixed order (per thread down its    \
+     * planes, wave64 butterfly, one LDS slot per wave, per-workgroup partials in the context's scratch, a second small launch): two     \
+     * calls return the same bits, in every arithmetic mode.  mom_host and n_host (host memory, three entries each) receive the results; \
+     * the call blocks for this read-back like ns3d_max_abs.  NS3D_ERR_ARG: a null context or pointer, a grid below 3x3x3. */            \
+    int ns3d_solid_momentum_##S(ns3d_ctx *, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny, int nz,    \
+                                const int *seam_lo, const int *seam_hi, double *mom_host, long long *n_host);                           \
     /* update_∇V!(∇V,Vx,Vy,Vz,dx,dy,dz)                             multi.jl:61-64   gpu.jl:194-197 */        \
     int ns3d_update_divV_##S(ns3d_ctx *, T *divV, const T *Vx, const T *Vy, const T *Vz, double dx,          \
                              double dy, double dz, int nx, int ny, int nz);                                  \

@@ -30,6 +30,8 @@ UNITS = [
     ("ns3d_tracers.hip", "ns3d_tracers.o", ["-ffp-contract=off"]),
     # ns3d_isosurface: likewise
     ("ns3d_isosurface.hip", "ns3d_isosurface.o", ["-ffp-contract=off"]),
+    # ns3d_voxelize / ns3d_set_solid / ns3d_solid_momentum: likewise
+    ("ns3d_solid.hip", "ns3d_solid.o", ["-ffp-contract=off"]),
     ("ns3d_api.cpp", "ns3d_api.o", ["-x", "hip"]),
     ("ns3d_mgpu.cpp", "ns3d_mgpu.o", ["-x", "hip"]),
 ]

@@ -165,6 +165,7 @@ void ns3d_destroy(ns3d_ctx *c)
     if (c->diag_host) (void)hipHostFree(c->diag_host);
     if (c->iso_dev) (void)hipFree(c->iso_dev);
     if (c->mc_hat) (void)hipFree(c->mc_hat);
+    if (c->solid_dev) (void)hipFree(c->solid_dev);
     if (c->key_dev) (void)hipFree(c->key_dev);
     if (c->key_host) (void)hipHostFree(c->key_host);
     if (c->masked_stream) { (void)hipStreamSynchronize(c->masked_stream); (void)hipStreamDestroy(c->masked_stream); }
@@ -341,6 +342,14 @@ int ns3d_set_advection(ns3d_ctx *c, int scheme)
     return NS3D_OK;
 }
 int ns3d_advection(const ns3d_ctx *c) { return c ? c->advection : -1; }
+
+int ns3d_set_obstacle(ns3d_ctx *c, const unsigned char *mask)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_obstacle: null context");
+    c->obstacle = mask;
+    return NS3D_OK;
+}
+const unsigned char *ns3d_obstacle(const ns3d_ctx *c) { return c ? c->obstacle : nullptr; }
 
 int ns3d_set_pt2_variant(ns3d_ctx *c, int v)
 {
@@ -1160,6 +1169,31 @@ static int iso_prepare(ns3d_ctx *c, int ex, int ey, int ez, const int *box, cons
     w->segbase = w->bsum + w->nblk;
     w->segcnt = (unsigned *)(w->segbase + w->nsegs);
     return NS3D_OK;
+}
+// ---- ns3d_voxelize / ns3d_set_solid / ns3d_solid_momentum (ns3d_solid.hip) ----------------------------------------------------------
+// the scratch both share: grown lazily, after a wait for the stream (the header's table)
+static int ensure_solid(ns3d_ctx *c, size_t need)
+{
+    if (c->solid_bytes >= need) return NS3D_OK;
+    if (c->solid_dev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->solid_dev); c->solid_dev = nullptr; c->solid_bytes = 0; }
+    HIPCHK(c, hipMalloc(&c->solid_dev, need));
+    c->solid_bytes = need;
+    return NS3D_OK;
+}
+extern "C" int ns3d_voxelize(ns3d_ctx *c, unsigned char *mask, const double *tri, long long n_tri, int nx, int ny, int nz, const int *origin)
+{
+    CHECK_CTX(c);
+    if (!mask) return fail(NS3D_ERR_ARG, "%s: null mask", __func__);
+    if (n_tri < 0) return fail(NS3D_ERR_ARG, "%s: n_tri = %lld is negative", __func__, n_tri);
+    if (!tri && n_tri > 0) return fail(NS3D_ERR_ARG, "%s: tri is NULL with n_tri = %lld", __func__, n_tri);
+    if (n_tri > 4ll * 0x7fffffffll) return fail(NS3D_ERR_ARG, "%s: n_tri = %lld exceeds one launch (4 x 2^31 triangles)", __func__, n_tri);
+    CHECK_GRID(nx, ny, nz, 3);
+    const int zero[3] = {0, 0, 0};
+    const int *o = origin ? origin : zero;
+    if (o[0] < 0 || o[1] < 0 || o[2] < 0) return fail(NS3D_ERR_ARG, "%s: origin %d, %d, %d (each >= 0)", __func__, o[0], o[1], o[2]);
+    const int rc = ensure_solid(c, ns3d_solid::voxelize_scratch_bytes(nx, ny, nz));
+    if (rc) return rc;
+    return finish(c, ns3d_solid::voxelize(c->stream, mask, tri, n_tri, nx, ny, nz, o, c->solid_dev), "voxelize");
 }
 extern "C" int ns3d_poisson_direct_f64(ns3d_ctx *, double *, double *, const double *, const ns3d_pt_params *);      // ns3d_direct.hip
 extern "C" int ns3d_poisson_direct_f32(ns3d_ctx *, float *, float *, const float *, const ns3d_pt_params *);

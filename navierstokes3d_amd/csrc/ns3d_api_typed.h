@@ -43,6 +43,30 @@ extern "C" int NS3D_FN(set_cylinder_local)(ns3d_ctx *c, T *C, T *Vx, T *Vy, T *V
     return finish(c, DISPATCH(c, set_cylinder<T>(c->stream, C, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb, 1, 0.0, 0.0, lx, ly, dx, dy, nx, ny, nz)),
                   "set_cylinder_local");
 }
+// ns3d_set_solid / ns3d_solid_momentum: one kernel build for every arithmetic mode (ns3d_solid.hip), hence no DISPATCH
+extern "C" int NS3D_FN(set_solid)(ns3d_ctx *c, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, mask); CHECK_GRID(nx, ny, nz, 1);
+    return finish(c, ns3d_solid::set_solid<T>(c->stream, C, Vx, Vy, Vz, mask, nx, ny, nz), "set_solid");
+}
+extern "C" int NS3D_FN(solid_momentum)(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny, int nz,
+                                       const int *seam_lo, const int *seam_hi, double *mom_host, long long *n_host)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, mask, mom_host, n_host); CHECK_GRID(nx, ny, nz, 3);
+    const int zero[3] = {0, 0, 0};
+    const int rc = ensure_solid(c, ns3d_solid::momentum_scratch_bytes(nx, ny, nz));
+    if (rc) return rc;
+    hipError_t e = ns3d_solid::momentum<T>(c->stream, Vx, Vy, Vz, mask, nx, ny, nz, seam_lo ? seam_lo : zero, seam_hi ? seam_hi : zero,
+                                           c->solid_dev, c->key_dev);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "solid_momentum launch: %s", hipGetErrorString(e)); }
+    HIPCHK(c, hipMemcpyAsync(c->key_host, c->key_dev, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int q = 0; q < 3; ++q) {
+        std::memcpy(&mom_host[q], &c->key_host[q], sizeof(double));
+        n_host[q] = (long long)c->key_host[3 + q];
+    }
+    return NS3D_OK;
+}
 extern "C" int NS3D_FN(update_divV)(ns3d_ctx *c, T *divV, const T *Vx, const T *Vy, const T *Vz, double dx, double dy, double dz, int nx,
                                     int ny, int nz)
 {
@@ -440,7 +464,8 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
     bool deferred_residual = false;
     T *Vx = (T *)f->Vx, *Vy = (T *)f->Vy, *Vz = (T *)f->Vz, *Vxo = (T *)f->Vx_o, *Vyo = (T *)f->Vy_o, *Vzo = (T *)f->Vz_o;
     T *C = (T *)f->C, *Co = (T *)f->C_o, *Pr = (T *)f->Pr, *D = (T *)f->dPrdtau, *divV = (T *)f->divV;
-    auto cylinder = [&]() -> int {          // multi.jl:249-281 (global coordinates) / gpu.jl:336-368 (local)
+    auto cylinder = [&]() -> int {          // multi.jl:249-281 (global coordinates) / gpu.jl:336-368 (local); ns3d_set_obstacle: the mask
+        if (c->obstacle) return NS3D_FN(set_solid)(c, C, Vx, Vy, Vz, c->obstacle, nx, ny, nz);
         return p->script == NS3D_BC_MULTI
                    ? NS3D_FN(set_cylinder)(c, C, Vx, Vy, Vz, p->a2, p->b2, p->ox, p->oy, p->sinb, p->cosb, p->xco_g, p->yco_g, p->zco_g, p->lx,
                                            p->ly, p->lz, p->dx, p->dy, p->dz, nx, ny, nz)

@@ -56,6 +56,9 @@ struct ns3d_ctx {
     int advection = 0;                      // ns3d_set_advection: what ns3d_time_step advects with (NS3D_ADVECT_*)
     void *mc_hat = nullptr;                 // ns3d_time_step under NS3D_ADVECT_MACCORMACK: stage 1's four complete fields (grown lazily)
     size_t mc_hat_bytes = 0;
+    void *solid_dev = nullptr;              // ns3d_voxelize's bit planes / ns3d_solid_momentum's partials (grown lazily; one stream orders both)
+    size_t solid_bytes = 0;
+    const unsigned char *obstacle = nullptr; // ns3d_set_obstacle: the caller's mask ns3d_time_step masks with; null: the cylinder
     void clear_graphs()
     {
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.exec);
@@ -233,4 +236,19 @@ hipError_t mig_pack(hipStream_t s, const ns3d_mig_scratch &w, double *rec, doubl
                     long cap);
 hipError_t mig_insert(hipStream_t s, const ns3d_mig_scratch &w, int P, const double *rec, long n_arr, double *X, unsigned char *state,
                       long long *id, double *U, long cap);
+}
+
+// ---- ns3d_solid.hip: ns3d_voxelize / ns3d_set_solid / ns3d_solid_momentum.  One compilation without contraction serves every
+// arithmetic mode.  voxelize: origin is three ints (not null), scratch holds voxelize_scratch_bytes (zeroed inside, on s); momentum:
+// seam flags not null, scratch holds momentum_scratch_bytes, result receives 3 sums (fp64 bit patterns) and 3 counts.
+namespace ns3d_solid {
+size_t voxelize_scratch_bytes(int nx, int ny, int nz);
+hipError_t voxelize(hipStream_t s, unsigned char *mask, const double *tri, long long n_tri, int nx, int ny, int nz, const int *origin,
+                    void *scratch);
+template <class T>
+hipError_t set_solid(hipStream_t s, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, int nx, int ny, int nz);
+size_t momentum_scratch_bytes(int nx, int ny, int nz);
+template <class T>
+hipError_t momentum(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny, int nz,
+                    const int *seam_lo, const int *seam_hi, void *scratch, unsigned long long *result);
 }

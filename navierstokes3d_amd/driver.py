@@ -193,7 +193,8 @@ def pt_loop_fused_slab(ctx, grid, f, p, pt, niter, do_print=False, scratch=None)
 def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=10, *, mode="strict", fused=True,
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
-                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None, advection="reference"):
+                       statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None, advection="reference",
+                       obstacle=None):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -259,7 +260,14 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     scheme (ns3d_advect_mc: second order where the reference's backtrack! is first order; include/ns3d.h has the definition) — with
     `one_call` inside ns3d_time_step (Context.set_advection), otherwise as one advect_mc call per step; the same bits either way.  It
     advects Vz, so it needs faithful=False, and it runs on one rank: anything else raises Ns3dError before the first step.  Every
-    observer keyword keeps working."""
+    observer keyword keeps working.
+    obstacle=… (default None: the reference's cylinder, not one extra call; OUTSIDE the reference): the body the flow goes around, in
+    place of every set_cylinder! call (:372, :452, :473) — an (n,3,3) array, a closed triangle surface in the index space of the cell
+    grid (solid.box_mesh, solid.from_isosurface, solid.load_ply with solid.to_index), voxelized once on the device (ns3d_voxelize),
+    or a ready uint8 mask of (nx+1)(ny+1)(nz+1) bytes (solid.voxelize, solid.mask_of_cylinder).  With `one_call` the step masks
+    inside ns3d_time_step (Context.set_obstacle), otherwise with one set_solid call where set_cylinder stands; the same bits either
+    way.  With diagnostics=True, force comes from ns3d_solid_momentum taken before each of the step's two maskings.  One rank:
+    anything else raises Ns3dError before the first step."""
     _check_advection(advection)
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
@@ -298,8 +306,10 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     grid.update_halo(col("Pr"))                                                               # :371
     cyls = [(q.a2, q.b2, q.ox, q.oy, q.sinb, q.cosb, q.xco_g, q.yco_g, q.zco_g, q.lx, q.ly, q.lz, q.dx, q.dy, q.dz)
             for q in ps]
+    solid = _obstacle_mask(obstacle, P, ctxs[0], (nx, ny, nz))
+    body = _body(solid)
     for f, c, cyl in zip(fs, ctxs, cyls):
-        K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                                    # :372
+        body(f, cyl, c)                                                                       # :372
     grid.update_halo(col("C"), col("Vx"), col("Vy"), col("Vz"))                               # :373
     sync = lambda: [c.sync() for c in ctxs]
     iframe = 0
@@ -341,7 +351,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         if P > 1 and mg is None:
             raise L.Ns3dError("diagnostics on %d ranks needs the C-ABI grid (mgpu.MgpuGrid)" % P)
         info.diag = []
-        monitor = _monitor(grid, ctxs, fs, cyls, p)
+        monitor = _monitor(grid, ctxs, fs, cyls if solid is None else [None], p)
+    removed = _removed(monitor, solid, fs, ctxs)
     obs.start()
     nsave = nvis = 10                                                                         # :330,332
     # :450's halo update of the normal stresses may only go with the stress arrays where the interior planes two ranks both compute
@@ -354,6 +365,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     step_params = None
     if fused and one_call and P == 1 and mg is None and not diagnostics:
         step_params = _step_params(L.NS3D_BC_MULTI, p, niter, faithful, pressure)
+    if solid is not None and step_params is not None:
+        ctxs[0].set_obstacle(solid)                             # ns3d_time_step masks with it; back to the cylinder after the loop
     hats = None
     if maccormack and step_params is not None:
         ctxs[0].set_advection("maccormack")                     # ns3d_time_step advects with it; back to the default after the loop
@@ -383,9 +396,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                     K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
                                 ctx=c)                                                        # :451
             if monitor:
-                mom_predict = monitor(False).mom
+                mom_predict = removed()
             for f, c, cyl in zip(fs, ctxs, cyls):
-                K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                            # :452
+                body(f, cyl, c)                                                               # :452
             grid.update_halo(col("C"), col("Vx"), col("Vy"), col("Vz"))                       # :453
             for f, c in zip(fs, ctxs):
                 K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=c)              # :454
@@ -417,9 +430,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             for f, c in zip(fs, ctxs):
                 K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=c)     # :472
             if monitor:
-                mom_correct = monitor(False).mom
+                mom_correct = removed()
             for f, c, cyl, q in zip(fs, ctxs, cyls, ps):
-                K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)                            # :473
+                body(f, cyl, c)                                                               # :473
                 K.set_bc_Vel_multi(f.Vx, f.Vy, f.Vz, q.owns_inlet, p.vin, ctx=c)              # :474 → :157-166
             grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                 # :167
             if monitor:
@@ -452,6 +465,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
     if maccormack and step_params is not None:
         ctxs[0].set_advection("reference")
+    if solid is not None and step_params is not None:
+        ctxs[0].set_obstacle(None)
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
             K.copy(f.Vz_o, f.Vz, ctx=c)     # the one copy of :475 the swaps skipped (Vz is never advected): same final state
@@ -486,6 +501,47 @@ def _copy_advect_swap(f, p, faithful, ctx):
     f.C, f.C_o = f.C_o, f.C
     if not faithful:
         f.Vz, f.Vz_o = f.Vz_o, f.Vz
+
+
+def _obstacle_mask(obstacle, P, ctx, n):
+    """the `obstacle` keyword of both drivers → None (the cylinder) or the uint8 device mask of the cell grid n; raises before anything
+    is advanced"""
+    if obstacle is None:
+        return None
+    if P != 1:
+        raise L.Ns3dError("obstacle= runs on one rank (this grid has %d): the ranks of a decomposed grid voxelize with their own origin "
+                          "through solid.voxelize" % P)
+    from . import solid as S
+    nbytes = (n[0] + 1) * (n[1] + 1) * (n[2] + 1)
+    if isinstance(obstacle, torch.Tensor) and obstacle.dtype == torch.uint8:
+        mask = obstacle.to(torch.device("cuda", ctx.device))
+    elif isinstance(obstacle, np.ndarray) and obstacle.dtype == np.uint8:
+        mask = torch.from_numpy(np.ascontiguousarray(np.asarray(obstacle).reshape(-1, order="F"))).to(torch.device("cuda", ctx.device))
+    else:
+        tri = np.asarray(obstacle, dtype=np.float64)
+        if tri.ndim != 3 or tri.shape[1:] != (3, 3):
+            raise L.Ns3dError("obstacle: an (n,3,3) array of triangles in index space, or a uint8 mask; got shape %r" % (tri.shape,))
+        return S.voxelize(ctx, tri, *n)
+    if mask.numel() != nbytes:
+        raise L.Ns3dError("obstacle: the mask has %d bytes, a %dx%dx%d grid needs %d" % ((mask.numel(),) + tuple(n) + (nbytes,)))
+    ctx.after_torch_fill()
+    return mask
+
+
+def _body(solid):
+    """what stands where the reference calls set_cylinder!: the cylinder's analytic test, or ns3d_set_solid with the obstacle's mask"""
+    if solid is None:
+        return lambda f, cyl, c: K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)
+    return lambda f, cyl, c: K.set_solid(f.C, f.Vx, f.Vy, f.Vz, solid, ctx=c)
+
+
+def _removed(monitor, solid, fs, ctxs):
+    """diagnostics=True: the momentum the next masking call removes — the monitor's masked sums, or ns3d_solid_momentum for an obstacle"""
+    if monitor is None:
+        return None
+    if solid is None:
+        return lambda: monitor(False).mom
+    return lambda: K.solid_momentum(fs[0].Vx, fs[0].Vy, fs[0].Vz, solid, ctx=ctxs[0])[0]
 
 
 def _check_advection(advection, faithful=False, P=1):
@@ -548,7 +604,7 @@ def _save_mat(path, f, p, step0):
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
           diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None,
-          advection="reference"):
+          advection="reference", obstacle=None):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -565,7 +621,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     each MAT file (numbered 0, 1, … in the order the MAT files are written), do_vis 3D_NavierStokes_tracers_%04d.png per frame.
     isosurface: as in run_navierstokes3D, of the final state → info.isosurface; do_save adds out_save/out_iso_%04d.ply beside each
     MAT file (numbered like the tracer dumps).
-    advection: as in run_navierstokes3D, in place of :141-142; "maccormack" needs faithful=False."""
+    advection: as in run_navierstokes3D, in place of :141-142; "maccormack" needs faithful=False.
+    obstacle: as in run_navierstokes3D, in place of the set_cylinder! calls :123 and :139."""
     maccormack = _check_advection(advection, faithful)
     if device is None:
         device = torch.cuda.current_device()
@@ -584,6 +641,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     cyl = (p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.lx, p.ly, p.lz, p.dx, p.dy, p.dz)
     pt = K.pt_params(f.Pr, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, L.NS3D_BC_GPU, False, 0.0, p.g)
     info = SimpleNamespace(iters=[], errs=[], params=p)
+    solid = _obstacle_mask(obstacle, 1, ctx, (nx, ny, nz))
+    body = _body(solid)
     nsave = nvis = 10                                                                         # :50,52
     obs = Observers(grid, [ctx], p, nt, dtype, gathered=False, **watch)
     iframe = 0
@@ -608,11 +667,14 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     monitor = None
     if diagnostics:
         info.diag = []
-        monitor = _monitor(grid, [ctx], [f], [cyl], p)
+        monitor = _monitor(grid, [ctx], [f], [cyl if solid is None else None], p)
+    removed = _removed(monitor, solid, [f], [ctx])
     obs.start()
     step_params = None
     if fused and one_call and not diagnostics:
         step_params = _step_params(L.NS3D_BC_GPU, p, niter, faithful, pressure)
+    if solid is not None and step_params is not None:
+        ctx.set_obstacle(solid)                             # ns3d_time_step masks with it (the context is this run's own)
     hats = None
     if maccormack and step_params is not None:
         ctx.set_advection("maccormack")                     # ns3d_time_step advects with it (the context is this run's own)
@@ -632,8 +694,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
                 K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
                             ctx=ctx)                                                          # :122
             if monitor:
-                mom_predict = monitor(False).mom
-            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                              # :123
+                mom_predict = removed()
+            body(f, cyl, ctx)                                                                 # :123
             K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz, ctx=ctx)                # :124
             if pressure == "direct":        # (:125, :134 print after the step)  outside parity: the exact solution of what :126-137 iterates towards
                 K.poisson_direct(f.Pr, f.dPrdtau, f.divV, pt, ctx=ctx)
@@ -655,8 +717,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
                             break
             K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz, ctx=ctx)       # :138
             if monitor:
-                mom_correct = monitor(False).mom
-            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=ctx)                              # :139
+                mom_correct = removed()
+            body(f, cyl, ctx)                                                                 # :139
             K.set_bc_Vel_gpu(f.Vx, f.Vy, f.Vz, ctx=ctx)                                       # :140
             if monitor:
                 info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
@@ -676,6 +738,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             drawn()
         if do_save and it % nsave == 0:                                                       # :168-170
             saved(it)
+    if solid is not None and step_params is not None:
+        ctx.set_obstacle(None)
     if fused and faithful and nt > 0:
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()

@@ -207,6 +207,17 @@ class Context:
     def advection(self):
         return {L.NS3D_ADVECT_REFERENCE: "reference", L.NS3D_ADVECT_MACCORMACK: "maccormack"}[int(self.lib.ns3d_advection(self.handle))]
 
+    def set_obstacle(self, mask):
+        """What ns3d_time_step masks with: a uint8 mask tensor (voxelize's, of the grid the step runs on; kept alive here until it is
+        replaced) in place of both set_cylinder! calls, or None: back to the cylinder.  The single calls do not read it."""
+        ptr = None if mask is None else _chk_mask(mask, None, mask)
+        L.check(self.lib.ns3d_set_obstacle(self.handle, ptr))
+        self._obstacle = mask
+
+    def obstacle(self):
+        """the device address ns3d_time_step masks with; None: the cylinder"""
+        return self.lib.ns3d_obstacle(self.handle)
+
     def set_pt_depth(self, depth):
         """PT iterations per pass over memory in pt_iterate / pt_solve: 0 automatic, 1…4 forced (5: float32 fields only)."""
         L.check(self.lib.ns3d_set_pt_depth(self.handle, int(depth)))
@@ -304,6 +315,55 @@ def set_cylinder(Cf, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb, *rest, ctx=None):
         _ctx(ctx, Cf).call("set_cylinder_local", Cf, *ptrs, *_d(a2, b2, ox, oy, sinb, cosb, *rest), nx, ny, nz)
     else:
         raise TypeError("set_cylinder: expected 19 (multi.jl) or 16 (gpu.jl) positional arguments")
+
+
+def _chk_mask(mask, n, ref):
+    """a contiguous uint8 device array of (nx+1)(ny+1)(nz+1) bytes on ref's device (any shape; column-major, x fastest, in memory)"""
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.uint8:
+        raise L.Ns3dError("mask must be a uint8 CUDA/HIP tensor")
+    if mask.device != ref.device:
+        raise L.Ns3dError("mask is on %s, the fields on %s" % (mask.device, ref.device))
+    if n is not None and mask.numel() != (n[0] + 1) * (n[1] + 1) * (n[2] + 1):
+        raise L.Ns3dError("mask has %d bytes, a %dx%dx%d grid needs %d" % ((mask.numel(),) + tuple(n) + ((n[0] + 1) * (n[1] + 1) * (n[2] + 1),)))
+    if not (mask.is_contiguous() or (mask.dim() == 3 and mask.permute(2, 1, 0).is_contiguous())):
+        raise L.Ns3dError("mask must be contiguous, or column-major like the fields")
+    return C.c_void_p(mask.data_ptr())
+
+
+def voxelize(mask, tri, n, origin=None, ctx=None):
+    """ns3d_voxelize: the four staggered masks of the closed triangle surface `tri` (a contiguous float64 device array of 9 doubles per
+    triangle, index space) on the cell grid n = (nx, ny, nz), into `mask` ((nx+1)(ny+1)(nz+1) uint8: bit 0 C, 1 Vx, 2 Vy, 3 Vz at their
+    stagger locations; include/ns3d.h has the rule, the same bytes in every arithmetic mode).  origin: the rank's first cell in the
+    global index space.  Enqueues; no read-back."""
+    nx, ny, nz = (int(q) for q in n)
+    n_tri = 0
+    ptr = None
+    if tri is not None:
+        if not isinstance(tri, torch.Tensor) or not tri.is_cuda or tri.dtype != torch.float64 or not tri.is_contiguous() or tri.numel() % 9:
+            raise L.Ns3dError("tri must be a contiguous float64 CUDA/HIP tensor of 9 values per triangle")
+        if tri.device != mask.device:
+            raise L.Ns3dError("tri is on %s, the mask on %s" % (tri.device, mask.device))
+        n_tri = tri.numel() // 9
+        ptr = C.c_void_p(tri.data_ptr()) if n_tri else None
+    _untyped(ctx, mask, "ns3d_voxelize", _chk_mask(mask, (nx, ny, nz), mask), ptr, C.c_longlong(n_tri), nx, ny, nz, _int3(origin))
+
+
+def set_solid(Cf, Vx, Vy, Vz, mask, ctx=None):
+    """ns3d_set_solid: what set_cylinder! stores, with the flags read from `mask` (voxelize's bytes): C = 1, Vx = Vy = Vz = 0 where their
+    bits are set.  Cf may be None.  Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    _ctx(ctx, Vx).call("set_solid", Vx, None if Cf is None else _chk(Cf, (nx, ny, nz), "C"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)),
+                       _chk_mask(mask, (nx, ny, nz), Vx), nx, ny, nz)
+
+
+def solid_momentum(Vx, Vy, Vz, mask, seam_lo=None, seam_hi=None, ctx=None):
+    """ns3d_solid_momentum: (mom, n) — per direction the fp64 sum and the number of the owned nodes of Vx, Vy, Vz whose mask bit is set:
+    what the next set_solid removes (the monitor's mom / n_masked for a mask).  Blocks for the read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    mom, cnt = (C.c_double * 3)(), (C.c_longlong * 3)()
+    _ctx(ctx, Vx).call("solid_momentum", Vx, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), _chk_mask(mask, (nx, ny, nz), Vx), nx, ny, nz,
+                       _int3(seam_lo), _int3(seam_hi), mom, cnt)
+    return tuple(mom), tuple(int(q) for q in cnt)
 
 
 def update_divV(divV, Vx, Vy, Vz, dx, dy, dz, ctx=None):

@@ -112,13 +112,16 @@ DERIVED_SIGNATURES = {
     # the limited MacCormack advection, beside the reference's advect / copy_advect above
     "advect_correct": [_P] * 12 + [_D] * 4 + [_I] * 3,
     "advect_mc": [_P] * 12 + [_D] * 4 + [_I] * 3,
+    # obstacles from a mask (ns3d_voxelize writes one), beside set_cylinder / set_cylinder_local above
+    "set_solid": [_P] * 5 + [_I] * 3,
+    "solid_momentum": [_P] * 4 + [_I] * 3 + [C.POINTER(_I)] * 2 + [C.POINTER(_D), C.POINTER(C.c_longlong)],
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
                    "ns3d_set_pt2_variant", "ns3d_set_ptn_variant", "ns3d_set_pt_depth", "ns3d_set_graph_mode", "ns3d_set_autotune", "ns3d_last_pt2_variant", "ns3d_last_ptn_variant", "ns3d_last_pt_depth",
                    "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
                    "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test", "ns3d_set_advection", "ns3d_advection",
-                   "ns3d_stats_reset", "ns3d_stats_finalize"]
+                   "ns3d_stats_reset", "ns3d_stats_finalize", "ns3d_voxelize", "ns3d_set_obstacle", "ns3d_obstacle"]
 NS3D_STATS_SLOTS = 11
 
 
@@ -229,6 +232,12 @@ def load():
     lib.ns3d_set_advection.restype = _I
     lib.ns3d_advection.argtypes = [_P]
     lib.ns3d_advection.restype = _I
+    lib.ns3d_voxelize.argtypes = [_P, _P, _P, C.c_longlong] + [_I] * 3 + [C.POINTER(_I)]
+    lib.ns3d_voxelize.restype = _I
+    lib.ns3d_set_obstacle.argtypes = [_P, _P]
+    lib.ns3d_set_obstacle.restype = _I
+    lib.ns3d_obstacle.argtypes = [_P]
+    lib.ns3d_obstacle.restype = _P
     lib.ns3d_cached_graphs.argtypes = [_P]
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
