@@ -47,9 +47,9 @@
  *        ns3d_poisson_direct                    the stream, WHEN it builds or      no
  *                                               replaces its plan (a new grid)
  *        any call that grows a scratch buffer   the stream, before the old         as the call otherwise
- *        of the context (ping-pong, monitor,    buffer is freed
- *        isosurface, voxelizer) and
- *        ns3d_reserve_cus
+ *        of the context (ping-pong, advection   buffer is freed
+ *        hat, monitor, isosurface, voxelizer)
+ *        and ns3d_reserve_cus
  *        ns3d_set_stream, ns3d_use_own_stream,  the stream the context LEAVES       (none)
  *        ns3d_reserve_cus                       (when it differs from the new one)
  *    Everything else only enqueues.

@@ -106,30 +106,11 @@ ns3d_ctx *ns3d_create(int device, int flags)
     ns3d_ctx *c = new ns3d_ctx();
     c->device = device;
     c->flags = flags;
-    c->own_stream = nullptr;
-    c->stream = nullptr;
-    c->pingpong = nullptr;
-    c->pingpong_bytes = 0;
-    c->pingpong_d = nullptr;
-    c->pingpong_d_bytes = 0;
-    c->pt_variant = 0;
-    c->pt2_variant = 0; // temporal blocking on by default (ns3d_set_pt2_variant(ctx,-1) turns it off)
     if (const char *ev = std::getenv("NS3D_PT2_VARIANT")) c->pt2_variant = std::atoi(ev);   // experiments without an API call
-    c->ptn_variant = 0;
     if (const char *ev = std::getenv("NS3D_PTN_VARIANT")) c->ptn_variant = std::atoi(ev);
-    c->pt_depth = 0;
     if (const char *ev = std::getenv("NS3D_PT_DEPTH")) c->pt_depth = std::atoi(ev);
-    c->autotune = 1;
-    c->last_pt2 = 0;
-    c->last_ptn = 0;
-    c->last_depth = 0;
-    c->tune_ev[0] = c->tune_ev[1] = nullptr;
-    c->graph_mode = -1;
     if (const char *ev = std::getenv("NS3D_GRAPH_MODE")) c->graph_mode = std::atoi(ev);     // A/B without an API call
     if (const char *ev = std::getenv("NS3D_PT_PERSIST")) c->persist_mode = std::atoi(ev);
-    c->fence = nullptr;
-    c->key_dev = nullptr;
-    c->key_host = nullptr;
     if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipMalloc((void **)&c->key_dev, 64)) != hipSuccess ||
         (e = hipHostMalloc((void **)&c->key_host, 64, hipHostMallocDefault)) != hipSuccess ||
@@ -155,30 +136,24 @@ void ns3d_destroy(ns3d_ctx *c)
     if (c->pace.ctr) (void)hipFree(c->pace.ctr);
     if (c->persist.err_host) (void)hipHostFree(c->persist.err_host);
     if (c->persist.ev) (void)hipEventDestroy(c->persist.ev);
-    if (c->direct_plan && c->direct_free) c->direct_free(c->direct_plan);
+    c->direct.release();
     if (c->fence) (void)hipEventDestroy(c->fence);
     for (int q = 0; q < 2; ++q)
         if (c->tune_ev[q]) (void)hipEventDestroy(c->tune_ev[q]);
-    if (c->pingpong) (void)hipFree(c->pingpong);
-    if (c->pingpong_d) (void)hipFree(c->pingpong_d);
-    if (c->diag_dev) (void)hipFree(c->diag_dev);
     if (c->diag_host) (void)hipHostFree(c->diag_host);
-    if (c->iso_dev) (void)hipFree(c->iso_dev);
-    if (c->mc_hat) (void)hipFree(c->mc_hat);
-    if (c->solid_dev) (void)hipFree(c->solid_dev);
     if (c->key_dev) (void)hipFree(c->key_dev);
     if (c->key_host) (void)hipHostFree(c->key_host);
     if (c->masked_stream) { (void)hipStreamSynchronize(c->masked_stream); (void)hipStreamDestroy(c->masked_stream); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                               // the ns3d_scratch members go here: the device is current, the streams have been waited for
 }
 
 int ns3d_flags(const ns3d_ctx *c) { return c ? c->flags : -1; }
 
 // A context waits for the stream it leaves.  What it remembers is ordered by the stream it launches on and by nothing else: the
-// ping-pong, monitor and isosurface scratch (freed when it grows, after a wait for c->stream and c->own_stream only), the key word
-// of the residual read-backs, k_pt_persist's exchange area and the pace counters (reset by fills on the launch's stream).  Work
-// of an NS3D_ASYNC context still queued on a stream the context no longer names would meet all of these unordered.  A stream that
+// ping-pong, advection-hat, monitor, isosurface and voxelizer scratch (freed when it grows, after a wait for c->stream — and, for
+// the ping-pong and the hat, c->own_stream — only), the key word of the residual read-backs, k_pt_persist's exchange area and the
+// pace counters (reset by fills on the launch's stream).  Work of an NS3D_ASYNC context still queued on a stream the context no longer names would meet all of these unordered.  A stream that
 // is being captured runs nothing and is not waited for, and there is no wait either while the stream moved TO is being captured.
 static int leave_stream(ns3d_ctx *c, hipStream_t next)
 {
@@ -386,14 +361,11 @@ int ns3d_diag_enqueue(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const 
 {
     const size_t need = NS3D_DIAG_RESULT_WORDS + (size_t)NS3D_DIAG_SLOTS * ns3d_diag_geometry(p->nx, p->ny, p->nz, nullptr);
     if (!c->diag_host) HIPCHK(c, hipHostMalloc((void **)&c->diag_host, NS3D_DIAG_RESULT_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-    if (c->diag_words < need) {
-        if (c->diag_dev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->diag_dev); c->diag_dev = nullptr; c->diag_words = 0; }
-        HIPCHK(c, hipMalloc((void **)&c->diag_dev, need * sizeof(unsigned long long)));
-        c->diag_words = need;
-    }
-    hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, diagnostics<T>(c->stream, Vx, Vy, Vz, Pr, C, *p, c->diag_dev + NS3D_DIAG_RESULT_WORDS, c->diag_dev));
+    if (const int rc = c->diag_dev.reserve(need * sizeof(unsigned long long), ns3d_drain_stream(c))) return rc;
+    unsigned long long *words = c->diag_dev.as<unsigned long long>();
+    hipError_t e = DISPATCHG(c, p->dx, p->dy, p->dz, diagnostics<T>(c->stream, Vx, Vy, Vz, Pr, C, *p, words + NS3D_DIAG_RESULT_WORDS, words));
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "diagnostics launch: %s", hipGetErrorString(e)); }
-    HIPCHK(c, hipMemcpyAsync(c->diag_host, c->diag_dev, NS3D_DIAG_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->diag_host, words, NS3D_DIAG_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     return NS3D_OK;
 }
 template int ns3d_diag_enqueue<double>(ns3d_ctx *, const double *, const double *, const double *, const double *, const double *, const ns3d_diag_params *);
@@ -479,35 +451,29 @@ static bool use_two(const ns3d_ctx *c, const ns3d_pt_params *p)
     return (long long)p->nx * p->ny * p->nz >= NS3D_TWO_MIN_CELLS;
 }
 
-// a scratch buffer of the context, grown to `need` bytes; whatever may still use the old one (either stream, a captured block) goes first
-static int ensure_scratch(ns3d_ctx *c, void *&buf, size_t &bytes, size_t need)
+// The drain of the ping-pong and hat buffers: whatever may still use the old one — either stream, a captured block — goes first
+static auto drain_streams_and_graphs(ns3d_ctx *c)
 {
-    if (bytes >= need) return NS3D_OK;
-    if (buf) {
+    return [c]() -> int {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipStreamSynchronize(c->own_stream));
         c->clear_graphs();
-        HIPCHK(c, hipFree(buf));
-        buf = nullptr;
-        bytes = 0;
-    }
-    HIPCHK(c, hipMalloc(&buf, need));
-    bytes = need;
-    return NS3D_OK;
+        return NS3D_OK;
+    };
 }
-// its two uses: the second Pr buffer (every cell) and the second dPrdτ buffer (interior cells) of the PT loop
+// the second Pr buffer (every cell) and the second dPrdτ buffer (interior cells) of the PT loop
 template <class T>
 static int ensure_pingpong(ns3d_ctx *c, const ns3d_pt_params *p, T **buf)
 {
-    const int rc = ensure_scratch(c, c->pingpong, c->pingpong_bytes, (size_t)p->nx * p->ny * p->nz * sizeof(T));
-    if (!rc) *buf = (T *)c->pingpong;
+    const int rc = c->pingpong.reserve((size_t)p->nx * p->ny * p->nz * sizeof(T), drain_streams_and_graphs(c));
+    if (!rc) *buf = c->pingpong.as<T>();
     return rc;
 }
 template <class T>
 static int ensure_pingpong_d(ns3d_ctx *c, const ns3d_pt_params *p, T **buf)
 {
-    const int rc = ensure_scratch(c, c->pingpong_d, c->pingpong_d_bytes, (size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T));
-    if (!rc) *buf = (T *)c->pingpong_d;
+    const int rc = c->pingpong_d.reserve((size_t)(p->nx - 2) * (p->ny - 2) * (p->nz - 2) * sizeof(T), drain_streams_and_graphs(c));
+    if (!rc) *buf = c->pingpong_d.as<T>();
     return rc;
 }
 
@@ -516,9 +482,9 @@ template <class T>
 static int ensure_mc_hat(ns3d_ctx *c, int nx, int ny, int nz, T *hat[4])
 {
     const size_t n[4] = {(size_t)(nx + 1) * ny * nz, (size_t)nx * (ny + 1) * nz, (size_t)nx * ny * (nz + 1), (size_t)nx * ny * nz};
-    const int rc = ensure_scratch(c, c->mc_hat, c->mc_hat_bytes, (n[0] + n[1] + n[2] + n[3]) * sizeof(T));
+    const int rc = c->mc_hat.reserve((n[0] + n[1] + n[2] + n[3]) * sizeof(T), drain_streams_and_graphs(c));
     if (rc) return rc;
-    T *p = (T *)c->mc_hat;
+    T *p = c->mc_hat.as<T>();
     for (int q = 0; q < 4; ++q) { hat[q] = p; p += n[q]; }
     return NS3D_OK;
 }
@@ -1159,27 +1125,15 @@ static int iso_prepare(ns3d_ctx *c, int ex, int ey, int ez, const int *box, cons
     w->nsegs = (unsigned long long)g->nseg * g->cy * g->cz;
     w->nblk = (unsigned)((w->nsegs + NS3D_ISO_SCAN_BLOCK - 1) / NS3D_ISO_SCAN_BLOCK);
     const size_t need = 8 * (size_t)(1 + w->nblk + w->nsegs) + 4 * (size_t)w->nsegs;
-    if (c->iso_bytes < need) {
-        if (c->iso_dev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->iso_dev); c->iso_dev = nullptr; c->iso_bytes = 0; }
-        HIPCHK(c, hipMalloc(&c->iso_dev, need));
-        c->iso_bytes = need;
-    }
-    w->total = (unsigned long long *)c->iso_dev;
+    if (const int rc = c->iso_dev.reserve(need, ns3d_drain_stream(c))) return rc;
+    w->total = c->iso_dev.as<unsigned long long>();
     w->bsum = w->total + 1;
     w->segbase = w->bsum + w->nblk;
     w->segcnt = (unsigned *)(w->segbase + w->nsegs);
     return NS3D_OK;
 }
 // ---- ns3d_voxelize / ns3d_set_solid / ns3d_solid_momentum (ns3d_solid.hip) ----------------------------------------------------------
-// the scratch both share: grown lazily, after a wait for the stream (the header's table)
-static int ensure_solid(ns3d_ctx *c, size_t need)
-{
-    if (c->solid_bytes >= need) return NS3D_OK;
-    if (c->solid_dev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->solid_dev); c->solid_dev = nullptr; c->solid_bytes = 0; }
-    HIPCHK(c, hipMalloc(&c->solid_dev, need));
-    c->solid_bytes = need;
-    return NS3D_OK;
-}
+// voxelize and solid_momentum share c->solid_dev: grown lazily, after a wait for the stream (the header's table)
 extern "C" int ns3d_voxelize(ns3d_ctx *c, unsigned char *mask, const double *tri, long long n_tri, int nx, int ny, int nz, const int *origin)
 {
     CHECK_CTX(c);
@@ -1191,9 +1145,9 @@ extern "C" int ns3d_voxelize(ns3d_ctx *c, unsigned char *mask, const double *tri
     const int zero[3] = {0, 0, 0};
     const int *o = origin ? origin : zero;
     if (o[0] < 0 || o[1] < 0 || o[2] < 0) return fail(NS3D_ERR_ARG, "%s: origin %d, %d, %d (each >= 0)", __func__, o[0], o[1], o[2]);
-    const int rc = ensure_solid(c, ns3d_solid::voxelize_scratch_bytes(nx, ny, nz));
+    const int rc = c->solid_dev.reserve(ns3d_solid::voxelize_scratch_bytes(nx, ny, nz), ns3d_drain_stream(c));
     if (rc) return rc;
-    return finish(c, ns3d_solid::voxelize(c->stream, mask, tri, n_tri, nx, ny, nz, o, c->solid_dev), "voxelize");
+    return finish(c, ns3d_solid::voxelize(c->stream, mask, tri, n_tri, nx, ny, nz, o, c->solid_dev.ptr), "voxelize");
 }
 extern "C" int ns3d_poisson_direct_f64(ns3d_ctx *, double *, double *, const double *, const ns3d_pt_params *);      // ns3d_direct.hip
 extern "C" int ns3d_poisson_direct_f32(ns3d_ctx *, float *, float *, const float *, const ns3d_pt_params *);

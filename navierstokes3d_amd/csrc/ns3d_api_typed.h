@@ -54,10 +54,10 @@ extern "C" int NS3D_FN(solid_momentum)(ns3d_ctx *c, const T *Vx, const T *Vy, co
 {
     CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, mask, mom_host, n_host); CHECK_GRID(nx, ny, nz, 3);
     const int zero[3] = {0, 0, 0};
-    const int rc = ensure_solid(c, ns3d_solid::momentum_scratch_bytes(nx, ny, nz));
+    const int rc = c->solid_dev.reserve(ns3d_solid::momentum_scratch_bytes(nx, ny, nz), ns3d_drain_stream(c));
     if (rc) return rc;
     hipError_t e = ns3d_solid::momentum<T>(c->stream, Vx, Vy, Vz, mask, nx, ny, nz, seam_lo ? seam_lo : zero, seam_hi ? seam_hi : zero,
-                                           c->solid_dev, c->key_dev);
+                                           c->solid_dev.ptr, c->key_dev);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "solid_momentum launch: %s", hipGetErrorString(e)); }
     HIPCHK(c, hipMemcpyAsync(c->key_host, c->key_dev, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -345,46 +345,23 @@ void eig1d_cached(int m, double d, int kind, std::vector<double> &V, std::vector
     V = hit->V; lam = hit->lam;
 }
 
-struct DirectPlan {
-    int nx = 0, ny = 0, nz = 0, xkind = -1;
-    double dx = 0, dy = 0, dz = 0;
-    double *V[3] = {nullptr, nullptr, nullptr}, *lam[3] = {nullptr, nullptr, nullptr};
-    double *W[2] = {nullptr, nullptr};
-    void release()
-    {
-        for (int d = 0; d < 3; ++d) { if (V[d]) (void)hipFree(V[d]); if (lam[d]) (void)hipFree(lam[d]); V[d] = lam[d] = nullptr; }
-        for (int q = 0; q < 2; ++q) { if (W[q]) (void)hipFree(W[q]); W[q] = nullptr; }
-        nx = ny = nz = 0; xkind = -1;
-    }
-};
-
-void free_plan(void *p)
+// the context's plan (ns3d_internal.h: ns3d_direct_plan) for this grid, boundary kind and spacings: replaced whole when any differs
+int ensure_plan(ns3d_ctx *c, const ns3d_pt_params *p, int xkind)
 {
-    DirectPlan *pl = (DirectPlan *)p;
-    if (!pl) return;
-    pl->release();
-    delete pl;
-}
-
-int ensure_plan(ns3d_ctx *c, const ns3d_pt_params *p, int xkind, DirectPlan **out)
-{
-    DirectPlan *pl = (DirectPlan *)c->direct_plan;
-    if (!pl) { pl = new DirectPlan(); c->direct_plan = pl; c->direct_free = free_plan; }
-    *out = pl;
-    if (pl->nx == p->nx && pl->ny == p->ny && pl->nz == p->nz && pl->xkind == xkind && pl->dx == p->dx && pl->dy == p->dy && pl->dz == p->dz)
-        return NS3D_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ns3d_direct_plan *pl = &c->direct;
+    if (pl->matches(p, xkind)) return NS3D_OK;
+    int rc = ns3d_drain_stream(c)();        // also ahead of the first plan: the header's table promises the wait for every new grid
+    if (rc) return rc;
     pl->release();
     const int m[3] = {p->nx - 2, p->ny - 2, p->nz - 2};
     const double d[3] = {p->dx, p->dy, p->dz};
     const int kind[3] = {xkind, 0, 0};
-    for (int q = 0; q < 3; ++q) {
-        int rc = ns3d_direct_basis(m[q], d[q], kind[q], &pl->V[q], &pl->lam[q]);
-        if (rc) return rc;
-    }
+    for (int q = 0; q < 3; ++q)
+        if ((rc = ns3d_direct_basis(m[q], d[q], kind[q], &pl->V[q], &pl->lam[q]))) return rc;
     const size_t cells = (size_t)m[0] * m[1] * m[2];
-    for (int q = 0; q < 2; ++q) HIPCHK(c, hipMalloc((void **)&pl->W[q], cells * sizeof(double)));
-    pl->nx = p->nx; pl->ny = p->ny; pl->nz = p->nz; pl->xkind = xkind; pl->dx = p->dx; pl->dy = p->dy; pl->dz = p->dz;
+    for (ns3d_scratch &w : pl->W)           // empty since the release above: nothing left to drain
+        if ((rc = w.reserve(cells * sizeof(double), ns3d_drain_stream(c)))) return rc;
+    pl->set_key(p, xkind);
     return NS3D_OK;
 }
 
@@ -411,11 +388,11 @@ int poisson_direct(ns3d_ctx *c, T *Pr, T *D, const T *divV, const ns3d_pt_params
         return fail(NS3D_ERR_ARG, "ns3d_poisson_direct: single-rank grids only (a z-slab rank's planes are not a closed problem)");
     if (p->nx < 4 || p->ny < 4 || p->nz < 4) return fail(NS3D_ERR_ARG, "ns3d_poisson_direct: grid %dx%dx%d too small", p->nx, p->ny, p->nz);
     const int xkind = ns3d_direct_xkind(p);
-    DirectPlan *pl = nullptr;
-    if ((rc = ensure_plan(c, p, xkind, &pl))) return rc;
+    if ((rc = ensure_plan(c, p, xkind))) return rc;
+    const ns3d_direct_plan *pl = &c->direct;
     hipStream_t s = c->stream;
     const int mx = p->nx - 2, my = p->ny - 2, mz = p->nz - 2;
-    double *W0 = pl->W[0], *W1 = pl->W[1];
+    double *W0 = pl->W[0].as<double>(), *W1 = pl->W[1].as<double>();
     hipError_t e = ns3d_direct_rhs_x<T>(s, divV, p, pl->V[0], W0, W1);
     if (e == hipSuccess) e = ns3d_direct_fwd_y(s, W1, pl->V[1], W0, mx, my, mz, 0, my);
     if (e == hipSuccess) e = ns3d_direct_z(s, W0, W1, pl->V[2], pl->lam[0], pl->lam[1], pl->lam[2], mx, my, mz);

@@ -5,36 +5,59 @@
 #include <vector>
 
 #include "ns3d_launch.h"
+#include "ns3d_scratch.h"
 
-// records the message behind ns3d_last_error() and returns `code`
-int ns3d_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// ns3d_fail (declared in ns3d_scratch.h) records the message behind ns3d_last_error() and returns `code`
 #define fail ns3d_fail
 
+// What a direct Poisson solve keeps while its key — grid, x boundary kind, spacings — stays the same: the three eigenbases with their
+// eigenvalues (x, y, z).  ns3d_direct_basis allocates V and lam and hands them to the caller, so release() frees them, explicitly:
+// the struct is plain data.  ns3d_direct.hip adds one rank's work buffers (below), ns3d_mgpu.cpp a z-slab rank's (DirectSlab).
+struct ns3d_direct_bases {
+    int nx = 0, ny = 0, nz = 0, xkind = -1;
+    double dx = 0, dy = 0, dz = 0;
+    double *V[3] = {nullptr, nullptr, nullptr}, *lam[3] = {nullptr, nullptr, nullptr};
+    bool matches(const ns3d_pt_params *p, int kind) const
+    {
+        return nx == p->nx && ny == p->ny && nz == p->nz && xkind == kind && dx == p->dx && dy == p->dy && dz == p->dz;
+    }
+    void set_key(const ns3d_pt_params *p, int kind) { nx = p->nx; ny = p->ny; nz = p->nz; xkind = kind; dx = p->dx; dy = p->dy; dz = p->dz; }
+    void release()
+    {
+        for (int q = 0; q < 3; ++q) { if (V[q]) (void)hipFree(V[q]); if (lam[q]) (void)hipFree(lam[q]); V[q] = lam[q] = nullptr; }
+        nx = ny = nz = 0; xkind = -1;
+    }
+};
+struct ns3d_direct_plan : ns3d_direct_bases {      // ns3d_poisson_direct: the bases and two work arrays of the interior cells
+    ns3d_scratch W[2];
+    void release() { ns3d_direct_bases::release(); for (ns3d_scratch &w : W) w.release(); }
+};
+
 struct ns3d_ctx {
-    int device;
-    int flags;
-    hipStream_t own_stream;
+    int device = 0;
+    int flags = 0;
+    hipStream_t own_stream = nullptr;
     hipStream_t masked_stream = nullptr;  // ns3d_reserve_cus: a stream whose CU mask leaves `reserved_cus` compute units out
     int reserved_cus = 0;
-    hipStream_t stream;
-    unsigned long long *key_dev;  // device scratch for max reductions
-    unsigned long long *key_host; // pinned host mirror
-    void *pingpong;               // second Pr buffer of the fused PT path (lazily sized)
-    size_t pingpong_bytes;
-    void *pingpong_d;             // second dPrdτ buffer (temporal blocking only)
-    size_t pingpong_d_bytes;
-    int pt_variant;
-    int pt2_variant; // tile shape of the two-iteration sweep; <0: temporal blocking off
-    int ptn_variant; // tile shape of the N-iteration sweep (k_pt_sweepN); 0: built-in
-    int pt_depth;    // PT iterations per pass in pt_iterate / pt_solve: 0 automatic, 1…4 forced
-    int graph_mode;  // HIP-graph replay of residual-check blocks: -1 auto (launch-bound grids), 0 off, 1 on
+    hipStream_t stream = nullptr;
+    unsigned long long *key_dev = nullptr;  // device scratch for max reductions
+    unsigned long long *key_host = nullptr; // pinned host mirror
+    // Scratch grown lazily (ns3d_scratch: freed with the context).  What is waited for before an old buffer goes is the site's choice:
+    // ns3d_drain_stream below, or both streams and the captured blocks for what the PT loop and the step use (ns3d_api.cpp).
+    ns3d_scratch pingpong;        // second Pr buffer of the fused PT path
+    ns3d_scratch pingpong_d;      // second dPrdτ buffer (temporal blocking only)
+    int pt_variant = 0;
+    int pt2_variant = 0; // tile shape of the two-iteration sweep; <0: temporal blocking off (on by default: ns3d_set_pt2_variant(ctx,-1) turns it off)
+    int ptn_variant = 0; // tile shape of the N-iteration sweep (k_pt_sweepN); 0: built-in
+    int pt_depth = 0;    // PT iterations per pass in pt_iterate / pt_solve: 0 automatic, 1…4 forced
+    int graph_mode = -1; // HIP-graph replay of residual-check blocks: -1 auto (launch-bound grids), 0 off, 1 on
     int persist_mode = -1; // k_pt_persist (a whole residual-check block in one cooperative launch): -1 auto (small grids), 0 off, 1 on
-    int autotune;    // time the tile shapes of the two-iteration sweep on first use of a grid (pt2_variant == 0 only)
-    int last_pt2;    // variant of the latest two-iteration launch (0: built-in choice by grid)
-    int last_ptn;    // variant of the latest N-iteration launch
-    int last_depth;  // PT iterations of the latest multi-iteration pass
-    hipEvent_t tune_ev[2];
-    hipEvent_t fence;
+    int autotune = 1;    // time the tile shapes of the two-iteration sweep on first use of a grid (pt2_variant == 0 only)
+    int last_pt2 = 0;    // variant of the latest two-iteration launch (0: built-in choice by grid)
+    int last_ptn = 0;    // variant of the latest N-iteration launch
+    int last_depth = 0;  // PT iterations of the latest multi-iteration pass
+    hipEvent_t tune_ev[2] = {nullptr, nullptr};
+    hipEvent_t fence = nullptr;
     struct BlockGraph {
         struct Bufs { void *src, *dst, *dsrc, *ddst; } in, out;   // PtBufs<T> (ns3d_api.cpp) the block was captured on / leaves behind
         const void *rhs;
@@ -46,18 +69,13 @@ struct ns3d_ctx {
     std::vector<BlockGraph> graphs;
     ns3d_persist_state persist;             // k_pt_persist's exchange area
     ns3d_pt_pace pace;                      // k_pt_sweepN's PACE instance (shape 29): arrival counters, launch number, settings
-    unsigned long long *diag_dev = nullptr;  // ns3d_diagnostics: NS3D_DIAG_RESULT_WORDS result / staging words, then the workgroups' partials
-    size_t diag_words = 0;
+    ns3d_scratch diag_dev;                  // ns3d_diagnostics: NS3D_DIAG_RESULT_WORDS result / staging words, then the workgroups' partials
     unsigned long long *diag_host = nullptr; // pinned mirror of the result / staging words
-    void *direct_plan = nullptr;            // ns3d_direct.hip: eigenvector matrices and scratch of the direct Poisson solve
-    void (*direct_free)(void *) = nullptr;
-    void *iso_dev = nullptr;                // ns3d_isosurface: segment counts, their scan and the total (grown lazily)
-    size_t iso_bytes = 0;
+    ns3d_direct_plan direct;                // ns3d_direct.hip: eigenvector matrices and scratch of the direct Poisson solve
+    ns3d_scratch iso_dev;                   // ns3d_isosurface: segment counts, their scan and the total
     int advection = 0;                      // ns3d_set_advection: what ns3d_time_step advects with (NS3D_ADVECT_*)
-    void *mc_hat = nullptr;                 // ns3d_time_step under NS3D_ADVECT_MACCORMACK: stage 1's four complete fields (grown lazily)
-    size_t mc_hat_bytes = 0;
-    void *solid_dev = nullptr;              // ns3d_voxelize's bit planes / ns3d_solid_momentum's partials (grown lazily; one stream orders both)
-    size_t solid_bytes = 0;
+    ns3d_scratch mc_hat;                    // ns3d_time_step under NS3D_ADVECT_MACCORMACK: stage 1's four complete fields
+    ns3d_scratch solid_dev;                 // ns3d_voxelize's bit planes / ns3d_solid_momentum's partials (one stream orders both)
     const unsigned char *obstacle = nullptr; // ns3d_set_obstacle: the caller's mask ns3d_time_step masks with; null: the cylinder
     void clear_graphs()
     {
@@ -96,7 +114,14 @@ struct ns3d_device_guard {
         }                                                                                                   \
     } while (0)
 
-#define CHECK_CTX(ctx)                                                                                      \
+// The drain (ns3d_scratch::reserve) of what only launches on c->stream ever touch — monitor, isosurface and voxelizer scratch, the
+// direct solve's plan: a wait for that stream.  Captured blocks never hold these pointers, so the graphs stay.
+inline auto ns3d_drain_stream(ns3d_ctx *c)
+{
+    return [c]() -> int { HIPCHK(c, hipStreamSynchronize(c->stream)); return NS3D_OK; };
+}
+
+#define CHECK_CTX(ctx)                                                                                    \
     if (!(ctx)) return fail(NS3D_ERR_ARG, "%s: null context", __func__);                                    \
     ns3d_device_guard dev_guard_((ctx)->device);                                                            \
     if (dev_guard_.err != hipSuccess) return fail(NS3D_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(dev_guard_.err))

@@ -39,6 +39,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <utility>
 
 #include <rccl/rccl.h>   // types and prototypes only; every symbol is resolved by dlopen below
 
@@ -99,23 +100,29 @@ static_assert(sizeof(ncclUniqueId) == NS3D_UNIQUE_ID_BYTES, "NS3D_UNIQUE_ID_BYTE
 // ---- one z-slab rank driven by this process ----------------------------------------------------------------------
 struct SlabState {                // deep-ghost pseudo-transient state (library-owned)
     void *P[2] = {nullptr, nullptr}, *D[2] = {nullptr, nullptr}, *R = nullptr;      // working bases (plane 0 of the CURRENT ghost depth)
-    void *Pa[2] = {nullptr, nullptr}, *Da[2] = {nullptr, nullptr}, *Ra = nullptr;   // the allocations (ghost depth at load)
-    size_t bytes_P = 0, bytes_D = 0;
+    ns3d_scratch Pa[2], Da[2], Ra;                                                  // the allocations (ghost depth at load)
+    size_t bytes_P = 0, bytes_D = 0;                                                // their sizes once all five stand zero-filled
     int ip = 0, id = 0;           // current Pr / dPrdτ buffer
 };
-struct DirectSlab {               // ns3d_poisson_direct_slab: what a rank keeps while (grid, P, spacings, x rule) stay the same
-    int nx = 0, ny = 0, nz = 0, P = 0, xkind = -1;
-    double dx = 0, dy = 0, dz = 0;
-    double *V[3] = {nullptr, nullptr, nullptr}, *lam[3] = {nullptr, nullptr, nullptr};   // x, y (local extents) and z (all mz_g planes)
-    double *L[2] = {nullptr, nullptr};    // the rank's planes: mx·my·mz each (plane-major or chunk-major)
-    double *Z[2] = {nullptr, nullptr};    // the rank's y chunk over every global plane: mx·nky·mz_g each
+struct DirectSlab : ns3d_direct_bases {   // ns3d_poisson_direct_slab: what a rank keeps while (grid, P, spacings, x rule) stay the same;
+    int P = 0;                    // the bases: x, y (local extents) and z (all mz_g planes)
+    ns3d_scratch L[2];            // the rank's planes: mx·my·mz each (plane-major or chunk-major)
+    ns3d_scratch Z[2];            // the rank's y chunk over every global plane: mx·nky·mz_g each
+    double *l(int q) const { return L[q].as<double>(); }
+    double *z(int q) const { return Z[q].as<double>(); }
+    void release()
+    {
+        ns3d_direct_bases::release();
+        for (int q = 0; q < 2; ++q) { L[q].release(); Z[q].release(); }
+        P = 0;
+    }
 };
 struct MRank {
     int rank = 0, device = 0;
     int coords[3] = {0, 0, 0};                     // Cartesian coordinates (MPI_Cart_coords order: last dimension fastest)
     int nbr[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}}; // neighbour ranks per dimension (lower, upper), −1 at a physical end
-    void *hbuf = nullptr;                          // update_halo!: packed x / y faces (send lo, send hi, recv lo, recv hi per field)
-    size_t hbuf_bytes = 0;
+    // Device buffers grown lazily (ns3d_scratch: freed with the rank); each site passes the drain its old buffer needs (below)
+    ns3d_scratch hbuf;                             // update_halo!: packed x / y faces (send lo, send hi, recv lo, recv hi per field)
     ns3d_ctx *ctx = nullptr;
     hipStream_t comm = nullptr;                    // halo traffic (high priority)
     hipEvent_t ev_ready = nullptr, ev_landed = nullptr;
@@ -123,19 +130,13 @@ struct MRank {
     int plan_v2 = -1, plan_vn = -1;                // tile shapes deep_plan measured for this rank's interior sweeps
     int plan_lo = 0, plan_hi = 0;                  // … and the plane range they were measured on (sub-ranges of it use them too)
     SlabState st;
-    void *cbuf = nullptr;                          // solve_cart: the second pressure buffer
-    size_t cbuf_bytes = 0;
-    void *bbuf = nullptr;                          // box_exchange: packed x / y ghost layers (send lo, send hi, recv lo, recv hi per array)
-    size_t bbuf_bytes = 0;
-    void *gbuf = nullptr;                          // gather!: packed halo-stripped block
-    size_t gbuf_bytes = 0;
-    void *wbuf = nullptr;                          // advect_wide: the four old and four new fields, one plane wider per seam
-    size_t wbuf_bytes = 0;
+    ns3d_scratch cbuf;                             // solve_cart: the second pressure buffer
+    ns3d_scratch bbuf;                             // box_exchange: packed x / y ghost layers (send lo, send hi, recv lo, recv hi per array)
+    ns3d_scratch gbuf;                             // gather!: packed halo-stripped block
+    ns3d_scratch wbuf;                             // advect_wide: the four old and four new fields, one plane wider per seam
     DirectSlab ds;                                 // ns3d_poisson_direct_slab: eigenbases and transposed scratch
-    void *tbuf = nullptr;                          // ns3d_tracers_migrate_mgpu: per-slot codes, per-workgroup counts and offsets, totals
-    size_t tbuf_bytes = 0;
-    void *tsend = nullptr, *trecv = nullptr;       // … the leavers' records by destination, the arrivals' by source
-    size_t tsend_bytes = 0, trecv_bytes = 0;
+    ns3d_scratch tbuf;                             // ns3d_tracers_migrate_mgpu: per-slot codes, per-workgroup counts and offsets, totals
+    ns3d_scratch tsend, trecv;                     // … the leavers' records by destination, the arrivals' by source
     unsigned long long *thost = nullptr;           // … pinned: P+1 totals read back, then P send-buffer bases uploaded
 };
 struct Block {                    // one contiguous piece that travels to both neighbours (pointers on the owning rank)
@@ -161,8 +162,7 @@ struct ns3d_mgpu {
     bool loaded = false;
     int esize = 0, G = 0;
     ns3d_pt_params p;             // the caller's (local grid)
-    void *stage = nullptr;        // rank 0, RCCL gather: the global halo-stripped array on the device
-    size_t stage_bytes = 0;
+    ns3d_scratch stage;           // rank 0, RCCL gather: the global halo-stripped array on the device
 };
 
 namespace {
@@ -310,30 +310,32 @@ int finish_m(ns3d_mgpu *m)
     return (m->flags & NS3D_ASYNC) ? NS3D_OK : sync_all(m);
 }
 
+// What is waited for before a rank's scratch is freed (ns3d_scratch::reserve), by who may still use the old buffer: the rank's own
+// compute stream; its compute and communication streams; every stream of the grid (a neighbour pulls from message and state buffers)
+auto drain_compute(MRank &r)
+{
+    return [&r]() -> int { HIPCHK(0, hipStreamSynchronize(compute(r))); return NS3D_OK; };
+}
+auto drain_rank(MRank &r)
+{
+    return [&r]() -> int { HIPCHK(0, hipStreamSynchronize(compute(r))); HIPCHK(0, hipStreamSynchronize(r.comm)); return NS3D_OK; };
+}
+auto drain_grid(ns3d_mgpu *m)
+{
+    return [m] { return sync_all(m); };
+}
+
 void free_slab(MRank &r)
 {
     ns3d_device_guard g(r.device);
     for (int q = 0; q < 2; ++q) {
-        if (r.st.Pa[q]) (void)hipFree(r.st.Pa[q]);
-        if (r.st.Da[q]) (void)hipFree(r.st.Da[q]);
-        r.st.P[q] = r.st.D[q] = r.st.Pa[q] = r.st.Da[q] = nullptr;
+        r.st.Pa[q].release();
+        r.st.Da[q].release();
+        r.st.P[q] = r.st.D[q] = nullptr;
     }
-    if (r.st.Ra) (void)hipFree(r.st.Ra);
-    r.st.R = r.st.Ra = nullptr;
+    r.st.Ra.release();
+    r.st.R = nullptr;
     r.st.bytes_P = r.st.bytes_D = 0;
-}
-
-void free_direct(MRank &r)
-{
-    ns3d_device_guard g(r.device);
-    DirectSlab &d = r.ds;
-    for (int q = 0; q < 3; ++q) { if (d.V[q]) (void)hipFree(d.V[q]); if (d.lam[q]) (void)hipFree(d.lam[q]); d.V[q] = d.lam[q] = nullptr; }
-    for (int q = 0; q < 2; ++q) {
-        if (d.L[q]) (void)hipFree(d.L[q]);
-        if (d.Z[q]) (void)hipFree(d.Z[q]);
-        d.L[q] = d.Z[q] = nullptr;
-    }
-    d.nx = d.ny = d.nz = d.P = 0; d.xkind = -1;
 }
 
 int init_rank(ns3d_mgpu *m, MRank &r, int rank, int device, int flags)
@@ -473,19 +475,11 @@ int update_halo_core(ns3d_mgpu *m, T *const *fields, const int *extents, int nfi
             need += 4 * (size_t)(d == 0 ? e[1] : e[0]) * e[2] * sizeof(T);
         }
     }
-    for (int l = 0; l < n && need; ++l) {
+    for (int l = 0; l < n; ++l) {
         MRank &r = m->loc[l];
-        if (r.hbuf_bytes >= need) continue;
+        if (r.hbuf.bytes >= need) continue;         // every call but the first of a size: no device switch
         ns3d_device_guard g(r.device);
-        if (r.hbuf) {
-            // a neighbour may still be pulling from the old buffer: drain every stream of this grid first
-            int rc = sync_all(m);
-            if (rc) return rc;
-            HIPCHK(0, hipFree(r.hbuf));
-            r.hbuf = nullptr; r.hbuf_bytes = 0;
-        }
-        HIPCHK(0, hipMalloc(&r.hbuf, need));
-        r.hbuf_bytes = need;
+        if (const int rc = r.hbuf.reserve(need, drain_grid(m))) return rc;     // a neighbour may still be pulling from the old buffer
     }
     for (int d = 0; d < 3; ++d) {
         if (m->dims[d] == 1) continue;
@@ -513,7 +507,7 @@ int update_halo_core(ns3d_mgpu *m, T *const *fields, const int *extents, int nfi
                     continue;
                 }
                 const size_t face = (size_t)(d == 0 ? sy : sx) * sz;
-                T *b0 = (T *)((char *)r.hbuf + off);
+                T *b0 = (T *)(r.hbuf.as<char>() + off);
                 off += 4 * face * sizeof(T);
                 blocks[l].push_back({b0, b0 + 2 * face, b0 + face, b0 + 3 * face, face * sizeof(T)});
                 hipError_t e1 = hipSuccess, e2 = hipSuccess;
@@ -560,13 +554,11 @@ int update_halo_impl(ns3d_mgpu *m, T *const *fields, const int *extents, int nfi
 int ensure_direct(ns3d_mgpu *m, MRank &r, const ns3d_pt_params *p, int xkind)
 {
     DirectSlab &d = r.ds;
-    if (d.nx == p->nx && d.ny == p->ny && d.nz == p->nz && d.P == m->P && d.xkind == xkind && d.dx == p->dx && d.dy == p->dy &&
-        d.dz == p->dz)
-        return NS3D_OK;
+    if (d.matches(p, xkind) && d.P == m->P) return NS3D_OK;
     int rc = sync_all(m);                 // a peer may still be pulling from the old buffers
     if (rc) return rc;
-    free_direct(r);
     ns3d_device_guard g(r.device);
+    d.release();
     const int mx = p->nx - 2, my = p->ny - 2, mz = p->nz - 2, mzg = m->P * mz;
     int ky0, nky;
     ns3d_direct_ychunk(my, m->P, 0, &ky0, &nky);      // chunk 0 is a widest one
@@ -575,11 +567,11 @@ int ensure_direct(ns3d_mgpu *m, MRank &r, const ns3d_pt_params *p, int xkind)
     const int k3[3] = {xkind, 0, 0};
     for (int q = 0; q < 3; ++q)
         if ((rc = ns3d_direct_basis(m3[q], d3[q], k3[q], &d.V[q], &d.lam[q]))) return rc;
-    for (int q = 0; q < 2; ++q) {
-        HIPCHK(0, hipMalloc((void **)&d.L[q], (size_t)mx * my * mz * sizeof(double)));
-        HIPCHK(0, hipMalloc((void **)&d.Z[q], (size_t)mx * nky * mzg * sizeof(double)));
+    for (int q = 0; q < 2; ++q) {        // empty since the release above: nothing left to drain
+        if ((rc = d.L[q].reserve((size_t)mx * my * mz * sizeof(double), drain_grid(m)))) return rc;
+        if ((rc = d.Z[q].reserve((size_t)mx * nky * mzg * sizeof(double), drain_grid(m)))) return rc;
     }
-    d.nx = p->nx; d.ny = p->ny; d.nz = p->nz; d.P = m->P; d.xkind = xkind; d.dx = p->dx; d.dy = p->dy; d.dz = p->dz;
+    d.set_key(p, xkind); d.P = m->P;
     return NS3D_OK;
 }
 
@@ -618,9 +610,9 @@ int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, c
         ns3d_device_guard g(r.device);
         DirectSlab &d = r.ds;
         hipStream_t s = compute(r);
-        if ((rc = launch(ns3d_direct_rhs_x<T>(s, divV[l], p, d.V[0], d.L[0], d.L[1]), "rhs / x"))) return rc;
+        if ((rc = launch(ns3d_direct_rhs_x<T>(s, divV[l], p, d.V[0], d.l(0), d.l(1)), "rhs / x"))) return rc;
         for (int c = 0; c < P; ++c)
-            if (nky[c] && (rc = launch(ns3d_direct_fwd_y(s, d.L[1], d.V[1], d.L[0] + (size_t)mx * mz * ky0[c], mx, my, mz, ky0[c], nky[c]), "y")))
+            if (nky[c] && (rc = launch(ns3d_direct_fwd_y(s, d.l(1), d.V[1], d.l(0) + (size_t)mx * mz * ky0[c], mx, my, mz, ky0[c], nky[c]), "y")))
                 return rc;
     }
     // (2) transpose: rank c receives chunk c of every rank's planes, in rank order = [global plane][column]
@@ -629,8 +621,8 @@ int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, c
         DirectSlab &d = m->loc[l].ds;
         const int me = m->loc[l].rank;
         for (int c = 0; c < P; ++c) {
-            snd[l][c] = {d.L[0] + (size_t)mx * mz * ky0[c], (size_t)mx * mz * nky[c] * sizeof(double)};
-            rcv[l][c] = {d.Z[0] + (size_t)c * mz * mx * nky[me], (size_t)mx * mz * nky[me] * sizeof(double)};
+            snd[l][c] = {d.l(0) + (size_t)mx * mz * ky0[c], (size_t)mx * mz * nky[c] * sizeof(double)};
+            rcv[l][c] = {d.z(0) + (size_t)c * mz * mx * nky[me], (size_t)mx * mz * nky[me] * sizeof(double)};
         }
     }
     if ((rc = alltoall(m, snd, rcv))) return rc;
@@ -639,7 +631,7 @@ int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, c
         ns3d_device_guard g(r.device);
         DirectSlab &d = r.ds;
         const int me = r.rank;
-        if (nky[me] && (rc = launch(ns3d_direct_z(compute(r), d.Z[0], d.Z[1], d.V[2], d.lam[0], d.lam[1] + ky0[me], d.lam[2], mx, nky[me], mzg), "z")))
+        if (nky[me] && (rc = launch(ns3d_direct_z(compute(r), d.z(0), d.z(1), d.V[2], d.lam[0], d.lam[1] + ky0[me], d.lam[2], mx, nky[me], mzg), "z")))
             return rc;
     }
     // (4) back: rank r gets its planes of every chunk, chunk-major again
@@ -647,8 +639,8 @@ int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, c
         DirectSlab &d = m->loc[l].ds;
         const int me = m->loc[l].rank;
         for (int c = 0; c < P; ++c) {
-            snd[l][c] = {d.Z[0] + (size_t)c * mz * mx * nky[me], (size_t)mx * mz * nky[me] * sizeof(double)};
-            rcv[l][c] = {d.L[1] + (size_t)mx * mz * ky0[c], (size_t)mx * mz * nky[c] * sizeof(double)};
+            snd[l][c] = {d.z(0) + (size_t)c * mz * mx * nky[me], (size_t)mx * mz * nky[me] * sizeof(double)};
+            rcv[l][c] = {d.l(1) + (size_t)mx * mz * ky0[c], (size_t)mx * mz * nky[c] * sizeof(double)};
         }
     }
     if ((rc = alltoall(m, snd, rcv))) return rc;
@@ -658,8 +650,8 @@ int direct_slab(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, c
         ns3d_device_guard g(r.device);
         DirectSlab &d = r.ds;
         hipStream_t s = compute(r);
-        if ((rc = launch(ns3d_direct_unpack(s, d.L[1], d.L[0], mx, my, mz, P), "unpack"))) return rc;
-        if ((rc = launch(ns3d_direct_inv_yx<T>(s, d.L[0], d.L[1], d.V[0], d.V[1], Pr[l], D[l], p->nx, p->ny, p->nz), "y / x backward")))
+        if ((rc = launch(ns3d_direct_unpack(s, d.l(1), d.l(0), mx, my, mz, P), "unpack"))) return rc;
+        if ((rc = launch(ns3d_direct_inv_yx<T>(s, d.l(0), d.l(1), d.V[0], d.V[1], Pr[l], D[l], p->nx, p->ny, p->nz), "y / x backward")))
             return rc;
         const int flags = r.ctx->flags;
         r.ctx->flags |= NS3D_ASYNC;       // enqueue only: the call as a whole blocks (or not) at its end
@@ -700,14 +692,8 @@ int solve_cart(ns3d_mgpu *m, T *const *Pr, T *const *D, const T *const *divV, co
         MRank &r = m->loc[l];
         if (!Pr[l] || !D[l] || !divV[l]) return fail(NS3D_ERR_ARG, "ns3d_pt_solve_slab: null field pointer (local rank %d)", l);
         ns3d_device_guard g(r.device);
-        if (r.cbuf_bytes < bytes) {
-            HIPCHK(0, hipStreamSynchronize(compute(r)));
-            if (r.cbuf) HIPCHK(0, hipFree(r.cbuf));
-            r.cbuf = nullptr; r.cbuf_bytes = 0;
-            HIPCHK(0, hipMalloc(&r.cbuf, bytes));
-            r.cbuf_bytes = bytes;
-        }
-        cur[l] = Pr[l]; other[l] = (T *)r.cbuf;
+        if ((rc = r.cbuf.reserve(bytes, drain_compute(r)))) return rc;
+        cur[l] = Pr[l]; other[l] = r.cbuf.as<T>();
         pe[l].owns_outlet = (p->owns_outlet && r.nbr[0][1] < 0) ? 1 : 0;      // multi.jl:179: the ranks on the outlet plane
         pe[l].z_lo_is_halo = pe[l].z_hi_is_halo = 0;                          // every face folded; update_halo! overwrites
     }
@@ -855,16 +841,9 @@ int box_exchange(ns3d_mgpu *m, const std::vector<std::vector<BoxArr>> &arrs, boo
             }
             need = std::max(need, nd);
         }
-        if (need > r.bbuf_bytes) {
+        if (need > r.bbuf.bytes) {                  // every call but the first of a size: no device switch
             ns3d_device_guard g(r.device);
-            if (r.bbuf) {
-                int rc = sync_all(m);                  // a neighbour may still be pulling from the old buffer
-                if (rc) return rc;
-                HIPCHK(0, hipFree(r.bbuf));
-                r.bbuf = nullptr; r.bbuf_bytes = 0;
-            }
-            HIPCHK(0, hipMalloc(&r.bbuf, need));
-            r.bbuf_bytes = need;
+            if (const int rc = r.bbuf.reserve(need, drain_grid(m))) return rc;     // a neighbour may still be pulling from the old buffer
         }
     }
     for (int d = 0; d < 3; ++d) {
@@ -890,7 +869,7 @@ int box_exchange(ns3d_mgpu *m, const std::vector<std::vector<BoxArr>> &arrs, boo
                 int c[3] = {s[0], s[1], s[2]};
                 c[d] = L;
                 const size_t face = (size_t)c[0] * c[1] * c[2];
-                T *b0 = (T *)((char *)r.bbuf + off);
+                T *b0 = (T *)(r.bbuf.as<char>() + off);
                 off += 4 * face * sizeof(T);
                 blocks[l].push_back({b0, b0 + 2 * face, b0 + face, b0 + 3 * face, face * sizeof(T)});
                 pieces[l].push_back({A, px, pl, {c[0], c[1], c[2]}, recv_lo, recv_hi});
@@ -966,21 +945,21 @@ int deep_load(ns3d_mgpu *m, const T *const *Pr, const T *const *D, const T *cons
         const size_t bp = b.cells * sizeof(T), bd = b.dcells * sizeof(T);
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
-        if (r.st.bytes_P != bp || r.st.bytes_D != bd) {
-            if ((rc = sync_all(m))) return rc;          // a neighbour may still be pulling from the old buffers
+        if (r.st.bytes_P != bp || r.st.bytes_D != bd) {     // replaced when the size DIFFERS (smaller too), and zero-filled again
+            if (r.st.Pa[0].ptr && (rc = sync_all(m))) return rc;       // a neighbour may still be pulling from the old buffers
             free_slab(r);
-            for (int q = 0; q < 2; ++q) {
-                HIPCHK(0, hipMalloc(&r.st.Pa[q], bp));
-                HIPCHK(0, hipMalloc(&r.st.Da[q], bd));
-                HIPCHK(0, hipMemsetAsync(r.st.Pa[q], 0, bp, s));
-                HIPCHK(0, hipMemsetAsync(r.st.Da[q], 0, bd, s));
-            }
-            HIPCHK(0, hipMalloc(&r.st.Ra, bp));
-            HIPCHK(0, hipMemsetAsync(r.st.Ra, 0, bp, s));
+            auto fresh = [&](ns3d_scratch &b, size_t bytes) -> int {      // b is empty since free_slab: nothing left to drain
+                if (const int e = b.reserve(bytes, drain_grid(m))) return e;
+                HIPCHK(0, hipMemsetAsync(b.ptr, 0, bytes, s));
+                return NS3D_OK;
+            };
+            for (int q = 0; q < 2; ++q)
+                if ((rc = fresh(r.st.Pa[q], bp)) || (rc = fresh(r.st.Da[q], bd))) return rc;
+            if ((rc = fresh(r.st.Ra, bp))) return rc;
             r.st.bytes_P = bp; r.st.bytes_D = bd;
         }
-        for (int q = 0; q < 2; ++q) { r.st.P[q] = r.st.Pa[q]; r.st.D[q] = r.st.Da[q]; }
-        r.st.R = r.st.Ra;
+        for (int q = 0; q < 2; ++q) { r.st.P[q] = r.st.Pa[q].ptr; r.st.D[q] = r.st.Da[q].ptr; }
+        r.st.R = r.st.Ra.ptr;
         r.st.ip = r.st.id = 0;
         r.plan_v2 = r.plan_vn = -1; r.plan_lo = r.plan_hi = 0;       // a new state: planned again by deep_plan
         T *P0 = (T *)r.st.P[0] + b.op, *D0 = (T *)r.st.D[0] + b.od, *R0 = (T *)r.st.R + b.op;
@@ -1342,15 +1321,9 @@ int advect_wide(ns3d_mgpu *m, T *const *V[4], T *const *Vo[4], double dt, double
             if (!V[f][l] || !Vo[f][l]) return fail(NS3D_ERR_ARG, "ns3d_advect_wide: null field pointer (local rank %zu)", l);
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
-        if (r.wbuf_bytes < total * sizeof(T)) {
-            if ((rc = sync_all(m))) return rc;           // a neighbour may still pull from the old buffer
-            if (r.wbuf) HIPCHK(0, hipFree(r.wbuf));
-            r.wbuf = nullptr; r.wbuf_bytes = 0;
-            HIPCHK(0, hipMalloc(&r.wbuf, total * sizeof(T)));
-            r.wbuf_bytes = total * sizeof(T);
-        }
+        if ((rc = r.wbuf.reserve(total * sizeof(T), drain_grid(m)))) return rc;     // a neighbour may still pull from the old buffer
         const int elo = has_lower(m, r) ? 1 : 0;
-        T *W = (T *)r.wbuf;
+        T *W = r.wbuf.as<T>();
         for (int f = 0; f < 4; ++f) {
             const int sz = ext[f][2], ol = 2 + (sz - nz);
             T *old = W + off_o[f];
@@ -1369,7 +1342,7 @@ int advect_wide(ns3d_mgpu *m, T *const *V[4], T *const *Vo[4], double dt, double
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
         const int elo = has_lower(m, r) ? 1 : 0, ehi = has_upper(m, r) ? 1 : 0;
-        T *W = (T *)r.wbuf;
+        T *W = r.wbuf.as<T>();
         hipError_t e = ns3d_enqueue_advect<T>(r.ctx, s, W + off_n[0], W + off_o[0], W + off_n[1], W + off_o[1], W + off_n[2], W + off_o[2],
                                               W + off_n[3], W + off_o[3], dt, dx, dy, dz, nx, ny, nz + elo + ehi, (faithful ? 1 : 0) | 2,
                                               r.coords[2] * (nz - 2) - elo, m->dims[2] * (nz - 2) + 2);    // departure indices from GLOBAL plane numbers
@@ -1408,12 +1381,8 @@ int gather_impl(ns3d_mgpu *m, const T *const *A, int sx, int sy, int sz, T *out_
         MRank &r = m->loc[l];
         if (!A[l]) return fail(NS3D_ERR_ARG, "ns3d_gather: null pointer (local rank %zu)", l);
         ns3d_device_guard g(r.device);
-        if (r.gbuf_bytes < bytes) {
-            if (r.gbuf) { HIPCHK(0, hipStreamSynchronize(compute(r))); HIPCHK(0, hipFree(r.gbuf)); r.gbuf = nullptr; r.gbuf_bytes = 0; }
-            HIPCHK(0, hipMalloc(&r.gbuf, bytes));
-            r.gbuf_bytes = bytes;
-        }
-        hipError_t e = ns3d_enqueue_strip_inner<T>(r.ctx, compute(r), A[l], (T *)r.gbuf, sx, sy, sz);
+        if (const int rc = r.gbuf.reserve(bytes, drain_compute(r))) return rc;
+        hipError_t e = ns3d_enqueue_strip_inner<T>(r.ctx, compute(r), A[l], r.gbuf.as<T>(), sx, sy, sz);
         if (e != hipSuccess) return fail(NS3D_ERR_HIP, "strip_inner launch: %s", hipGetErrorString(e));
     }
     const bool root = !m->rccl || m->loc[0].rank == 0;
@@ -1427,7 +1396,7 @@ int gather_impl(ns3d_mgpu *m, const T *const *A, int sx, int sy, int sz, T *out_
         for (size_t l = 0; l < m->loc.size(); ++l) {
             MRank &r = m->loc[l];
             ns3d_device_guard g(r.device);
-            HIPCHK(0, hipMemcpyAsync(land + blk * r.rank, r.gbuf, bytes, hipMemcpyDeviceToHost, compute(r)));
+            HIPCHK(0, hipMemcpyAsync(land + blk * r.rank, r.gbuf.ptr, bytes, hipMemcpyDeviceToHost, compute(r)));
         }
         int rc = sync_all(m);
         if (rc) return rc;
@@ -1436,22 +1405,18 @@ int gather_impl(ns3d_mgpu *m, const T *const *A, int sx, int sy, int sz, T *out_
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
         if (r.rank != 0) {
-            if (m->P > 1) NCCLCHK(g_rccl.Send(r.gbuf, bytes, ncclUint8, 0, m->comm, s));
+            if (m->P > 1) NCCLCHK(g_rccl.Send(r.gbuf.ptr, bytes, ncclUint8, 0, m->comm, s));
             HIPCHK(0, hipStreamSynchronize(s));
             return NS3D_OK;
         }
-        if (m->stage_bytes < bytes * m->P) {
-            if (m->stage) { HIPCHK(0, hipStreamSynchronize(s)); HIPCHK(0, hipFree(m->stage)); m->stage = nullptr; m->stage_bytes = 0; }
-            HIPCHK(0, hipMalloc(&m->stage, bytes * m->P));
-            m->stage_bytes = bytes * m->P;
-        }
-        HIPCHK(0, hipMemcpyAsync(m->stage, r.gbuf, bytes, hipMemcpyDeviceToDevice, s));
+        if (const int rc = m->stage.reserve(bytes * m->P, drain_compute(r))) return rc;
+        HIPCHK(0, hipMemcpyAsync(m->stage.ptr, r.gbuf.ptr, bytes, hipMemcpyDeviceToDevice, s));
         if (m->P > 1) {
             NCCLCHK(g_rccl.GroupStart());
-            for (int q = 1; q < m->P; ++q) NCCLCHK(g_rccl.Recv((char *)m->stage + bytes * q, bytes, ncclUint8, q, m->comm, s));
+            for (int q = 1; q < m->P; ++q) NCCLCHK(g_rccl.Recv(m->stage.as<char>() + bytes * q, bytes, ncclUint8, q, m->comm, s));
             NCCLCHK(g_rccl.GroupEnd());
         }
-        HIPCHK(0, hipMemcpyAsync(land, m->stage, bytes * m->P, hipMemcpyDeviceToHost, s));
+        HIPCHK(0, hipMemcpyAsync(land, m->stage.ptr, bytes * m->P, hipMemcpyDeviceToHost, s));
         HIPCHK(0, hipStreamSynchronize(s));
     }
     if (!direct)
@@ -1506,7 +1471,7 @@ int diag_mgpu(ns3d_mgpu *m, const T *const *Vx, const T *const *Vy, const T *con
         MRank &r = m->loc[0];
         ns3d_device_guard g(r.device);
         hipStream_t s = compute(r);
-        unsigned long long *hw = r.ctx->diag_host + 16, *dw = r.ctx->diag_dev + 16;
+        unsigned long long *hw = r.ctx->diag_host + 16, *dw = r.ctx->diag_dev.as<unsigned long long>() + 16;
         const double sums[5] = {tot.ke, tot.c_vol, tot.mom[0], tot.mom[1], tot.mom[2]};
         std::memcpy(hw, sums, sizeof sums);
         for (int q = 0; q < 3; ++q) hw[5 + q] = (unsigned long long)tot.n_masked[q];
@@ -1573,22 +1538,6 @@ int tracers_advance_all(ns3d_mgpu *m, double *const *X, unsigned char *const *st
     return NS3D_OK;
 }
 
-// a rank's scratch buffer, at least `need` bytes: grown behind everything its streams hold
-int grow_buffer(MRank &r, void *&buf, size_t &have, size_t need)
-{
-    if (have >= need && buf) return NS3D_OK;
-    if (buf) {
-        HIPCHK(0, hipStreamSynchronize(compute(r)));
-        HIPCHK(0, hipStreamSynchronize(r.comm));
-        HIPCHK(0, hipFree(buf));
-        buf = nullptr; have = 0;
-    }
-    if (need < 256) need = 256;
-    HIPCHK(0, hipMalloc(&buf, need));
-    have = need;
-    return NS3D_OK;
-}
-
 // ns3d_tracers_migrate_mgpu (one-process form: local index == rank).  Count on every rank, read the (P+1)·P totals back, decide on
 // the host whether every rank has room; only then pack, exchange (alltoall: the receivers pull) and insert.
 int tracers_migrate(ns3d_mgpu *m, double *const *X, unsigned char *const *state, long long *const *id, double *const *U, const long *cap,
@@ -1608,11 +1557,11 @@ int tracers_migrate(ns3d_mgpu *m, double *const *X, unsigned char *const *state,
         const size_t nwg = (size_t)((cap[l] + 255) / 256), rows = (size_t)P + 1;
         const size_t words = rows + (size_t)P + rows * nwg;                        // 8-byte entries: totals, dbase, offs
         const size_t bytes = words * 8 + rows * nwg * sizeof(unsigned) + 2 * (size_t)cap[l] * sizeof(int);
-        int rc = grow_buffer(r, r.tbuf, r.tbuf_bytes, bytes);
+        int rc = r.tbuf.reserve(std::max(bytes, (size_t)256), drain_rank(r));
         if (rc) return rc;
         if (!r.thost) HIPCHK(0, hipHostMalloc((void **)&r.thost, (2 * (size_t)P + 1) * sizeof(unsigned long long)));
         ns3d_mig_scratch &w = ws[l];
-        w.totals = (unsigned long long *)r.tbuf;
+        w.totals = r.tbuf.as<unsigned long long>();
         w.dbase = w.totals + rows;
         w.offs = w.dbase + P;
         w.counts = (unsigned *)(w.offs + rows * nwg);
@@ -1653,9 +1602,10 @@ int tracers_migrate(ns3d_mgpu *m, double *const *X, unsigned char *const *state,
     for (int l = 0; l < n; ++l) {
         MRank &r = m->loc[l];
         ns3d_device_guard g(r.device);
-        int rc = grow_buffer(r, r.tsend, r.tsend_bytes, (size_t)leavers[l] * rec_bytes);
+        // at least 256 bytes: a rank without leavers or arrivals still hands out non-null pointers
+        int rc = r.tsend.reserve(std::max((size_t)leavers[l] * rec_bytes, (size_t)256), drain_rank(r));
         if (rc) return rc;
-        rc = grow_buffer(r, r.trecv, r.trecv_bytes, (size_t)arrivals[l] * rec_bytes);
+        rc = r.trecv.reserve(std::max((size_t)arrivals[l] * rec_bytes, (size_t)256), drain_rank(r));
         if (rc) return rc;
     }
     for (int l = 0; l < n; ++l) {
@@ -1664,14 +1614,14 @@ int tracers_migrate(ns3d_mgpu *m, double *const *X, unsigned char *const *state,
         unsigned long long *base = r.thost + P + 1, run = 0ull, from = 0ull;
         for (int d = 0; d < P; ++d) {
             base[d] = run;
-            send[l][d] = Piece{(char *)r.tsend + run * rec_bytes, (size_t)r.thost[d] * rec_bytes};
+            send[l][d] = Piece{r.tsend.as<char>() + run * rec_bytes, (size_t)r.thost[d] * rec_bytes};
             run += r.thost[d];
-            recv[l][d] = Piece{(char *)r.trecv + from * rec_bytes, (size_t)m->loc[d].thost[l] * rec_bytes};
+            recv[l][d] = Piece{r.trecv.as<char>() + from * rec_bytes, (size_t)m->loc[d].thost[l] * rec_bytes};
             from += m->loc[d].thost[l];
         }
         if (leavers[l] == 0) continue;
         HIPCHK(0, hipMemcpyAsync(ws[l].dbase, base, (size_t)P * sizeof(unsigned long long), hipMemcpyHostToDevice, compute(r)));
-        hipError_t e = ns3d_tracers::mig_pack(compute(r), ws[l], (double *)r.tsend, X[l], state[l], id[l], U ? U[l] : nullptr, cap[l]);
+        hipError_t e = ns3d_tracers::mig_pack(compute(r), ws[l], r.tsend.as<double>(), X[l], state[l], id[l], U ? U[l] : nullptr, cap[l]);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "%s: pack launch: %s", fn, hipGetErrorString(e)); }
     }
     int rc = alltoall(m, send, recv);
@@ -1680,7 +1630,7 @@ int tracers_migrate(ns3d_mgpu *m, double *const *X, unsigned char *const *state,
         MRank &r = m->loc[l];
         if (arrivals[l] == 0) continue;
         ns3d_device_guard g(r.device);
-        hipError_t e = ns3d_tracers::mig_insert(compute(r), ws[l], P, (const double *)r.trecv, (long)arrivals[l], X[l], state[l], id[l],
+        hipError_t e = ns3d_tracers::mig_insert(compute(r), ws[l], P, r.trecv.as<double>(), (long)arrivals[l], X[l], state[l], id[l],
                                                 U ? U[l] : nullptr, cap[l]);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "%s: insert launch: %s", fn, hipGetErrorString(e)); }
     }
@@ -1833,24 +1783,15 @@ void ns3d_mgpu_destroy(ns3d_mgpu *m)
     for (MRank &r : m->loc) {
         if (!r.ctx) continue;              // a rank that never came up (failed create) owns nothing
         ns3d_device_guard g(r.device);
-        free_slab(r);
-        free_direct(r);
-        if (r.gbuf) (void)hipFree(r.gbuf);
-        if (r.hbuf) (void)hipFree(r.hbuf);
-        if (r.cbuf) (void)hipFree(r.cbuf);
-        if (r.bbuf) (void)hipFree(r.bbuf);
-        if (r.wbuf) (void)hipFree(r.wbuf);
-        if (r.tbuf) (void)hipFree(r.tbuf);
-        if (r.tsend) (void)hipFree(r.tsend);
-        if (r.trecv) (void)hipFree(r.trecv);
+        r.ds.release();                    // the eigenbases are plain pointers (ns3d_direct_bases)
         if (r.thost) (void)hipHostFree(r.thost);
         if (r.ev_ready) (void)hipEventDestroy(r.ev_ready);
         if (r.ev_landed) (void)hipEventDestroy(r.ev_landed);
         if (r.ev_pass) (void)hipEventDestroy(r.ev_pass);
         if (r.comm) (void)hipStreamDestroy(r.comm);
         if (r.ctx) ns3d_destroy(r.ctx);
+        MRank gone(std::move(r));          // the rank's ns3d_scratch members go here: its device current, every stream waited for
     }
-    if (m->stage) (void)hipFree(m->stage);
     delete m;
 }
 
