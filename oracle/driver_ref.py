@@ -195,16 +195,57 @@ def _maccormack(advection, faithful, P=1):
         raise ValueError("advection=\"maccormack\" advects Vz: it needs faithful=False")
     if P != 1:
         raise ValueError("advection=\"maccormack\" is defined on one rank (this grid has %d)" % P)
+    return _tests_module("advect_mc_ref").advect_mc
+
+
+def _tests_module(name):
+    """a module of tests/ by file (the suite has tests/ on its path and the module loaded; anyone else gets it from the file)"""
     import importlib.util
     import os
     import sys
-    if "advect_mc_ref" not in sys.modules:          # the suite has tests/ on its path and the module loaded; anyone else gets it by file
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "advect_mc_ref.py")
-        spec = importlib.util.spec_from_file_location("advect_mc_ref", path)
+    if name not in sys.modules:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", name + ".py")
+        spec = importlib.util.spec_from_file_location(name, path)
         mod = importlib.util.module_from_spec(spec)
-        sys.modules["advect_mc_ref"] = mod
+        sys.modules[name] = mod
         spec.loader.exec_module(mod)
-    return sys.modules["advect_mc_ref"].advect_mc
+    return sys.modules[name]
+
+
+def _obstacle(obstacle, n, P=1):
+    """the `obstacle` keyword of both drivers → None (the cylinder) or (tests/solid_ref.py, the uint8 mask of shape (nx+1, ny+1, nz+1)).
+    The masking's statement is solid_ref.set_solid, imported only here, when a mask is given."""
+    if obstacle is None:
+        return None
+    if P != 1:
+        raise ValueError("obstacle= is defined on one rank (this grid has %d)" % P)
+    mask = np.asarray(obstacle)
+    want = (n[0] + 1, n[1] + 1, n[2] + 1)
+    if mask.dtype != np.uint8 or mask.shape != want:
+        raise ValueError("obstacle: a uint8 mask of shape %r; got %s %r" % (want, mask.dtype, mask.shape))
+    return _tests_module("solid_ref"), np.asfortranarray(mask)
+
+
+def _mask_step(solid, f, removed):
+    """ns3d_set_solid where the script calls set_cylinder!; `removed` (a list, or None before the time loop) first receives
+    solid_ref.momentum of the velocities as they are: what this masking removes — (fsum, counts, Σ|term|) per direction"""
+    SR, mask = solid
+    if removed is not None:
+        removed.append(SR.momentum(f.Vx, f.Vy, f.Vz, mask))
+    SR.set_solid(f.C, f.Vx, f.Vy, f.Vz, mask)
+
+
+def _set_initial(f, initial):
+    """the `initial` keyword of both drivers: name → array for any of C, Pr, Vx, Vy, Vz, copied over the script's own initial fields"""
+    if initial is None:
+        return
+    for name, a in initial.items():
+        if name not in ("C", "Pr", "Vx", "Vy", "Vz"):
+            raise ValueError("initial: %r is none of C, Pr, Vx, Vy, Vz" % (name,))
+        a = np.asarray(a)
+        if a.shape != f[name].shape:
+            raise ValueError("initial[%r] has shape %r, the field %r" % (name, a.shape, f[name].shape))
+        f[name][...] = a.astype(f[name].dtype)
 
 
 def advect_mc_step(f, p, advect_mc):
@@ -217,17 +258,26 @@ def advect_mc_step(f, p, advect_mc):
 
 
 def run_navierstokes3D_ref(nx=63, nt=1, dims_z=1, dtype=np.float64, faithful=True, niter_cap=None,
-                           record=None, shape=None, dims=None, pressure="pt", wide_advect_halo=False, advection="reference"):
+                           record=None, shape=None, dims=None, pressure="pt", wide_advect_halo=False, advection="reference",
+                           obstacle=None, initial=None):
     """multi.jl:287-536 without vis/save.  Returns (C_v,Pr_v,Vx_v,Vy_v,Vz_v, info) where info holds the
     per-step PT iteration counts and err histories, and the final local states.
     advection="maccormack" (outside the reference; faithful=False, one rank — anything else raises ValueError): :475-476 are replaced
-    by the definition of ns3d_advect_mc."""
+    by the definition of ns3d_advect_mc.
+    obstacle= (outside the reference; one rank — more raise ValueError): a uint8 mask of shape (nx+1, ny+1, nz+1) applied by
+    tests/solid_ref.py::set_solid wherever the script calls set_cylinder! (:372, :452, :473); info.removed then holds per step the
+    pair of solid_ref.momentum results taken right before the step's two maskings.
+    initial=: a dict name → array for any of C, Pr, Vx, Vy, Vz, copied over the script's own initial fields (after :369-371, before
+    the masking :372).  Both default to None, and the defaults change nothing."""
     p = multi_params(nx, dims_z, dtype, dims=dims, **(shape or {}))
     nx, ny, nz = p.nx, p.ny, p.nz
     niter = p.niter if niter_cap is None else min(p.niter, niter_cap)
     dims = p.dims
     P = dims[0] * dims[1] * dims[2]
     advect_mc = _maccormack(advection, faithful, P)
+    solid = _obstacle(obstacle, (nx, ny, nz), P)
+    if initial is not None and P != 1:
+        raise ValueError("initial= is defined on one rank (this grid has %d)" % P)
     update_halo_z = lambda rks, name, _nz: update_halo_3d(rks, name, (nx, ny, nz), dims)      # noqa: F841 (shadows the z-only form)
     gather_z = lambda rks, name: gather_3d(rks, name, dims)                                     # noqa: F841
     ranks = []
@@ -250,14 +300,27 @@ def run_navierstokes3D_ref(nx=63, nt=1, dims_z=1, dtype=np.float64, faithful=Tru
             f.Pr[:, :, iz] = -(_x_g(iz + 1, p.dz, nz, nz, c) - p.dz / 2) * p.rho * p.g + 0.0
         ranks.append(f)
     update_halo_z(ranks, "Pr", nz)                                                         # :371
-    for f in ranks:                                                                        # :372
+    for f in ranks:
+        _set_initial(f, initial)
+
+    def mask(f, removed=None):              # set_cylinder! :372, :452, :473 — or the obstacle's mask in its place
+        if solid is not None:
+            return _mask_step(solid, f, removed)
         K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, f.xco_g, f.yco_g,
                        f.zco_g, p.lx, p.ly, p.lz, p.dx, p.dy, p.dz)
+    for f in ranks:                                                                        # :372
+        mask(f)
     for n in ("C", "Vx", "Vy", "Vz"):                                                      # :373
         update_halo_z(ranks, n, nz)
 
     info = Obj(iters=[], errs=[], params=p)
+    if solid is not None:
+        info.removed = []
     for it in range(1, nt + 1):                                                            # :446
+        removed = None
+        if solid is not None:
+            removed = []
+            info.removed.append(removed)
         for f in ranks:                                                                    # :449
             K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz)
         for n in ("txx", "tyy", "tzz"):                                                    # :450
@@ -265,8 +328,7 @@ def run_navierstokes3D_ref(nx=63, nt=1, dims_z=1, dtype=np.float64, faithful=Tru
         for f in ranks:                                                                    # :451-452
             K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt,
                         p.dx, p.dy, p.dz)
-            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, f.xco_g, f.yco_g,
-                           f.zco_g, p.lx, p.ly, p.lz, p.dx, p.dy, p.dz)
+            mask(f, removed)
         for n in ("C", "Vx", "Vy", "Vz"):                                                  # :453
             update_halo_z(ranks, n, nz)
         for f in ranks:                                                                    # :454
@@ -310,8 +372,7 @@ def run_navierstokes3D_ref(nx=63, nt=1, dims_z=1, dtype=np.float64, faithful=Tru
         info.errs.append(errs)
         for f in ranks:                                                                    # :472-474
             K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz)
-            K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, f.xco_g, f.yco_g,
-                           f.zco_g, p.lx, p.ly, p.lz, p.dx, p.dy, p.dz)
+            mask(f, removed)
             K.set_bc_Vel(f.Vx, f.Vy, f.Vz, 0, f.owns_inlet, p.vin)
         for n in ("Vx", "Vy", "Vz"):                                                       # :167
             update_halo_z(ranks, n, nz)
@@ -382,22 +443,38 @@ def gpu_initial_fields(p):
     return Vx, Pr
 
 
-def runme_ref(nx=255, nt=1, dtype=np.float64, faithful=True, niter_cap=None, pressure="pt", advection="reference"):
+def runme_ref(nx=255, nt=1, dtype=np.float64, faithful=True, niter_cap=None, pressure="pt", advection="reference", obstacle=None,
+              initial=None):
     """gpu.jl:12-173 without vis/save; returns the final local fields + per-step PT info.
-    advection: as in run_navierstokes3D_ref, in place of :141-142."""
+    advection: as in run_navierstokes3D_ref, in place of :141-142.
+    obstacle, initial: as in run_navierstokes3D_ref — the mask in place of set_cylinder! :123 and :139 (info.removed), the given
+    fields over :85-88's."""
     advect_mc = _maccormack(advection, faithful)
     p = gpu_params(nx, dtype)
     nx, ny, nz = p.nx, p.ny, p.nz
+    solid = _obstacle(obstacle, (nx, ny, nz))
     f = _alloc_multi(Obj(nx=nx, ny=ny, nz=nz, dtype=dtype))
     Vx0, Pr0 = gpu_initial_fields(p)
     f.Vx[...] = Vx0.astype(dtype); f.Pr[...] = Pr0.astype(dtype)
+    _set_initial(f, initial)
     niter = p.niter if niter_cap is None else min(p.niter, niter_cap)
     info = Obj(iters=[], errs=[], params=p)
-    for it in range(1, nt + 1):                                                            # :119
-        K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz)
-        K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz)
+    if solid is not None:
+        info.removed = []
+
+    def mask(removed):                      # set_cylinder! :123, :139 — or the obstacle's mask in its place
+        if solid is not None:
+            return _mask_step(solid, f, removed)
         K.set_cylinder_local(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.lx, p.ly, p.lz,
                              p.dx, p.dy, p.dz)
+    for it in range(1, nt + 1):                                                            # :119
+        removed = None
+        if solid is not None:
+            removed = []
+            info.removed.append(removed)
+        K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz)
+        K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz)
+        mask(removed)                                                                      # :123
         K.update_divV(f.divV, f.Vx, f.Vy, f.Vz, p.dx, p.dy, p.dz)
         if pressure == "direct":        # the option outside parity (oracle/direct_ref.py)
             from oracle.direct_ref import poisson_direct
@@ -410,8 +487,7 @@ def runme_ref(nx=255, nt=1, dtype=np.float64, faithful=True, niter_cap=None, pre
                                           p.dz, 1, False, 0.0, p.g, p.eps, niter, p.nchk, p.ly * p.ly, p.psc)   # :126-137
         info.iters.append(iters_done); info.errs.append(errs)
         K.correct_V(f.Vx, f.Vy, f.Vz, f.Pr, p.dt, p.rho, p.dx, p.dy, p.dz)                 # :138
-        K.set_cylinder_local(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.lx, p.ly, p.lz,
-                             p.dx, p.dy, p.dz)                                             # :139
+        mask(removed)                                                                      # :139
         K.set_bc_Vel(f.Vx, f.Vy, f.Vz, 1)                                                  # :140
         if advect_mc is not None:
             advect_mc_step(f, p, advect_mc)

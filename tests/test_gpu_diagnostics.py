@@ -271,6 +271,44 @@ def test_virtual_ranks_count_the_global_arrays_once(hip, dims, dtype):
     mg.close()
 
 
+REDUCTION_GRIDS = [((3, 255, 63), 8, 512), ((3, 1023, 127), 16, 2048), ((3, 2047, 127), 32, 2048)]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("n,kz,partials", REDUCTION_GRIDS, ids=["%dx%dx%d" % n for n, _, _ in REDUCTION_GRIDS])
+def test_more_than_256_partials_and_every_chunk_depth(hip, n, kz, partials, dtype):
+    """k_diag_final's thread t combines the partials t, t + 256, …: GRIDS leaves at most 255 (131×66×37), so the second trip of that
+    loop never ran, and ns3d_diag_geometry returned kz = 8 only.  Thin grids of under 0.8 M cells with 512 and 2 048 partials and kz =
+    8, 16, 32 — asserted from the formula restated here —, against _reference with the file's bound, seams none and all."""
+    nx, ny, nz = n
+    gx, gy = (nx + 1 + 63) // 64, (ny + 1 + 3) // 4                  # ns3d_diag_geometry (csrc/ns3d_launch.h)
+    z = 32
+    while z > 8 and gx * gy * ((nz + 1 + z - 1) // z) < 2048:
+        z //= 2
+    assert (z, gx * gy * ((nz + 1 + z - 1) // z)) == (kz, partials) and D.launch_geometry(*n) == (partials, kz)
+    assert partials > 256 and nx * ny * nz < 800000
+    g = geometry(*n)
+    F = _host_fields(n, dtype, 31)
+    cyl = _cyl("multi", n[0], n[1], g)
+    L = D.path_length(*n)
+    assert L == kz + 9 + partials // 256 + 9
+    ctx = hip.Context(0, "strict")
+    masks = _masks(hip, ctx, n, cyl, dtype)
+    dev = _upload(hip, F)
+    for lo, hi in (((0, 0, 0), (0, 0, 0)), ((1, 1, 1), (1, 1, 1))):
+        dp = hip.diag_params(*n, g["dx"], g["dy"], g["dz"], g["rho"], lo, hi, cylinder=cyl)
+        ref, mag = _reference(hip, ctx, F, n, g, lo, hi, masks)
+        got = hip.diagnostics(*dev, dp, ctx=ctx)
+        assert got.vmax == ref["vmax"] and (got.pr_min, got.pr_max, got.div_max) == (ref["pr_min"], ref["pr_max"], ref["div_max"])
+        assert got.n_masked == ref["n_masked"] and got.nonfinite == 0
+        if lo == (0, 0, 0):
+            assert sum(got.n_masked) > 0
+        _check_sums(got, ref, mag, L, "%r seams %r" % (n, lo))
+        again = hip.diagnostics(*dev, dp, ctx=ctx)
+        assert all(_same(getattr(got, k), getattr(again, k)) for k in vars(got)), "a repeated call changed bits"
+    ctx.close()
+
+
 # ---- drivers -----------------------------------------------------------------------------------------------------------
 def _same_run(a, b):
     from util import errs_identical

@@ -617,6 +617,27 @@ def test_time_step_maccormack(hip, oracle, script, mode):
     test_time_step(hip, oracle, script, mode, advection="maccormack")
 
 
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_time_step_obstacle(hip, oracle, script, mode):
+    """The step with ns3d_set_obstacle: the seventeen arrays AND the mask (uint8, on an odd byte) in the arena, from the scenario of
+    tests/solid_step_cases.py — a state in which every mask bit acts — with the body that meets five outer planes; multi.jl's
+    ns3d_set_solid before the loop reads the arena's mask as well.  Guards intact, the mask unchanged, every array and the iteration
+    record equal to the run on plain arrays, and in STRICT to the oracle driver with obstacle= (a test of its own: the existing cases
+    keep their names).  float64."""
+    import solid_step_cases as SS
+    from test_gpu_solid_step import assert_equals_the_oracle, assert_same_run, steps_on
+    ctx = hip.Context(0, mode, async_=True)
+    got = steps_on(hip, script, "f64", ctx, SS.body_mask(), in_arena=True)
+    want = steps_on(hip, script, "f64", ctx, SS.body_mask())
+    ctx.close()
+    assert got.arena["mask"].data_ptr() % 2 == 1
+    assert all(np.isfinite(a).all() for a in want.fields.values()) and np.abs(want.fields["txx"]).max() > 0
+    assert_same_run(got, want, (script, mode))
+    if mode == "strict":
+        assert_equals_the_oracle(got, script, "f64", "reference")
+
+
 # ---- 8. derived fields ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("dt", DTS)

@@ -1,7 +1,9 @@
 """GPU tests of the obstacle calls (include/ns3d.h): ns3d_voxelize byte for byte against its NumPy statement tests/solid_ref.py,
 ns3d_set_solid against set_cylinder! and in a guarded arena under a hostile mask, ns3d_solid_momentum against math.fsum and the
 monitor, ns3d_set_obstacle inside ns3d_time_step and the `obstacle` keyword of both drivers, and each call once in stream order.
-Every context kind (STRICT, NS3D_IEEE_DIV, FAST) must return the same bytes."""
+Every context kind (STRICT, NS3D_IEEE_DIV, FAST) must return the same bytes.  The kernels' edges: rows of up to three 64-word passes of
+k_vox_prefix, more than 256 partials in k_mom_final, ns3d_set_solid's mask at every address mod 16.  The whole step against its CPU
+statement is in tests/test_gpu_solid_step.py."""
 import ctypes as C
 import math
 
@@ -159,6 +161,40 @@ def test_voxelize_in_a_guarded_arena(hip, S, ctxs):
     assert np.array_equal(ar.get("mask"), SR.voxelize(tri, *n)) and np.array_equal(ar.get("tri"), tri.reshape(-1))
 
 
+LONG_ROWS = [((1100, 5, 3), 35, (7, 4096, 70001)), ((2046, 3, 3), 64, None), ((2047, 4, 3), 65, None), ((4200, 3, 3), 132, None)]
+
+
+@pytest.mark.parametrize("n,W,origin", LONG_ROWS, ids=[GID(n) for n, _, _ in LONG_ROWS])
+def test_voxelize_long_rows(hip, S, ctxs, n, W, origin):
+    """Rows of more than 96 samples: k_vox_prefix's ballot lanes ≥ 32 (W = 35 words per row), exactly one pass of 64 words (W = 64), a
+    second pass with one live lane (W = 65), three passes (W = 132) with the row parity carried from pass to pass; one grid with an
+    origin.  Bodies: an octahedron spanning the row (inside across every pass boundary), a box that leaves the grid at high x, and —
+    where the row has a sample 2048 — boxes whose x faces put a flip on samples 2047 and 2048 of the C and of the Vx family: bit 31
+    of word 63 and bit 0 of word 64."""
+    nx, ny, nz = n
+    assert (nx + 2 + 31) // 32 == W
+    o = np.zeros(3) if origin is None else np.array(origin, dtype=np.float64)
+    ext = np.array(n, dtype=np.float64)
+    j, k = (ny - 1) // 2, (nz - 1) // 2      # the row next to the octahedron's axis
+    span = SC.octahedron(o + (0.5 * nx + 0.2, j + 0.51, k + 0.505), (0.5 * nx - 1.3, j + 0.3, k + 0.3))
+    m = _check_all(S, ctxs, span, n, origin=origin, what="spanning octahedron")
+    assert (m[nx // 2, j, k] & 3) == 3 and (m[nx - 64, j, k] & 3) == 3 and not m[0, j, k] and not (m[nx - 1, j, k] & 1)
+    for b in range(2048, nx - 64, 2048):    # inside on both sides of every pass boundary of the central row: the parity is carried
+        assert (m[b - 1, j, k] & 3) == 3 and (m[b, j, k] & 3) == 3, (b, int(m[b - 1, j, k]), int(m[b, j, k]))
+    high = S.box_mesh(o + (nx - 40.5, 0.7, 0.6), o + (nx + 5.0, 1.9, 1.8))
+    m = _check_all(S, ctxs, high, n, origin=origin, what="box through the high x end")
+    assert (m[nx, 1, 1] & 2) and (m[nx - 1, 1, 1] & 1) and not m[nx - 42, 1, 1]
+    if nx > 2048:
+        flips = np.concatenate([S.box_mesh(o + (2046.75, 0.2, 0.2), o + (2047.75, 0.9, 2.8)),      # C and Vx: sample 2047 alone
+                                S.box_mesh(o + (100.3, 1.2, 0.2), o + (2047.25, 1.9, 2.8)),        # C ends on 2046, Vx on 2047
+                                S.box_mesh(o + (2047.75, 2.1, 0.2), o + (2100.4, 2.9, 2.8))])      # C and Vx begin on 2048
+        m = _check_all(S, ctxs, flips, n, origin=origin, what="flips on samples 2047 and 2048")
+        assert [int(m[i, 0, 1] & 3) for i in (2046, 2047, 2048)] == [0, 3, 0]
+        assert [int(m[i, 1, 1] & 3) for i in (2046, 2047, 2048, 2049)] == [3, 2, 0, 0]          # a dropped carry sets 2048 … of Vx
+        assert [int(m[i, 2, 1] & 3) for i in (2047, 2048, 2100, 2101)] == [0, 3, 2, 0]
+        assert (m[2047] != m[2048]).any()
+
+
 # ---- ns3d_set_solid --------------------------------------------------------------------------------------------------------------------
 def _cyl(script, nx):
     from navierstokes3d_amd.params import gpu_params, multi_params
@@ -219,6 +255,38 @@ def test_set_solid_hostile_mask_in_a_guarded_arena(hip, ctxs, dt, n):
         assert np.array_equal(ar.get("mask"), mask)
 
 
+@pytest.mark.parametrize("n", [(3, 3, 3), (5, 4, 3), (4, 4, 4)], ids=GID)
+@pytest.mark.parametrize("dt", DTS)
+def test_set_solid_at_every_lead(hip, ctxs, dt, n):
+    """k_set_solid shifts its 16-byte chunks by lead = address mod 16 and loads the first and the last chunk byte by byte: the mask at
+    byte offsets 0…15 of a larger tensor, N = 64, 120 and 125 bytes (N mod 16 = 0, 8, 13), a random hostile mask.  The four arrays
+    equal the statement's, and the bytes around the mask — all bits set: read as flags they would store — are unchanged."""
+    nx, ny, nz = n
+    N = (nx + 1) * (ny + 1) * (nz + 1)
+    assert N in (64, 120, 125)
+    host = fields(*n, ["c", "vx", "vy", "vz"], 9, NP[dt])
+    rng = np.random.Generator(np.random.MT19937(6))
+    ctx = ctxs["strict"]
+    for lead in range(16):
+        mask = np.asfortranarray(rng.integers(0, 256, (nx + 1, ny + 1, nz + 1)).astype(np.uint8))
+        big = np.full(N + 64, 0xFF, dtype=np.uint8)
+        big[16 + lead:16 + lead + N] = mask.reshape(-1, order="F")
+        dbig = torch.from_numpy(big).cuda()
+        assert dbig.data_ptr() % 16 == 0
+        view = dbig[16 + lead:16 + lead + N]
+        assert view.data_ptr() % 16 == lead
+        dev = [hip.from_numpy(h) for h in host]
+        torch.cuda.synchronize()
+        hip.set_solid(*dev, view, ctx=ctx)
+        ctx.sync()
+        ref = [h.copy() for h in host]
+        SR.set_solid(*ref, mask)
+        for name, d, r, h in zip(("C", "Vx", "Vy", "Vz"), dev, ref, host):
+            assert np.array_equal(hip.to_numpy(d), r), (lead, name, np.argwhere(hip.to_numpy(d) != r)[:4].tolist())
+            assert not np.array_equal(r, h)
+        assert np.array_equal(dbig.cpu().numpy(), big), lead
+
+
 # ---- ns3d_solid_momentum ---------------------------------------------------------------------------------------------------------------
 def _within_bound(got, terms):
     """the any-order summation bound n·2⁻⁵³·Σ|term| around math.fsum of the same terms"""
@@ -252,6 +320,48 @@ def test_solid_momentum_counts_and_sums(hip, ctxs, dt, n):
     mom, cnt = hip.solid_momentum(ar["Vx"], ar["Vy"], ar["Vz"], ar["mask"], ctx=ctxs["strict"])      # NULL seam arrays: no seams
     assert list(cnt) == [t.size for t in SR.momentum_terms(Vx, Vy, Vz, mask)]
     ar.assert_clean("solid_momentum")
+
+
+def diag_geometry(nx, ny, nz):
+    """(planes per workgroup kz, per-workgroup partials) of ns3d_solid_momentum and ns3d_diagnostics: ns3d_diag_geometry's formula
+    (csrc/ns3d_launch.h) restated — 64×4 columns per workgroup over (nx+1)×(ny+1), kz = 32 halved down to 8 while the launch has fewer
+    than 2 048 workgroups"""
+    gx, gy = (nx + 1 + 63) // 64, (ny + 1 + 3) // 4
+    kz = 32
+    while kz > 8 and gx * gy * ((nz + 1 + kz - 1) // kz) < 2048:
+        kz //= 2
+    return kz, gx * gy * ((nz + 1 + kz - 1) // kz)
+
+
+REDUCTION_GRIDS = [((3, 255, 63), 8, 512), ((3, 1023, 127), 16, 2048), ((3, 2047, 127), 32, 2048)]
+
+
+@pytest.mark.parametrize("n,kz,partials", REDUCTION_GRIDS, ids=[GID(n) for n, _, _ in REDUCTION_GRIDS])
+@pytest.mark.parametrize("dt", DTS)
+def test_solid_momentum_over_more_than_256_partials(hip, ctxs, dt, n, kz, partials):
+    """k_mom_final's thread t combines the partials t, t + 256, …: the grids of the other tests leave at most 6, so the second trip of
+    that loop never ran.  Here 512 and 2 048 partials, and kz = 8, 16 and 32 planes per workgroup; a random hostile mask; the counts
+    exact, the sums within the any-order bound, with no seams and with all six."""
+    from navierstokes3d_amd import diag as D
+    assert diag_geometry(*n) == (kz, partials) and D.launch_geometry(*n) == (partials, kz) and partials > 256
+    nx, ny, nz = n
+    Vx, Vy, Vz = fields(*n, ["vx", "vy", "vz"], 17, NP[dt])
+    rng = np.random.Generator(np.random.MT19937(8))
+    mask = np.asfortranarray(rng.integers(0, 256, (nx + 1, ny + 1, nz + 1)).astype(np.uint8))
+    d = [hip.from_numpy(a) for a in (Vx, Vy, Vz)]
+    dm = torch.from_numpy(np.ascontiguousarray(mask.reshape(-1, order="F"))).cuda()
+    torch.cuda.synchronize()
+    for lo, hi in (((0, 0, 0), (0, 0, 0)), ((1, 1, 1), (1, 1, 1))):
+        terms = SR.momentum_terms(Vx, Vy, Vz, mask, lo, hi)
+        first = None
+        for name, ctx in ctxs.items():
+            mom, cnt = hip.solid_momentum(*d, dm, lo, hi, ctx=ctx)
+            assert list(cnt) == [t.size for t in terms] and min(cnt) > 256, (lo, hi, name, cnt)
+            for q in range(3):
+                ok, fig = _within_bound(mom[q], terms[q])
+                assert ok, (lo, hi, name, q, fig)
+            first = first or mom
+            assert np.array_equal(np.array(mom), np.array(first)), "the sums depend on the context or the call"
 
 
 @pytest.mark.parametrize("script", ["multi", "gpu"])

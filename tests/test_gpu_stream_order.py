@@ -449,10 +449,13 @@ def test_shared_read_backs(hip, delay, dt, kind):
 
 
 # ---- 5b. a whole time step in one call ------------------------------------------------------------------------------------------------
-def _step_case(script, pressure, advection="reference"):
+def _step_case(script, pressure, advection="reference", obstacle=False):
     """two ns3d_time_step calls from the driver's own initial state at 24×15×15 (tests/test_gpu_footprint.py::_two_steps_on), fp64;
     the decoy is a gentle flow (magnitude 1e-2), so that a step taken on it stays finite.  advection="maccormack": the knob on (on
-    every context the case runs on) and faithful = 0; the second step's stage 1 refills the hat scratch the first step's stage 2 read"""
+    every context the case runs on) and faithful = 0; the second step's stage 1 refills the hat scratch the first step's stage 2 read.
+    obstacle: the scenario of tests/solid_step_cases.py instead — its state, its body's mask as one more late input (ns3d_set_solid
+    before multi.jl's loop, ns3d_set_obstacle for the steps, the knob put back behind them), 3·nchk iterations, faithful = 0; the
+    mask's decoy holds C bits only, so the decoy run masks no velocity"""
     from navierstokes3d_amd import driver as Dr, lib as L
     from navierstokes3d_amd.params import gpu_params, multi_params
     from test_gpu_footprint import STEP_SHAPES
@@ -466,38 +469,62 @@ def _step_case(script, pressure, advection="reference"):
     else:
         Vx0, Pr0 = Dr.gpu_initial_fields(p)
         host["Vx"], host["Pr"] = np.asfortranarray(Vx0), np.asfortranarray(Pr0)
+    extra = []
+    if obstacle:
+        import solid_step_cases as SS
+        sc = SS.scenario(script, "f64")
+        for k, a in sc.initial.items():
+            host[k] = np.asfortranarray(a.copy())
+        extra = [("mask", np.asfortranarray(sc.mask), "state")]
     common = dict(nx=p.nx, ny=p.ny, nz=p.nz, mu=p.mu, rho=p.rho, g=p.g, dt=p.dt, dtau=p.dtau, damp=p.damp, dx=p.dx, dy=p.dy, dz=p.dz,
-                  eps=p.eps, niter=p.niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2, ox=p.ox, oy=p.oy,
-                  sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz, faithful=0 if advection == "maccormack" else 1, pressure=pressure,
-                  write_stress=0)
+                  eps=p.eps, niter=sc.niter if obstacle else p.niter, nchk=p.nchk, err_mul=p.ly * p.ly, err_div=p.psc, a2=p.a2, b2=p.b2,
+                  ox=p.ox, oy=p.oy, sinb=p.sinb, cosb=p.cosb, lx=p.lx, ly=p.ly, lz=p.lz,
+                  faithful=0 if advection == "maccormack" or obstacle else 1, pressure=pressure, write_stress=0)
 
     def call(hip, ctx, t):
-        assert ctx.advection() == advection
+        if not obstacle:
+            return steps(hip, ctx, t)
+        try:
+            return steps(hip, ctx, t)
+        finally:
+            ctx.set_obstacle(None)          # the knob never outlives the case's mask
+
+    def steps(hip, ctx, t):
+        assert ctx.advection() == advection and ctx.obstacle() is None
+        t = dict(t)
+        mask = t.pop("mask", None)
         f = SimpleNamespace(**t)
         if script == "multi":
-            hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly, p.lz,
-                             p.dx, p.dy, p.dz, ctx=ctx)
+            if obstacle:
+                hip.set_solid(f.C, f.Vx, f.Vy, f.Vz, mask, ctx=ctx)
+            else:
+                hip.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.xco_g, p.yco_g, p.zco_g, p.lx, p.ly,
+                                 p.lz, p.dx, p.dy, p.dz, ctx=ctx)
             sp = L.StepParams(script=L.NS3D_BC_MULTI, xco_g=p.xco_g, yco_g=p.yco_g, zco_g=p.zco_g, owns_inlet=int(bool(p.owns_inlet)),
                               owns_outlet=int(bool(p.owns_outlet)), vin=p.vin, **common)
         else:
             sp = L.StepParams(script=L.NS3D_BC_GPU, xco_g=0.0, yco_g=0.0, zco_g=0.0, owns_inlet=0, owns_outlet=0, vin=0.0, **common)
+        if obstacle:
+            ctx.set_obstacle(mask)
         out = []
         for step in (1, 2):
             sp.write_stress = 1 if step == 2 else 0
             out.append(hip.time_step(f, sp, ctx=ctx))
         return out
-    return SO.Case("time_step %s pressure %d%s" % (script, pressure, "" if advection == "reference" else " " + advection),
-                   [(k, a, ("field", 1e-2)) for k, a in host.items()], call, blocking=True, setup=lambda ctx: ctx.set_advection(advection))
+    return SO.Case("time_step %s pressure %d%s%s" % (script, pressure, "" if advection == "reference" else " " + advection,
+                                                     " obstacle" if obstacle else ""),
+                   [(k, a, ("field", 1e-2)) for k, a in host.items()] + extra, call, blocking=True,
+                   setup=lambda ctx: ctx.set_advection(advection))
 
 
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("pressure", [0, 1])
 @pytest.mark.parametrize("script", ["multi", "gpu"])
-def test_time_step(hip, delay, script, pressure, kind, advection="reference"):
+def test_time_step(hip, delay, script, pressure, kind, advection="reference", obstacle=False):
     """Two steps, every array of ns3d_step_fields (the arrays are compared by buffer: the step swaps roles, the same way in every
     run), iteration counts and residual histories.  pressure 1 reads its one residual back through the shared key word behind the
     rest of the step; the second step's start must not disturb it."""
-    case = _step_case(script, pressure, advection)
+    case = _step_case(script, pressure, advection, obstacle)
     (want_r, want), _ = SO.expected(hip, case)
     assert all(len(errs) > 0 for _, errs in want_r) and (pressure == 1 or all(it > 0 for it, _ in want_r)), want_r
     assert all(np.isfinite(a).all() for a in want.values()) and np.abs(want["Pr"]).max() > 0
@@ -514,6 +541,28 @@ def test_time_step_maccormack(hip, delay, script, pressure, kind):
     (_, mc), _ = SO.expected(hip, _step_case(script, pressure, "maccormack"))
     (_, ref), _ = SO.expected(hip, _step_case(script, pressure))
     assert not np.array_equal(mc["Vx"], ref["Vx"])
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("pressure", [0, 1])
+@pytest.mark.parametrize("script", ["multi", "gpu"])
+def test_time_step_obstacle(hip, oracle, delay, script, pressure, kind):
+    """test_time_step with ns3d_set_obstacle: the mask is one more late input — of ns3d_set_solid before multi.jl's loop and of both
+    maskings of each step — and its bytes come back unchanged (a test of its own: the existing cases keep their names).  With the PT
+    solve the expected bits are the oracle driver's with obstacle=; a step that read the decoy's mask cannot return them."""
+    import solid_step_cases as SS
+    test_time_step(hip, delay, script, pressure, kind, obstacle=True)
+    case = _step_case(script, pressure, obstacle=True)
+    (want_r, want), (_, dec) = SO.expected(hip, case)
+    assert np.array_equal(want["mask"], SS.body_mask()) and not np.array_equal(dec["Vx"], want["Vx"])
+    if pressure == 0:
+        ref, info = SS.scenario_ref(script, "f64")
+        assert [it for it, _ in want_r] == info.iters and all(np.array_equal(np.float64(a[1]), np.float64(b)) for a, b in zip(want_r, info.errs))
+        for k in ("Pr", "dPrdtau", "divV"):
+            assert np.array_equal(want[k], ref[k]), k
+        # the step swaps roles: after two steps every swapped name is back on its own buffer
+        for k in ("C", "Vx", "Vy", "Vz", "C_o", "Vx_o", "Vy_o", "Vz_o"):
+            assert np.array_equal(want[k], ref[k]), k
 
 
 # ---- 5c. the lazy paths INSIDE the window: a cold context, nothing warmed up on it ----------------------------------------------------------
