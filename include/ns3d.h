@@ -207,6 +207,21 @@ int ns3d_advection(const ns3d_ctx *ctx);
  * the setting (NULL for a null context).  Nothing else reads the knob: the single calls are what their names say. */
 int ns3d_set_obstacle(ns3d_ctx *ctx, const unsigned char *mask);
 const unsigned char *ns3d_obstacle(const ns3d_ctx *ctx);
+/* The subgrid-scale model of ns3d_time_step's predictor (outside parity with the reference, like the two knobs above).
+ * NS3D_TURB_NONE (the default): the step's first two statements are update_τ! (if write_stress) and ns3d_predict_fused with the scalar
+ * μ of ns3d_step_params — not one extra call.  NS3D_TURB_SMAGORINSKY: they are replaced, through the public entry points, by
+ *   ns3d_eddy_viscosity into mu_e, with μ, ρ and the spacings of ns3d_step_params and this `length` (ℓ = C_s·Δ; a caller forms it as
+ *   C_s·(dx·dy·dz)^(1/3));  ns3d_update_tau_var if write_stress;  ns3d_predict_var.
+ * mu_e is CALLER-OWNED device memory of nx·ny·nz elements of the element type the step is called with; the caller keeps it alive, and
+ * may read it after the step (it then holds the field the step's predictor used).  The context keeps no scratch for it and there is no
+ * accessor.  NS3D_TURB_NONE ignores `length` and `mu_e` and clears the setting.  The step runs on ONE rank: the boundary layer of
+ * cells where the model is off would sit at the seams of a decomposed grid.  ns3d_turbulence returns the model (-1 for a null context).
+ * Nothing else reads the knob: the single calls are what their names say.
+ * NS3D_ERR_ARG, the setting unchanged: a null context, an unknown model, a length that is negative or not finite, a null mu_e with a
+ * model. */
+enum { NS3D_TURB_NONE = 0, NS3D_TURB_SMAGORINSKY = 1 };
+int ns3d_set_turbulence(ns3d_ctx *ctx, int model, double length, void *mu_e);
+int ns3d_turbulence(const ns3d_ctx *ctx);
 
 /* Parameters of the fused pseudo-transient path (ns3d_pt_iterate / ns3d_pt_solve). */
 typedef struct ns3d_pt_params {
@@ -541,6 +556,43 @@ int ns3d_voxelize(ns3d_ctx *, unsigned char *mask, const double *tri, long long 
     int ns3d_predict_fused_##S(ns3d_ctx *, T *Vx_new, T *Vy_new, T *Vz_new, const T *Vx, const T *Vy, const T *Vz,          \
                                double mu, double rho, double g, double dt, double dx, double dy, double dz, int nx, int ny,  \
                                int nz);                                                                      \
+    /* Smagorinsky's effective viscosity (outside parity): mu_e = μ + ρ·ℓ²·|S|, |S| = √(2 S_ij S_ij), a cell-centred (nx,ny,nz) field \
+     * of the element type formed in ONE pass over Vx, Vy, Vz.  `length` is ℓ = C_s·Δ, formed by the caller: no cube root runs on the \
+     * device.  The velocity gradient at the cell centre is EXACTLY ns3d_vortex's (above): its diagonal update_∇V!'s terms, its        \
+     * off-diagonal entries central differences of the cell-centred averages — |S| and the Q field a user plots agree about what the  \
+     * gradient is.  All arithmetic in T: h = (T)0.5, two = (T)2, muT = (T)mu, c = (T)(rho·length·length) (the product in double, one  \
+     * conversion), dx, dy, dz converted to T on entry.  As NumPy, with I = [1:-1,1:-1,1:-1]:                                          \
+     *   u, v, w, gxx, gyy, gzz, uy, uz, vx, vz, wx, wy      as in ns3d_vortex's NumPy statement, verbatim                             \
+     *   a = uy + vx;  b = uz + wx;  cc = vz + wy                                                                                      \
+     *   s2 = (two*((gxx*gxx + gyy*gyy) + gzz*gzz)) + ((a*a + b*b) + cc*cc)                                                            \
+     *   mu_e[...] = muT;   mu_e[I] = muT + c*sqrt(s2)                                                                                 \
+     * Interior cells receive this value, EVERY other cell muT exactly — the model is off in the boundary layer of cells, whose stencil \
+     * would leave the arrays; one call writes mu_e completely.  STRICT returns the bits of that statement (float64 and float32, no    \
+     * contraction, whichever of the three division builds the spacings select; NS3D_IEEE_DIV is honoured) with the correctly rounded   \
+     * square root of the element type, which is what np.sqrt is.  FAST multiplies by reciprocals and may contract.  length == 0 gives \
+     * muT in every cell whose s2 is finite; a non-finite s2 propagates as NaN or Inf.  Enqueued on the context's stream, no read-back. \
+     * NS3D_ERR_ARG, with nothing written: a null context or pointer; a grid below 3×3×3; a spacing that is not finite or not > 0; mu, \
+     * rho or length not finite or negative; mu_e overlapping an input. */                                                             \
+    int ns3d_eddy_viscosity_##S(ns3d_ctx *, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length, \
+                                double dx, double dy, double dz, int nx, int ny, int nz);                    \
+    /* update_τ! with the scalar μ replaced by the field mu_e ((nx,ny,nz), e.g. ns3d_eddy_viscosity's).  Normal stresses use the cell's \
+     * own value, (two*mu_e)*(…): update_τ!'s expression tree with 2μ read per cell.  Shear stresses use the mean of the four cells    \
+     * around the edge; with q = (T)0.25, m = mu_e, for the (nx-1,ny-1,nz-1) shear arrays:                                             \
+     *   mxy = q*((m[0:nx-1,0:ny-1,1:nz] + m[1:nx,0:ny-1,1:nz]) + (m[0:nx-1,1:ny,1:nz] + m[1:nx,1:ny,1:nz]))                          \
+     *   mxz = q*((m[0:nx-1,1:ny,0:nz-1] + m[1:nx,1:ny,0:nz-1]) + (m[0:nx-1,1:ny,1:nz] + m[1:nx,1:ny,1:nz]))                          \
+     *   myz = q*((m[1:nx,0:ny-1,0:nz-1] + m[1:nx,1:ny,0:nz-1]) + (m[1:nx,0:ny-1,1:nz] + m[1:nx,1:ny,1:nz]))                          \
+     *   τxy = mxy*(d_yi(Vx)/dy + d_xi(Vy)/dx)   τxz = mxz*(d_zi(Vx)/dz + d_xi(Vz)/dx)   τyz = myz*(d_zi(Vy)/dz + d_yi(Vz)/dy)         \
+     * A uniform mu_e returns the bits of ns3d_update_tau with that μ (q*((m+m)+(m+m)) is exact).  STRICT: the bits of this statement; \
+     * FAST: reciprocals, every product rounded on its own (so that the fused form below can match it).  NS3D_ERR_ARG: a null context  \
+     * or pointer, a grid below 2×2×2. */                                                                                              \
+    int ns3d_update_tau_var_##S(ns3d_ctx *, T *txx, T *tyy, T *tzz, T *txy, T *txz, T *tyz, const T *Vx, const T *Vy, const T *Vz, \
+                                const T *mu_e, double dx, double dy, double dz, int nx, int ny, int nz);     \
+    /* {ns3d_update_tau_var; predict_V!} in one pass, with ns3d_predict_fused's contract: reads Vx, Vy, Vz and mu_e, writes COMPLETE    \
+     * predicted fields into Vx_new, Vy_new, Vz_new (buffers of their own), the caller swaps the names, the stresses are not stored.  \
+     * Bit for bit what those two calls leave in Vx, Vy, Vz, in every arithmetic mode.  NS3D_ERR_ARG, with nothing written: a null     \
+     * context or pointer, a grid below 2×2×2, an output that is its own input. */                                                     \
+    int ns3d_predict_var_##S(ns3d_ctx *, T *Vx_new, T *Vy_new, T *Vz_new, const T *Vx, const T *Vy, const T *Vz, const T *mu_e, \
+                             double rho, double g, double dt, double dx, double dy, double dz, int nx, int ny, int nz); \
     /* set_cylinder!(C,Vx,Vy,Vz,a2,b2,ox,oy,sinβ,cosβ,xco_g,yco_g,zco_g,lx,ly,lz,dx,dy,dz) multi.jl:249-281 */\
     int ns3d_set_cylinder_##S(ns3d_ctx *, T *C, T *Vx, T *Vy, T *Vz, double a2, double b2, double ox,        \
                               double oy, double sinb, double cosb, double xco_g, double yco_g, double zco_g, \

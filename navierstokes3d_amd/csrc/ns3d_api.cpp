@@ -326,6 +326,23 @@ int ns3d_set_obstacle(ns3d_ctx *c, const unsigned char *mask)
 }
 const unsigned char *ns3d_obstacle(const ns3d_ctx *c) { return c ? c->obstacle : nullptr; }
 
+int ns3d_set_turbulence(ns3d_ctx *c, int model, double length, void *mu_e)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_turbulence: null context");
+    if (model == NS3D_TURB_NONE) {
+        c->turbulence = NS3D_TURB_NONE; c->turb_length = 0.0; c->turb_mu_e = nullptr;
+        return NS3D_OK;
+    }
+    if (model != NS3D_TURB_SMAGORINSKY)
+        return fail(NS3D_ERR_ARG, "ns3d_set_turbulence: model %d (NS3D_TURB_NONE | NS3D_TURB_SMAGORINSKY)", model);
+    if (!(std::isfinite(length) && length >= 0.0))
+        return fail(NS3D_ERR_ARG, "ns3d_set_turbulence: length = %g (need a finite value >= 0)", length);
+    if (!mu_e) return fail(NS3D_ERR_ARG, "ns3d_set_turbulence: a model needs the mu_e array");
+    c->turbulence = model; c->turb_length = length; c->turb_mu_e = mu_e;
+    return NS3D_OK;
+}
+int ns3d_turbulence(const ns3d_ctx *c) { return c ? c->turbulence : -1; }
+
 int ns3d_set_pt2_variant(ns3d_ctx *c, int v)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_pt2_variant: null context");

@@ -130,6 +130,43 @@ extern "C" int NS3D_FN(vortex)(ns3d_ctx *c, T *Wx, T *Wy, T *Wz, T *Q, const T *
         return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (need finite values > 0)", __func__, dx, dy, dz);
     return finish(c, DISPATCHG(c, dx, dy, dz, vortex<T>(c->stream, Wx, Wy, Wz, Q, Vx, Vy, Vz, dx, dy, dz, nx, ny, nz)), "vortex");
 }
+// ns3d_eddy_viscosity / ns3d_update_tau_var / ns3d_predict_var: the Smagorinsky model and the predictor under a viscosity field
+static bool overlaps(const void *a, size_t na, const void *b, size_t nb)
+{
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p < q + nb && q < p + na;
+}
+extern "C" int NS3D_FN(eddy_viscosity)(ns3d_ctx *c, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length,
+                                       double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(mu_e, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 3);
+    if (!(std::isfinite(dx) && std::isfinite(dy) && std::isfinite(dz) && dx > 0.0 && dy > 0.0 && dz > 0.0))
+        return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (need finite values > 0)", __func__, dx, dy, dz);
+    if (!(std::isfinite(mu) && std::isfinite(rho) && std::isfinite(length) && mu >= 0.0 && rho >= 0.0 && length >= 0.0))
+        return fail(NS3D_ERR_ARG, "%s: mu = %g, rho = %g, length = %g (need finite values >= 0)", __func__, mu, rho, length);
+    const size_t cells = (size_t)nx * ny * nz * sizeof(T);
+    if (overlaps(mu_e, cells, Vx, cells + (size_t)ny * nz * sizeof(T)) || overlaps(mu_e, cells, Vy, cells + (size_t)nx * nz * sizeof(T)) ||
+        overlaps(mu_e, cells, Vz, cells + (size_t)nx * ny * sizeof(T)))
+        return fail(NS3D_ERR_ARG, "%s: mu_e must not alias a velocity array", __func__);
+    return finish(c, DISPATCHG(c, dx, dy, dz, eddy_viscosity<T>(c->stream, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz)),
+                  "eddy_viscosity");
+}
+extern "C" int NS3D_FN(update_tau_var)(ns3d_ctx *c, T *txx, T *tyy, T *tzz, T *txy, T *txz, T *tyz, const T *Vx, const T *Vy, const T *Vz,
+                                       const T *mu_e, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu_e); CHECK_GRID(nx, ny, nz, 2);
+    return finish(c, DISPATCHG(c, dx, dy, dz, update_tau_var<T>(c->stream, txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu_e, dx, dy, dz, nx, ny, nz)),
+                  "update_tau_var");
+}
+extern "C" int NS3D_FN(predict_var)(ns3d_ctx *c, T *Vx_new, T *Vy_new, T *Vz_new, const T *Vx, const T *Vy, const T *Vz, const T *mu_e,
+                                    double rho, double g, double dt, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu_e); CHECK_GRID(nx, ny, nz, 2);
+    if (Vx_new == Vx || Vy_new == Vy || Vz_new == Vz)
+        return fail(NS3D_ERR_ARG, "%s: the predicted velocities need buffers of their own", __func__);
+    return finish(c, DISPATCHG(c, dx, dy, dz, predict_var<T>(c->stream, Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu_e, rho, g, dt, dx, dy, dz, nx, ny, nz)),
+                  "predict_var");
+}
 // ns3d_sample / ns3d_tracers_advance: one kernel build for every arithmetic mode (ns3d_tracers.hip), hence no DISPATCH
 static int tracers_count_check(long n, const char *fn)
 {
@@ -473,10 +510,18 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
                                                  p->dy, p->dz, nx, ny, nz);
     };
     do {
-        if (p->write_stress && (rc = NS3D_FN(update_tau)(c, (T *)f->txx, (T *)f->tyy, (T *)f->tzz, (T *)f->txy, (T *)f->txz, (T *)f->tyz, Vx, Vy,
-                                                         Vz, p->mu, p->dx, p->dy, p->dz, nx, ny, nz))) break;
-        // :449-451 / :121-122 in one pass; the predicted fields land in the *_o buffers and the names swap
-        if ((rc = NS3D_FN(predict_fused)(c, Vxo, Vyo, Vzo, Vx, Vy, Vz, p->mu, p->rho, p->g, p->dt, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+        if (c->turbulence != NS3D_TURB_NONE) {  // ns3d_set_turbulence: μ_e into the caller's array, then the same two statements under it
+            T *mu_e = (T *)c->turb_mu_e;
+            if ((rc = NS3D_FN(eddy_viscosity)(c, mu_e, Vx, Vy, Vz, p->mu, p->rho, c->turb_length, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+            if (p->write_stress && (rc = NS3D_FN(update_tau_var)(c, (T *)f->txx, (T *)f->tyy, (T *)f->tzz, (T *)f->txy, (T *)f->txz,
+                                                                 (T *)f->tyz, Vx, Vy, Vz, mu_e, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+            if ((rc = NS3D_FN(predict_var)(c, Vxo, Vyo, Vzo, Vx, Vy, Vz, mu_e, p->rho, p->g, p->dt, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+        } else {
+            if (p->write_stress && (rc = NS3D_FN(update_tau)(c, (T *)f->txx, (T *)f->tyy, (T *)f->tzz, (T *)f->txy, (T *)f->txz, (T *)f->tyz, Vx,
+                                                             Vy, Vz, p->mu, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+            // :449-451 / :121-122 in one pass; the predicted fields land in the *_o buffers and the names swap
+            if ((rc = NS3D_FN(predict_fused)(c, Vxo, Vyo, Vzo, Vx, Vy, Vz, p->mu, p->rho, p->g, p->dt, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+        }
         std::swap(Vx, Vxo); std::swap(Vy, Vyo); std::swap(Vz, Vzo);
         if ((rc = cylinder())) break;                                                                               // :452 / :123
         if ((rc = NS3D_FN(update_divV)(c, divV, Vx, Vy, Vz, p->dx, p->dy, p->dz, nx, ny, nz))) break;               // :454 / :124

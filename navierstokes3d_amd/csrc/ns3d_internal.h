@@ -77,6 +77,9 @@ struct ns3d_ctx {
     ns3d_scratch mc_hat;                    // ns3d_time_step under NS3D_ADVECT_MACCORMACK: stage 1's four complete fields
     ns3d_scratch solid_dev;                 // ns3d_voxelize's bit planes / ns3d_solid_momentum's partials (one stream orders both)
     const unsigned char *obstacle = nullptr; // ns3d_set_obstacle: the caller's mask ns3d_time_step masks with; null: the cylinder
+    int turbulence = 0;                     // ns3d_set_turbulence: the subgrid model of ns3d_time_step's predictor (NS3D_TURB_*)
+    double turb_length = 0.0;               //   its length ℓ = C_s·Δ
+    void *turb_mu_e = nullptr;              //   the caller's nx·ny·nz array the step writes μ_e to
     void clear_graphs()
     {
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.exec);

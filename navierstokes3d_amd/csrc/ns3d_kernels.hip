@@ -440,6 +440,279 @@ hipError_t predict_fused(hipStream_t s, T *Vxn, T *Vyn, T *Vzn, const T *Vx, con
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The stresses under a viscosity FIELD (ns3d_update_tau_var / ns3d_predict_var; include/ns3d.h has the statement): update_τ! with
+// the scalar μ read per cell — the cell's own value for the normal stresses, the mean of the four cells around the edge for the
+// shear stresses.  k_update_tau_var stores them, k_predict_var evaluates them from its LDS window and must leave what
+// {k_update_tau_var; k_predict_V} leave, bit for bit, in FAST too.  STRICT never contracts, so there the expressions are plain.
+// FAST contracts a product into whatever addition consumes it — and which one depends on what else uses the product, which differs
+// between the two kernels, while a stress that went through memory was rounded on its own.  Hence var_prod: in FAST every product
+// of these expressions whose consumer could be an addition is fma(a, b, nz) with nz = −0.0 handed over as a kernel ARGUMENT: the
+// product a·b rounded once, the sign of a zero included (x + −0 = x for every x), in one instruction as before — and a value the
+// compiler cannot see through (a literal −0.0 it folds back into a multiplication), so nothing contracts it further.  Both
+// kernels evaluate the stresses through the same functions below.
+// ---------------------------------------------------------------------------------------------------------
+#if NS3D_FASTMATH
+__device__ __forceinline__ double var_prod(double a, double b, double nz) { return __builtin_fma(a, b, nz); }
+__device__ __forceinline__ float var_prod(float a, float b, float nz) { return __builtin_fmaf(a, b, nz); }
+#define VDIV_X(v) var_prod((v), g.rdx, nz)
+#define VDIV_Y(v) var_prod((v), g.rdy, nz)
+#define VDIV_Z(v) var_prod((v), g.rdz, nz)
+#define VDIV_3(v) var_prod((v), (T)(1.0 / 3.0), nz)
+#else
+template <class T> __device__ __forceinline__ T var_prod(T a, T b, T) { return a * b; }
+#define VDIV_X(v) DIV_X(v)
+#define VDIV_Y(v) DIV_Y(v)
+#define VDIV_Z(v) DIV_Z(v)
+#define VDIV_3(v) DIV_3(v)
+#endif
+template <class T> struct VarNormal { T xx, yy, zz; };
+// τxx, τyy, τzz of a cell from its three face differences and its own viscosity  (multi.jl:37-39 with 2μ read per cell)
+template <class T>
+__device__ __forceinline__ VarNormal<T> var_normal(T dVx, T dVy, T dVz, T m, const Geo<T> &g, T nz)
+{
+    const T gx = VDIV_X(dVx), gy = VDIV_Y(dVy), gz = VDIV_Z(dVz);
+    const T div = (gx + gy) + gz;                           // @∇V()  multi.jl:15
+    const T two_mu = (T)2 * m, d3 = VDIV_3(div);
+    VarNormal<T> n;
+    n.xx = var_prod(two_mu, gx - d3, nz);
+    n.yy = var_prod(two_mu, gy - d3, nz);
+    n.zz = var_prod(two_mu, gz - d3, nz);
+    return n;
+}
+// the viscosity at an edge: the mean of the four cells around it, paired as the statement pairs them
+template <class T>
+__device__ __forceinline__ T var_edge_mu(T m00, T m10, T m01, T m11) { return (T)0.25 * ((m00 + m10) + (m01 + m11)); }
+// τxy = m·(d_y Vx/dy + d_x Vy/dx), τxz = m·(d_z Vx/dz + d_x Vz/dx), τyz = m·(d_z Vy/dz + d_y Vz/dy)  (multi.jl:40-42)
+template <class T> __device__ __forceinline__ T var_txy(T m, T dyVx, T dxVy, const Geo<T> &g, T nz) { return var_prod(m, VDIV_Y(dyVx) + VDIV_X(dxVy), nz); }
+template <class T> __device__ __forceinline__ T var_txz(T m, T dzVx, T dxVz, const Geo<T> &g, T nz) { return var_prod(m, VDIV_Z(dzVx) + VDIV_X(dxVz), nz); }
+template <class T> __device__ __forceinline__ T var_tyz(T m, T dzVy, T dyVz, const Geo<T> &g, T nz) { return var_prod(m, VDIV_Z(dzVy) + VDIV_Y(dyVz), nz); }
+#undef VDIV_X
+#undef VDIV_Y
+#undef VDIV_Z
+#undef VDIV_3
+#if NS3D_FASTMATH
+// k_predict_V's (a + b) + c with a = da·ra, b = db·rb, c = dc·rc, contracted the way THIS build's k_predict_V contracts it — which of
+// two products joins the sum as an fma depends on what else uses them, and k_predict_var's statements are surrounded by other code.
+// Read off k_predict_V's instructions (gfx950): fp64  fma(dc, rc, fma(da, ra, db·rb)) in all three statements;  fp32, where two of
+// the products are formed by one packed multiplication,  fma(db, rb, da·ra) + dc·rc for Vx and Vy (b_joins) and
+// fma(da, ra, db·rb) + dc·rc for Vz.  The sum then enters the velocity as fma(dt_rho, Σ, v) in both types.  A compiler that contracts
+// k_predict_V otherwise fails tests/test_gpu_les.py::test_predict_var_equals_update_tau_var_then_predict_V.
+__device__ __forceinline__ double predict_sum3(double da, double ra, double db, double rb, double dc, double rc, double, bool)
+{
+    return __builtin_fma(dc, rc, __builtin_fma(da, ra, db * rb));
+}
+__device__ __forceinline__ float predict_sum3(float da, float ra, float db, float rb, float dc, float rc, float nz, bool b_joins)
+{
+    return (b_joins ? __builtin_fmaf(db, rb, da * ra) : __builtin_fmaf(da, ra, db * rb)) + var_prod(dc, rc, nz);
+}
+__device__ __forceinline__ double predict_axpy(double a, double x, double y) { return __builtin_fma(a, x, y); }
+__device__ __forceinline__ float predict_axpy(float a, float x, float y) { return __builtin_fmaf(a, x, y); }
+#endif
+
+// k_update_tau with μ a cell-centred (nx,ny,nz) field: the unfused form, for write_stress and as k_predict_var's statement
+template <class T>
+__global__ __launch_bounds__(256) void k_update_tau_var(T *__restrict__ txx, T *__restrict__ tyy, T *__restrict__ tzz,
+                                                        T *__restrict__ txy, T *__restrict__ txz, T *__restrict__ tyz,
+                                                        const T *__restrict__ Vx, const T *__restrict__ Vy,
+                                                        const T *__restrict__ Vz, const T *__restrict__ mu_e, T negz, Geo<T> g,
+                                                        int nx, int ny, int nz)
+{
+    TID3
+    if (i >= nx || j >= ny || k >= nz) return;
+    const T dVx = Vx[IX3(i + 1, j, k, nx + 1, ny)] - Vx[IX3(i, j, k, nx + 1, ny)];
+    const T dVy = Vy[IX3(i, j + 1, k, nx, ny + 1)] - Vy[IX3(i, j, k, nx, ny + 1)];
+    const T dVz = Vz[IX3(i, j, k + 1, nx, ny)] - Vz[IX3(i, j, k, nx, ny)];
+    const idx_t c = IX3(i, j, k, nx, ny);
+    const VarNormal<T> n = var_normal(dVx, dVy, dVz, mu_e[c], g, negz);
+    txx[c] = n.xx;
+    tyy[c] = n.yy;
+    tzz[c] = n.zz;
+    if (i < nx - 1 && j < ny - 1 && k < nz - 1) {
+        const idx_t s = IX3(i, j, k, nx - 1, ny - 1);
+#define M(i_, j_, k_) mu_e[IX3((i_), (j_), (k_), nx, ny)]
+        const T m011 = M(i, j + 1, k + 1), m101 = M(i + 1, j, k + 1), m110 = M(i + 1, j + 1, k), m111 = M(i + 1, j + 1, k + 1);
+        const T mxy = var_edge_mu(M(i, j, k + 1), m101, m011, m111);
+        const T mxz = var_edge_mu(M(i, j + 1, k), m110, m011, m111);
+        const T myz = var_edge_mu(M(i + 1, j, k), m110, m101, m111);
+#undef M
+        const T vx111 = Vx[IX3(i + 1, j + 1, k + 1, nx + 1, ny)];
+        const T vy111 = Vy[IX3(i + 1, j + 1, k + 1, nx, ny + 1)];
+        const T vz111 = Vz[IX3(i + 1, j + 1, k + 1, nx, ny)];
+        txy[s] = var_txy(mxy, vx111 - Vx[IX3(i + 1, j, k + 1, nx + 1, ny)], vy111 - Vy[IX3(i, j + 1, k + 1, nx, ny + 1)], g, negz);
+        txz[s] = var_txz(mxz, vx111 - Vx[IX3(i + 1, j + 1, k, nx + 1, ny)], vz111 - Vz[IX3(i, j + 1, k + 1, nx, ny)], g, negz);
+        tyz[s] = var_tyz(myz, vy111 - Vy[IX3(i + 1, j + 1, k, nx, ny + 1)], vz111 - Vz[IX3(i + 1, j, k + 1, nx, ny)], g, negz);
+    }
+}
+template <class T>
+hipError_t update_tau_var(hipStream_t s, T *txx, T *tyy, T *tzz, T *txy, T *txz, T *tyz, const T *Vx, const T *Vy, const T *Vz,
+                          const T *mu_e, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    hipLaunchKernelGGL(k_update_tau_var<T>, grid3(nx, ny, nz, BLK3), BLK3, 0, s, txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu_e,
+                       (T)-0.0, make_geo<T>(dx, dy, dz), nx, ny, nz);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// {update_tau_var; predict_V!} in one pass: k_predict_var — k_predict_fused's z-march (same tile, same ring of planes, same carried
+// stresses, same stores) with μ_e as a FOURTH array of the LDS window: [4 arrays][NSLOT][PLANE], fp64 152 064 B of the CU's 160 KiB,
+// one workgroup per CU as k_predict_fused.  μ_e's rows have the window's stride (66 elements: a wave reads 64 consecutive ones, no
+// bank is met twice within a half-wave), its planes ride in the same slots.  Entry (p, q, r) of μ_e is cell (p, q, r), 1-based;
+// positions outside the array are clamped into it like the velocities' and reach only results that are not stored.  The stresses
+// carried from the plane below already hold their edge viscosities: nothing else travels with them.
+// ---------------------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(1024) void k_predict_var(T *__restrict__ Vxn, T *__restrict__ Vyn, T *__restrict__ Vzn,
+                                                      const T *__restrict__ Vx, const T *__restrict__ Vy,
+                                                      const T *__restrict__ Vz, const T *__restrict__ mu_e, T negz, T dt_rho,
+                                                      T rho_g, Geo<T> g, int nx, int ny, int nz, int kz)
+{
+    typedef PredWin<T> W;
+    constexpr int NA = 4;
+    extern __shared__ __align__(16) unsigned char predict_var_lds_raw[];
+    T *L = reinterpret_cast<T *>(predict_var_lds_raw);
+    const int tid = threadIdx.y * W::TX + threadIdx.x;
+    const int x0 = blockIdx.x * W::TX + 1, y0 = blockIdx.y * W::TY + 1;
+    const int zb = blockIdx.z * kz + 1, ze = min(zb + kz, nz + 1);          // planes iz ∈ [zb, ze), iz ≤ nz
+    const int ix = x0 + threadIdx.x, iy = y0 + threadIdx.y;
+    const T *const src[NA] = {Vx, Vy, Vz, mu_e};
+    const int sxs[NA] = {nx + 1, nx, nx, nx}, sys[NA] = {ny, ny + 1, ny, ny}, szs[NA] = {nz, nz, nz + 1, nz};
+    // window positions this thread fills (two per array and plane), clamped into the arrays as in k_predict_fused
+    unsigned fbase[NA][2];
+    idx_t fplane[NA];
+    int q[2];
+    bool has[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        q[h] = tid + h * 1024;
+        has[h] = q[h] < W::PLANE;
+        const int qq = has[h] ? q[h] : 0;
+        const int gi = x0 - 1 + qq % W::WX, gj = y0 - 1 + qq / W::WX;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const int ci = min(max(gi, 1), sxs[a]), cj = min(max(gj, 1), sys[a]);
+            fbase[a][h] = (unsigned)(ci - 1) + (unsigned)sxs[a] * (unsigned)(cj - 1);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < NA; ++a) fplane[a] = (idx_t)sxs[a] * sys[a];
+    auto fetch = [&](int plane, T (&v)[NA][2]) {
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const T *__restrict__ pl = src[a] + fplane[a] * (min(max(plane, 1), szs[a]) - 1);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) v[a][h] = has[h] ? pl[fbase[a][h]] : (T)0;
+        }
+    };
+    auto publish = [&](int plane, const T (&v)[NA][2]) {
+        const int slot = plane & (W::NSLOT - 1);            // plane ≥ 0
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (has[h]) L[(a * W::NSLOT + slot) * W::PLANE + q[h]] = v[a][h];
+    };
+    {
+        T v[NA][2];
+        for (int pl = zb - 1; pl <= zb + 1; ++pl) { fetch(pl, v); publish(pl, v); }
+    }
+    __syncthreads();
+    const W w{(typename W::lds_ptr)L, x0, y0};
+#define VX(i_, j_, k_) w.get(0, (i_), (j_), (k_))
+#define VY(i_, j_, k_) w.get(1, (i_), (j_), (k_))
+#define VZ(i_, j_, k_) w.get(2, (i_), (j_), (k_))
+#define ME(i_, j_, k_) w.get(3, (i_), (j_), (k_))
+    // the stresses of ns3d_update_tau_var at 1-based entry (p, q, r) of their arrays
+    auto normal_at = [&](int p, int q_, int r) {
+        return var_normal(VX(p + 1, q_, r) - VX(p, q_, r), VY(p, q_ + 1, r) - VY(p, q_, r), VZ(p, q_, r + 1) - VZ(p, q_, r), ME(p, q_, r), g, negz);
+    };
+    auto txy_at = [&](int p, int q_, int r) {
+        const T m = var_edge_mu(ME(p, q_, r + 1), ME(p + 1, q_, r + 1), ME(p, q_ + 1, r + 1), ME(p + 1, q_ + 1, r + 1));
+        return var_txy(m, VX(p + 1, q_ + 1, r + 1) - VX(p + 1, q_, r + 1), VY(p + 1, q_ + 1, r + 1) - VY(p, q_ + 1, r + 1), g, negz);
+    };
+    auto txz_at = [&](int p, int q_, int r) {
+        const T m = var_edge_mu(ME(p, q_ + 1, r), ME(p + 1, q_ + 1, r), ME(p, q_ + 1, r + 1), ME(p + 1, q_ + 1, r + 1));
+        return var_txz(m, VX(p + 1, q_ + 1, r + 1) - VX(p + 1, q_ + 1, r), VZ(p + 1, q_ + 1, r + 1) - VZ(p, q_ + 1, r + 1), g, negz);
+    };
+    auto tyz_at = [&](int p, int q_, int r) {
+        const T m = var_edge_mu(ME(p + 1, q_, r), ME(p + 1, q_ + 1, r), ME(p + 1, q_, r + 1), ME(p + 1, q_ + 1, r + 1));
+        return var_tyz(m, VY(p + 1, q_ + 1, r + 1) - VY(p + 1, q_ + 1, r), VZ(p + 1, q_ + 1, r + 1) - VZ(p + 1, q_, r + 1), g, negz);
+    };
+    const bool in = ix <= nx && iy <= ny;
+    const int cix = min(ix, nx), ciy = min(iy, ny);
+    const unsigned oVx = (unsigned)(cix - 1) + (unsigned)(nx + 1) * (unsigned)(ciy - 1), oVy = (unsigned)(cix - 1) + (unsigned)nx * (unsigned)(ciy - 1);
+    const unsigned oVz = oVy;
+    const idx_t pVx = (idx_t)(nx + 1) * ny, pVy = (idx_t)nx * (ny + 1), pVz = (idx_t)nx * ny;
+    // what the first plane of this chunk needs from the plane below it (planes zb−1 and zb are in the window)
+    T tzz_lo = normal_at(ix, iy, zb - 1).zz;
+    T txz_a_lo = txz_at(ix - 1, iy - 1, zb - 1), txz_b_lo = txz_at(ix, iy - 1, zb - 1);
+    T tyz_a_lo = tyz_at(ix - 1, iy - 1, zb - 1), tyz_b_lo = tyz_at(ix - 1, iy, zb - 1);
+    for (int iz = zb; iz < ze; ++iz) {
+        T nxt[NA][2];
+        fetch(iz + 2, nxt);                                 // in flight behind this plane's arithmetic
+        if (in) {
+            const VarNormal<T> n0 = normal_at(ix, iy, iz);
+            const T txx_w = normal_at(ix - 1, iy, iz).xx, tyy_s = normal_at(ix, iy - 1, iz).yy;
+            const T txy_a = txy_at(ix - 1, iy, iz - 1), txy_b = txy_at(ix - 1, iy - 1, iz - 1), txy_c = txy_at(ix, iy - 1, iz - 1);
+            const T txz_a = txz_at(ix - 1, iy - 1, iz), txz_b = txz_at(ix, iy - 1, iz);
+            const T tyz_a = tyz_at(ix - 1, iy - 1, iz), tyz_b = tyz_at(ix - 1, iy, iz);
+            T *__restrict__ const Vxp = Vxn + pVx * (iz - 1), *__restrict__ const Vyp = Vyn + pVy * (iz - 1), *__restrict__ const Vzp = Vzn + pVz * (iz - 1);
+            const T vx = VX(ix, iy, iz), vy = VY(ix, iy, iz), vz = VZ(ix, iy, iz);
+            T ox = vx, oy = vy, oz = vz;
+            // the three statements of k_predict_V: written as there in STRICT, contracted as there in FAST (predict_sum3)
+#if NS3D_FASTMATH
+#define PREDICT3(v_, da_, A_, db_, B_, dc_, C_, minus_, bj_) \
+    predict_axpy(dt_rho, predict_sum3((da_), g.rd##A_, (db_), g.rd##B_, (dc_), g.rd##C_, negz, bj_) minus_, (v_))
+#else
+#define PREDICT3(v_, da_, A_, db_, B_, dc_, C_, minus_, bj_) ((v_) + dt_rho * (((DIV3_##A_(da_) + DIV3_##B_(db_)) + DIV3_##C_(dc_)) minus_))
+#define DIV3_x(v) DIV_X(v)
+#define DIV3_y(v) DIV_Y(v)
+#define DIV3_z(v) DIV_Z(v)
+#endif
+            if (ix >= 2 && iy >= 2 && iy <= ny - 1 && iz >= 2 && iz <= nz - 1)           // @inn(Vx)  multi.jl:51
+                ox = PREDICT3(vx, n0.xx - txx_w, x, txy_a - txy_b, y, txz_a - txz_a_lo, z, , true);
+            if (ix >= 2 && ix <= nx - 1 && iy >= 2 && iz >= 2 && iz <= nz - 1)           // @inn(Vy)  multi.jl:52
+                oy = PREDICT3(vy, n0.yy - tyy_s, y, txy_c - txy_b, x, tyz_a - tyz_a_lo, z, , true);
+            if (ix >= 2 && ix <= nx - 1 && iy >= 2 && iy <= ny - 1 && iz >= 2)           // @inn(Vz)  multi.jl:53 (iz ≤ nz here)
+                oz = PREDICT3(vz, n0.zz - tzz_lo, z, txz_b_lo - txz_a_lo, x, tyz_b_lo - tyz_a_lo, y, - rho_g, false);
+#undef PREDICT3
+#if !NS3D_FASTMATH
+#undef DIV3_x
+#undef DIV3_y
+#undef DIV3_z
+#endif
+            Vxp[oVx] = ox; Vyp[oVy] = oy; Vzp[oVz] = oz;
+            // the far faces of the staggered arrays: never predicted, written through
+            if (ix == nx) Vxp[oVx + 1] = VX(ix + 1, iy, iz);
+            if (iy == ny) Vyp[oVy + nx] = VY(ix, iy + 1, iz);
+            if (iz == nz) (Vzp + pVz)[oVz] = VZ(ix, iy, iz + 1);
+            tzz_lo = n0.zz; txz_a_lo = txz_a; txz_b_lo = txz_b; tyz_a_lo = tyz_a; tyz_b_lo = tyz_b;
+        }
+        publish(iz + 2, nxt);
+        __syncthreads();
+    }
+#undef VX
+#undef VY
+#undef VZ
+#undef ME
+}
+template <class T>
+hipError_t predict_var(hipStream_t s, T *Vxn, T *Vyn, T *Vzn, const T *Vx, const T *Vy, const T *Vz, const T *mu_e, double rho,
+                       double gg, double dt, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    typedef PredWin<T> W;
+    const size_t lds = (size_t)4 * W::NSLOT * W::PLANE * sizeof(T);
+    hipError_t ea = hipFuncSetAttribute((const void *)k_predict_var<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return ea;
+    const T dt_rho = (T)dt / (T)rho, rho_g = (T)rho * (T)gg;
+    const int kz = window_kz(((nx + W::TX - 1) / W::TX) * ((ny + W::TY - 1) / W::TY), nz, nz >= 128 ? 64 : 32);
+    const dim3 blk(W::TX, W::TY, 1);
+    const dim3 grd((unsigned)((nx + W::TX - 1) / W::TX), (unsigned)((ny + W::TY - 1) / W::TY), (unsigned)((nz + kz - 1) / kz));
+    hipLaunchKernelGGL(k_predict_var<T>, grd, blk, lds, s, Vxn, Vyn, Vzn, Vx, Vy, Vz, mu_e, (T)-0.0, dt_rho, rho_g, make_geo<T>(dx, dy, dz), nx,
+                       ny, nz, kz);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // update_∇V!  multi.jl:61-64 / gpu.jl:194-197
 // ---------------------------------------------------------------------------------------------------------
 template <class T>
@@ -4647,6 +4920,114 @@ hipError_t vortex(hipStream_t s, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// ns3d_eddy_viscosity: μ_e = μ + c·√(2 S_ij S_ij), c = ρ·ℓ² (include/ns3d.h has the expression), all in T.  The velocity gradient
+// is ns3d_vortex's, entry for entry, and so is the kernel: k_vortex's 64×4 columns, register z-march and one-cell LDS ring with
+// one barrier per plane (see there), with ONE output.  Interior cells receive the value, every other cell μ: the boundary cells'
+// stores — full rows, planes 0 and nz−1 by the chunks that hold them — carry μ where k_vortex's carry +0.0.  The square root is the
+// element type's correctly rounded one (no fast-math flag reaches this unit in any build).
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sqrt_rn(double a) { return __builtin_sqrt(a); }
+__device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
+template <class T>
+__global__ __launch_bounds__(256) void k_eddy_visc(T *__restrict__ mu_e, const T *__restrict__ Vx, const T *__restrict__ Vy,
+                                                   const T *__restrict__ Vz, T mu, T cl, Geo<T> g, int nx, int ny, int nz, int kz)
+{
+    constexpr int TY = 4, SU = 64, SV = 66;
+    constexpr int NU = (TY + 2) * SU, NV = TY * SV, NW = (TY + 2) * SV, NB = NU + NV + NW;   // u | v | w of one buffer
+    __shared__ T lds[2 * NB];
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int i0 = blockIdx.x * 64, j0 = blockIdx.y * TY, i = i0 + tx, j = j0 + ty;
+    const int kb = blockIdx.z * kz, ke = min(kb + kz, nz);
+    const int ks = max(kb, 1), kt = min(ke, nz - 1);       // the chunk's interior planes [ks, kt)
+    const T h = (T)0.5, two = (T)2;
+    const idx_t pVx = (idx_t)(nx + 1) * ny, pVy = (idx_t)nx * (ny + 1), pC = (idx_t)nx * ny;
+    const bool live = i < nx && j < ny, inner = i >= 1 && i <= nx - 2 && j >= 1 && j <= ny - 2;
+    const idx_t oVx = (idx_t)i + (idx_t)(nx + 1) * j, oC = (idx_t)i + (idx_t)nx * j;
+
+    if (live) {         // planes 0 and nz−1: μ, by the chunks that hold them
+        if (kb == 0) mu_e[oC] = mu;
+        if (ke == nz) mu_e[oC + pC * (nz - 1)] = mu;
+    }
+    if (ks >= kt) return;       // uniform: a chunk of boundary planes only
+
+    // own column: centred u, v of planes ks−1 and ks, face differences of plane ks, Vz of planes ks and ks+1
+    T up = 0, uc = 0, vp = 0, vc = 0, dxc = 0, dyc = 0, zk = 0, zk1 = 0;
+    if (live) {
+        const T *x = Vx + oVx + pVx * (ks - 1), *y = Vy + oC + pVy * (ks - 1);
+        up = h * (x[0] + x[1]);
+        vp = h * (y[0] + y[nx]);
+        const T x0 = x[pVx], x1 = x[pVx + 1], y0 = y[pVy], y1 = y[pVy + nx];
+        uc = h * (x0 + x1); dxc = x1 - x0;
+        vc = h * (y0 + y1); dyc = y1 - y0;
+        zk = Vz[oC + pC * ks];
+        zk1 = Vz[oC + pC * (ks + 1)];
+    }
+    // the ring cell this thread stages besides its own
+    const bool ring_u = ty < 2;
+    const int ei = ring_u ? i : (ty == 2 ? i0 - 1 : i0 + 64), ej = ring_u ? (ty == 0 ? j0 - 1 : j0 + TY) : j0 + tx;
+    const bool ring = (ring_u || tx < TY) && ei >= 0 && ei < nx && ej >= 0 && ej < ny;
+    const int ring_c = ring_u ? (ty == 0 ? 0 : TY + 1) * SU + tx : NU + tx * SV + (ty == 2 ? 0 : 65);
+    const int ring_w = NU + NV + (ring_u ? (ty == 0 ? 0 : TY + 1) * SV + tx + 1 : (tx + 1) * SV + (ty == 2 ? 0 : 65));
+    const T *eV = ring_u ? Vx : Vy;
+    const idx_t eF = (idx_t)ei + (idx_t)(ring_u ? nx + 1 : nx) * ej, eC = (idx_t)ei + (idx_t)nx * ej, ePl = ring_u ? pVx : pVy;
+    const int eStep = ring_u ? 1 : nx;
+    T ec = 0, ez = 0, ez1 = 0;
+    if (ring) {
+        ec = h * (eV[eF + ePl * ks] + eV[eF + eStep + ePl * ks]);
+        ez = Vz[eC + pC * ks];
+        ez1 = Vz[eC + pC * (ks + 1)];
+    }
+
+    for (int k = ks; k < kt; ++k) {
+        const bool more = k + 1 < kt;
+        T un = 0, vn = 0, dxn = 0, dyn = 0, zk2 = 0;
+        if (live) {             // plane k+1 ≤ nz−1 of Vx, Vy; plane k+2 ≤ nz−1 of Vz
+            const T *x = Vx + oVx + pVx * (k + 1), *y = Vy + oC + pVy * (k + 1);
+            const T x0 = x[0], x1 = x[1], y0 = y[0], y1 = y[nx];
+            un = h * (x0 + x1); dxn = x1 - x0;
+            vn = h * (y0 + y1); dyn = y1 - y0;
+            if (more) zk2 = Vz[oC + pC * (k + 2)];
+        }
+        T *buf = lds + ((k - ks) & 1) * NB;
+        buf[(ty + 1) * SU + tx] = uc;
+        buf[NU + ty * SV + tx + 1] = vc;
+        buf[NU + NV + (ty + 1) * SV + tx + 1] = h * (zk + zk1);
+        if (ring) {
+            buf[ring_c] = ec;
+            buf[ring_w] = h * (ez + ez1);
+            if (more) {
+                ec = h * (eV[eF + ePl * (k + 1)] + eV[eF + eStep + ePl * (k + 1)]);
+                ez = ez1;
+                ez1 = Vz[eC + pC * (k + 2)];
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const T *sw = buf + NU + NV + (ty + 1) * SV + tx + 1;
+            const T uy = h * DIV_Y(buf[(ty + 2) * SU + tx] - buf[ty * SU + tx]), uz = h * DIV_Z(un - up);
+            const T vx = h * DIV_X(buf[NU + ty * SV + tx + 2] - buf[NU + ty * SV + tx]), vz = h * DIV_Z(vn - vp);
+            const T wx = h * DIV_X(sw[1] - sw[-1]), wy = h * DIV_Y(sw[SV] - sw[-SV]);
+            const T gxx = DIV_X(dxc), gyy = DIV_Y(dyc), gzz = DIV_Z(zk1 - zk);
+            const T a = uy + vx, b = uz + wx, cc = vz + wy;
+            const T s2 = (two * ((gxx * gxx + gyy * gyy) + gzz * gzz)) + ((a * a + b * b) + cc * cc);
+            mu_e[oC + pC * k] = inner ? mu + cl * sqrt_rn(s2) : mu;
+        }
+        up = uc; uc = un; vp = vc; vc = vn; dxc = dxn; dyc = dyn; zk = zk1; zk1 = zk2;
+    }
+}
+template <class T>
+hipError_t eddy_viscosity(hipStream_t s, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length, double dx,
+                          double dy, double dz, int nx, int ny, int nz)
+{
+    const int kz = NS3D_VORTEX_KZ;
+    const dim3 blk(64, 4, 1);
+    const dim3 grd((unsigned)((nx + 63) / 64), (unsigned)((ny + 3) / 4), (unsigned)((nz + kz - 1) / kz));
+    hipLaunchKernelGGL(k_eddy_visc<T>, grd, blk, 0, s, mu_e, Vx, Vy, Vz, (T)mu, (T)(rho * length * length), make_geo<T>(dx, dy, dz), nx,
+                       ny, nz, kz);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Self-test of div_by_known against the hardware's IEEE division: n pseudo-random dividends per launch.  The QUOTIENT's
 // binade is drawn, x = RN(q·d), so that every admitted divisor — small or large — meets the fast path, the plain division
 // and the boundary between them: half of the quotients within 2^±60 (fp32: 2^±20), one in eight over the guard's whole
@@ -4771,6 +5152,12 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
                                             int, int);                                                       \
     template hipError_t vortex<T>(hipStream_t, T *, T *, T *, T *, const T *, const T *, const T *, double, double, double, \
                                   int, int, int);                                                            \
+    template hipError_t eddy_viscosity<T>(hipStream_t, T *, const T *, const T *, const T *, double, double, double, double, double, \
+                                          double, int, int, int);                                            \
+    template hipError_t update_tau_var<T>(hipStream_t, T *, T *, T *, T *, T *, T *, const T *, const T *, const T *, const T *, \
+                                          double, double, double, int, int, int);                            \
+    template hipError_t predict_var<T>(hipStream_t, T *, T *, T *, const T *, const T *, const T *, const T *, double, double, \
+                                       double, double, double, double, int, int, int);                       \
     template hipError_t divtest<T>(hipStream_t, double, long, unsigned long long, unsigned long long *);   \
     template hipError_t strip_inner<T>(hipStream_t, const T *, T *, int, int, int);                          \
     template hipError_t face_copy<T>(hipStream_t, T *, T *, int, int, int, int, int, int);                  \

@@ -213,6 +213,16 @@ hipError_t emit(hipStream_t, const T *A, const T *B, const ns3d_iso_geom &, doub
     template <class T>                                                                                       \
     hipError_t vortex(hipStream_t, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T *Vy, const T *Vz,        \
                       double dx, double dy, double dz, int nx, int ny, int nz);                              \
+    /* Smagorinsky: mu_e = mu + rho·length²·|S| on interior cells, mu elsewhere; then the stresses and the predictor under it */ \
+    template <class T>                                                                                       \
+    hipError_t eddy_viscosity(hipStream_t, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, \
+                              double length, double dx, double dy, double dz, int nx, int ny, int nz);       \
+    template <class T>                                                                                       \
+    hipError_t update_tau_var(hipStream_t, T *, T *, T *, T *, T *, T *, const T *, const T *, const T *, const T *mu_e, \
+                              double dx, double dy, double dz, int, int, int);                               \
+    template <class T>                                                                                       \
+    hipError_t predict_var(hipStream_t, T *, T *, T *, const T *, const T *, const T *, const T *mu_e, double rho, \
+                           double g, double dt, double dx, double dy, double dz, int, int, int);             \
     template <class T>                                                                                       \
     hipError_t divtest(hipStream_t, double d, long n, unsigned long long seed, unsigned long long *bad_dev); \
     template <class T>                                                                                       \

@@ -194,7 +194,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
                        statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None, advection="reference",
-                       obstacle=None):
+                       obstacle=None, turbulence=None):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -267,8 +267,16 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     or a ready uint8 mask of (nx+1)(ny+1)(nz+1) bytes (solid.voxelize, solid.mask_of_cylinder).  With `one_call` the step masks
     inside ns3d_time_step (Context.set_obstacle), otherwise with one set_solid call where set_cylinder stands; the same bits either
     way.  With diagnostics=True, force comes from ns3d_solid_momentum taken before each of the step's two maskings.  One rank:
-    anything else raises Ns3dError before the first step."""
+    anything else raises Ns3dError before the first step.
+    turbulence=… (default None: not one extra call; OUTSIDE the reference): the subgrid-scale model of the predictor :449-451 —
+    "smagorinsky", or dict(model="smagorinsky", cs=0.17).  Each step forms the effective viscosity μ_e = μ + ρ·ℓ²·|S| with
+    ℓ = cs·(dx·dy·dz)^(1/3) (ns3d_eddy_viscosity, into an array this driver allocates) and predicts under it (ns3d_predict_var; the
+    stress arrays of the last step come from ns3d_update_tau_var) — with `one_call` inside ns3d_time_step (Context.set_turbulence),
+    otherwise as these calls; the same bits either way.  info.turbulence gets length and mu_e, the field of the last step, as a host
+    array.  With diagnostics=True every record gains mu_e_max, and a step whose dt·mu_e_max/ρ·(1/dx² + 1/dy² + 1/dz²) exceeds 1/2 —
+    the explicit diffusion limit — raises Ns3dError.  One rank: anything else raises Ns3dError before anything is allocated."""
     _check_advection(advection)
+    _check_turbulence(turbulence)
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -281,6 +289,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     check_options(grid, **watch)
     P, dims, mg, root = grid.P, tuple(grid.dims), grid.mg, grid.is_root()
     maccormack = _check_advection(advection, faithful, P)
+    les = _check_turbulence(turbulence, P)
     # the contexts of the ns3d_mgpu's ranks (their devices), or this rank's own
     ctxs = list(grid.contexts) if grid.contexts is not None else [K.Context(device, mode, async_=True)]
     ps = [multi_params(nx, dims=dims, coords=c3, **shape) for c3 in grid.local_coords]
@@ -367,6 +376,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         step_params = _step_params(L.NS3D_BC_MULTI, p, niter, faithful, pressure)
     if solid is not None and step_params is not None:
         ctxs[0].set_obstacle(solid)                             # ns3d_time_step masks with it; back to the cylinder after the loop
+    if les is not None:
+        _les_start(les, p, fs[0], ctxs[0], step_params is not None)     # ns3d_time_step predicts under it; cleared after the loop
     hats = None
     if maccormack and step_params is not None:
         ctxs[0].set_advection("maccormack")                     # ns3d_time_step advects with it; back to the default after the loop
@@ -377,7 +388,9 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             step_params.write_stress = 1 if it == nt else 0     # the stress arrays as the reference leaves them after its last step
             done, errs = K.time_step(fs[0], step_params, ctx=ctxs[0])
         else:
-            if fuse_predictor:
+            if les is not None:     # :449-451 under the Smagorinsky viscosity (one rank)
+                mu_e_max = _les_predict(fs[0], p, ctxs[0], les, fused, it == nt, monitor is not None, it)
+            elif fuse_predictor:
                 # :449-451 in one pass (ns3d_predict_fused): the stresses evaluated on the fly, the predicted fields written into the
                 # *_o buffers (free until :475), the names swapped.  :450's halo update of τxx, τyy, τzz moves values every rank has
                 # already computed itself — the velocities it computes them from are consistent across ranks after :477 / :373 —
@@ -437,6 +450,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             grid.update_halo(col("Vx"), col("Vy"), col("Vz"))                                 # :167
             if monitor:
                 info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
+                if les is not None:
+                    info.diag[-1].mu_e_max = mu_e_max
                 if wide_advect_halo and P > 1:
                     _check_wide_precondition(it, info.diag[-1].courant)
             if wide_advect_halo and P > 1:                                                    # :475-477, decomposition-independent
@@ -467,12 +482,16 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         ctxs[0].set_advection("reference")
     if solid is not None and step_params is not None:
         ctxs[0].set_obstacle(None)
+    if les is not None:
+        ctxs[0].set_turbulence(None)
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
             K.copy(f.Vz_o, f.Vz, ctx=c)     # the one copy of :475 the swaps skipped (Vz is never advected): same final state
     sync()
     out = _gather_all(grid, fs)                                                               # :528-532
     obs.finish(info, fs)
+    if les is not None:
+        info.turbulence = dict(length=les.length, mu_e=K.to_numpy(les.mu_e))
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
@@ -558,6 +577,56 @@ def _check_advection(advection, faithful=False, P=1):
     return True
 
 
+def _check_turbulence(turbulence, P=1):
+    """the `turbulence` keyword of both drivers → None, or a namespace with the model's cs; raises before anything is allocated"""
+    if turbulence is None:
+        return None
+    opts = dict(model=turbulence) if isinstance(turbulence, str) else turbulence
+    if not isinstance(opts, dict) or opts.get("model") != "smagorinsky" or set(opts) - {"model", "cs"}:
+        raise L.Ns3dError("turbulence = %r (None | \"smagorinsky\" | dict(model=\"smagorinsky\", cs=0.17))" % (turbulence,))
+    cs = float(opts.get("cs", 0.17))
+    if not (math.isfinite(cs) and cs >= 0.0):
+        raise L.Ns3dError("turbulence: cs = %r (need a finite value >= 0)" % (opts.get("cs"),))
+    if P != 1:
+        raise L.Ns3dError("turbulence=\"smagorinsky\" runs on one rank (this grid has %d): the boundary layer of cells where mu_e is the "
+                          "molecular viscosity would sit at the seams, and mu_e's halo would have to be exchanged between the eddy-viscosity "
+                          "kernel and the predictor" % P)
+    return SimpleNamespace(cs=cs)
+
+
+def _les_start(les, p, f, ctx, in_step):
+    """ℓ = cs·Δ and the μ_e array of a run; in_step: ns3d_time_step issues the calls (the context's knob), otherwise _les_predict does"""
+    les.length = les.cs * (p.dx * p.dy * p.dz) ** (1.0 / 3.0)
+    les.mu_e = K.zeros(tuple(f.Pr.shape), f.Pr.dtype, f.Pr.device)
+    ctx.after_torch_fill()
+    if in_step:
+        ctx.set_turbulence("smagorinsky", les.length, les.mu_e)
+
+
+def _les_predict(f, p, ctx, les, fused, write_stress, watch, it):
+    """{update_τ!; predict_V!} under the Smagorinsky viscosity, call by call — what ns3d_time_step issues under the knob: μ_e, the
+    stress arrays where the plain step writes them, the predictor (in one pass, names swapped, if fused).  watch: returns max μ_e
+    (the monitor's mu_e_max) and raises where the step would leave the explicit diffusion limit."""
+    K.eddy_viscosity(les.mu_e, f.Vx, f.Vy, f.Vz, p.mu, p.rho, les.length, p.dx, p.dy, p.dz, ctx=ctx)
+    mu_e_max = None
+    if watch:
+        mu_e_max = K.max_abs(les.mu_e, ctx=ctx)
+        number = p.dt * mu_e_max / p.rho * (1.0 / p.dx ** 2 + 1.0 / p.dy ** 2 + 1.0 / p.dz ** 2)
+        if not number <= 0.5:
+            raise L.Ns3dError("step %d: dt*mu_e_max/rho*(1/dx^2 + 1/dy^2 + 1/dz^2) = %r with mu_e_max = %r is not within 1/2, the explicit "
+                              "diffusion limit of the predictor; reduce dt or cs" % (it, number, mu_e_max))
+    if write_stress or not fused:
+        K.update_tau_var(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, les.mu_e, p.dx, p.dy, p.dz, ctx=ctx)
+    if not fused:
+        K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz, ctx=ctx)
+        return mu_e_max
+    K.predict_var(f.Vx_o, f.Vy_o, f.Vz_o, f.Vx, f.Vy, f.Vz, les.mu_e, p.rho, p.g, p.dt, p.dx, p.dy, p.dz, ctx=ctx)
+    f.Vx, f.Vx_o = f.Vx_o, f.Vx
+    f.Vy, f.Vy_o = f.Vy_o, f.Vy
+    f.Vz, f.Vz_o = f.Vz_o, f.Vz
+    return mu_e_max
+
+
 def _alloc_hats(f, ctx):
     """buffers for stage 1 of the MacCormack advection (Vx, Vy, Vz, C) when the step runs call by call"""
     hats = tuple(K.zeros(tuple(a.shape), a.dtype, a.device) for a in (f.Vx, f.Vy, f.Vz, f.C))
@@ -604,7 +673,7 @@ def _save_mat(path, f, p, step0):
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
           diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None,
-          advection="reference", obstacle=None):
+          advection="reference", obstacle=None, turbulence=None):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -622,8 +691,10 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     isosurface: as in run_navierstokes3D, of the final state → info.isosurface; do_save adds out_save/out_iso_%04d.ply beside each
     MAT file (numbered like the tracer dumps).
     advection: as in run_navierstokes3D, in place of :141-142; "maccormack" needs faithful=False.
-    obstacle: as in run_navierstokes3D, in place of the set_cylinder! calls :123 and :139."""
+    obstacle: as in run_navierstokes3D, in place of the set_cylinder! calls :123 and :139.
+    turbulence: as in run_navierstokes3D, in place of :121-122."""
     maccormack = _check_advection(advection, faithful)
+    les = _check_turbulence(turbulence)
     if device is None:
         device = torch.cuda.current_device()
     p = gpu_params(nx)
@@ -675,6 +746,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         step_params = _step_params(L.NS3D_BC_GPU, p, niter, faithful, pressure)
     if solid is not None and step_params is not None:
         ctx.set_obstacle(solid)                             # ns3d_time_step masks with it (the context is this run's own)
+    if les is not None:
+        _les_start(les, p, f, ctx, step_params is not None)     # ns3d_time_step predicts under it; cleared after the loop
     hats = None
     if maccormack and step_params is not None:
         ctx.set_advection("maccormack")                     # ns3d_time_step advects with it (the context is this run's own)
@@ -685,7 +758,9 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             step_params.write_stress = 1 if it == nt else 0
             done, errs = K.time_step(f, step_params, ctx=ctx)
         else:
-            if fused:
+            if les is not None:         # :121-122 under the Smagorinsky viscosity
+                mu_e_max = _les_predict(f, p, ctx, les, fused, it == nt, monitor is not None, it)
+            elif fused:
                 if it == nt:            # the stress arrays as the reference leaves them after its last step: same final state
                     K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)
                 _predict_swap(f, p, ctx)                                                      # :121-122 in one pass
@@ -722,6 +797,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             K.set_bc_Vel_gpu(f.Vx, f.Vy, f.Vz, ctx=ctx)                                       # :140
             if monitor:
                 info.diag.append(_diag_step_record(monitor(True), mom_predict, mom_correct, p))
+                if les is not None:
+                    info.diag[-1].mu_e_max = mu_e_max
             if maccormack:
                 _advect_mc_swap(f, hats, p, ctx)                                              # :141-142 as the limited MacCormack scheme
             elif fused:
@@ -740,9 +817,13 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             saved(it)
     if solid is not None and step_params is not None:
         ctx.set_obstacle(None)
+    if les is not None:
+        ctx.set_turbulence(None)
     if fused and faithful and nt > 0:
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()
     info.ctx = ctx
     obs.finish(info, [f])
+    if les is not None:
+        info.turbulence = dict(length=les.length, mu_e=K.to_numpy(les.mu_e))
     return f, info

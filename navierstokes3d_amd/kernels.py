@@ -218,6 +218,21 @@ class Context:
         """the device address ns3d_time_step masks with; None: the cylinder"""
         return self.lib.ns3d_obstacle(self.handle)
 
+    def set_turbulence(self, model, length=0.0, mu_e=None):
+        """The subgrid model of ns3d_time_step's predictor: None / "none" (the default: the scalar μ, not one extra call) or
+        "smagorinsky" with length = C_s·Δ and mu_e, a column-major (nx,ny,nz) tensor of the step's dtype that the step writes the
+        effective viscosity to (kept alive here until the setting is replaced).  The single calls do not read it."""
+        codes = {None: L.NS3D_TURB_NONE, "none": L.NS3D_TURB_NONE, "smagorinsky": L.NS3D_TURB_SMAGORINSKY}
+        if model not in codes:
+            raise L.Ns3dError("turbulence model = %r (None | \"smagorinsky\")" % (model,))
+        off = codes[model] == L.NS3D_TURB_NONE
+        ptr = None if off or mu_e is None else _chk(mu_e, None, "mu_e")
+        L.check(self.lib.ns3d_set_turbulence(self.handle, codes[model], C.c_double(float(length)), ptr))
+        self._mu_e = None if off else mu_e
+
+    def turbulence(self):
+        return {L.NS3D_TURB_NONE: None, L.NS3D_TURB_SMAGORINSKY: "smagorinsky"}[int(self.lib.ns3d_turbulence(self.handle))]
+
     def set_pt_depth(self, depth):
         """PT iterations per pass over memory in pt_iterate / pt_solve: 0 automatic, 1…4 forced (5: float32 fields only)."""
         L.check(self.lib.ns3d_set_pt_depth(self.handle, int(depth)))
@@ -301,6 +316,45 @@ def predict_fused(Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu, rho, g, dt, dx, dy, dz
     nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
     _ctx(ctx, Vx).call("predict_fused", Vx, *_chk_V(Vx_new, Vy_new, Vz_new, (nx, ny, nz), "_new"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)),
                        *_d(mu, rho, g, dt, dx, dy, dz), nx, ny, nz)
+
+
+def _chk_like(t, shape, name, ref):
+    """_chk, and the dtype and device of the velocities"""
+    p = _chk(t, shape, name)
+    if t.dtype != ref.dtype or t.device != ref.device:
+        raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, ref.dtype, ref.device))
+    return p
+
+
+def eddy_viscosity(mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, ctx=None):
+    """ns3d_eddy_viscosity: Smagorinsky's effective viscosity mu_e = μ + ρ·length²·|S| of the staggered velocity field, a cell-centred
+    (nx,ny,nz) array of the fields' dtype, in one fused pass on the device (include/ns3d.h has the expression; the gradient is
+    vortex's).  length = C_s·Δ.  Interior cells receive the value, every other cell μ.  Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    out = _chk_like(mu_e, (nx, ny, nz), "mu_e", Vx)
+    V = _chk_V(Vx, Vy, Vz, (nx, ny, nz))
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if t.dtype != Vx.dtype or t.device != Vx.device:
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("eddy_viscosity", Vx, out, *V, *_d(mu, rho, length, dx, dy, dz), nx, ny, nz)
+
+
+def update_tau_var(txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu_e, dx, dy, dz, ctx=None):
+    """ns3d_update_tau_var: update_τ! with the scalar μ replaced by the (nx,ny,nz) field mu_e — the cell's own value in the normal
+    stresses, the mean of the four cells around the edge in the shear stresses."""
+    nx, ny, nz = txx.shape
+    c = (nx, ny, nz); s = (nx - 1, ny - 1, nz - 1)
+    _ctx(ctx, txx).call("update_tau_var", txx, _chk(txx, c, "txx"), _chk(tyy, c, "tyy"), _chk(tzz, c, "tzz"),
+                        _chk(txy, s, "txy"), _chk(txz, s, "txz"), _chk(tyz, s, "tyz"), *_chk_V(Vx, Vy, Vz, c), _chk_like(mu_e, c, "mu_e", txx),
+                        *_d(dx, dy, dz), nx, ny, nz)
+
+
+def predict_var(Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu_e, rho, g, dt, dx, dy, dz, ctx=None):
+    """{update_tau_var; predict_V!} in one pass, predict_fused's contract: complete predicted fields into buffers of their own, the
+    stress arrays neither read nor written; the caller swaps the names."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    _ctx(ctx, Vx).call("predict_var", Vx, *_chk_V(Vx_new, Vy_new, Vz_new, (nx, ny, nz), "_new"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)),
+                       _chk_like(mu_e, (nx, ny, nz), "mu_e", Vx), *_d(rho, g, dt, dx, dy, dz), nx, ny, nz)
 
 
 def set_cylinder(Cf, Vx, Vy, Vz, a2, b2, ox, oy, sinb, cosb, *rest, ctx=None):

@@ -12,6 +12,7 @@ NS3D_UNIQUE_ID_BYTES = 128
 NS3D_STRICT, NS3D_FAST, NS3D_ASYNC, NS3D_IEEE_DIV = 0x0, 0x1, 0x2, 0x4
 NS3D_BC_MULTI, NS3D_BC_GPU = 0, 1
 NS3D_ADVECT_REFERENCE, NS3D_ADVECT_MACCORMACK = 0, 1
+NS3D_TURB_NONE, NS3D_TURB_SMAGORINSKY = 0, 1
 
 
 class Ns3dError(RuntimeError):
@@ -115,13 +116,18 @@ DERIVED_SIGNATURES = {
     # obstacles from a mask (ns3d_voxelize writes one), beside set_cylinder / set_cylinder_local above
     "set_solid": [_P] * 5 + [_I] * 3,
     "solid_momentum": [_P] * 4 + [_I] * 3 + [C.POINTER(_I)] * 2 + [C.POINTER(_D), C.POINTER(C.c_longlong)],
+    # the Smagorinsky model: the viscosity field, and update_tau / predict_fused under it
+    "eddy_viscosity": [_P] * 4 + [_D] * 6 + [_I] * 3,
+    "update_tau_var": [_P] * 10 + [_D] * 3 + [_I] * 3,
+    "predict_var": [_P] * 7 + [_D] * 6 + [_I] * 3,
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
                    "ns3d_set_pt2_variant", "ns3d_set_ptn_variant", "ns3d_set_pt_depth", "ns3d_set_graph_mode", "ns3d_set_autotune", "ns3d_last_pt2_variant", "ns3d_last_ptn_variant", "ns3d_last_pt_depth",
                    "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
                    "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test", "ns3d_set_advection", "ns3d_advection",
-                   "ns3d_stats_reset", "ns3d_stats_finalize", "ns3d_voxelize", "ns3d_set_obstacle", "ns3d_obstacle"]
+                   "ns3d_stats_reset", "ns3d_stats_finalize", "ns3d_voxelize", "ns3d_set_obstacle", "ns3d_obstacle",
+                   "ns3d_set_turbulence", "ns3d_turbulence"]
 NS3D_STATS_SLOTS = 11
 
 
@@ -238,6 +244,10 @@ def load():
     lib.ns3d_set_obstacle.restype = _I
     lib.ns3d_obstacle.argtypes = [_P]
     lib.ns3d_obstacle.restype = _P
+    lib.ns3d_set_turbulence.argtypes = [_P, _I, _D, _P]
+    lib.ns3d_set_turbulence.restype = _I
+    lib.ns3d_turbulence.argtypes = [_P]
+    lib.ns3d_turbulence.restype = _I
     lib.ns3d_cached_graphs.argtypes = [_P]
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
