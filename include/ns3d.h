@@ -222,6 +222,16 @@ const unsigned char *ns3d_obstacle(const ns3d_ctx *ctx);
 enum { NS3D_TURB_NONE = 0, NS3D_TURB_SMAGORINSKY = 1 };
 int ns3d_set_turbulence(ns3d_ctx *ctx, int model, double length, void *mu_e);
 int ns3d_turbulence(const ns3d_ctx *ctx);
+/* The differential operator the step forms mu_e with WHILE ns3d_set_turbulence has a model set (codes and expressions at
+ * ns3d_sgs_viscosity).  NS3D_SGS_SMAGORINSKY (the default of a fresh context): the step's first statement is the ns3d_eddy_viscosity
+ * call described above, and nothing else.  NS3D_SGS_WALE, NS3D_SGS_VREMAN: it is ns3d_sgs_viscosity with that operator and the same
+ * arguments; `length` of ns3d_set_turbulence is then C_w·Δ or √c_v·Δ.  The operator is a setting of its own, not a model code: a
+ * plain int that holds no scratch.  ns3d_set_turbulence(NS3D_TURB_NONE) does NOT touch it — the step then ignores it — and
+ * ns3d_set_turbulence with a model does not either.  ns3d_sgs_operator returns the setting (-1 for a null context).  Nothing but
+ * ns3d_time_step reads the knob.  NS3D_ERR_ARG, the setting unchanged: a null context, an unknown operator. */
+enum { NS3D_SGS_SMAGORINSKY = 0, NS3D_SGS_WALE = 1, NS3D_SGS_VREMAN = 2 };
+int ns3d_set_sgs_operator(ns3d_ctx *ctx, int op);
+int ns3d_sgs_operator(const ns3d_ctx *ctx);
 
 /* Parameters of the fused pseudo-transient path (ns3d_pt_iterate / ns3d_pt_solve). */
 typedef struct ns3d_pt_params {
@@ -575,6 +585,39 @@ int ns3d_voxelize(ns3d_ctx *, unsigned char *mask, const double *tri, long long 
      * rho or length not finite or negative; mu_e overlapping an input. */                                                             \
     int ns3d_eddy_viscosity_##S(ns3d_ctx *, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length, \
                                 double dx, double dy, double dz, int nx, int ny, int nz);                    \
+    /* ns3d_eddy_viscosity with |S| replaced by the differential operator `op` (outside parity): mu_e = muT + c*op(G) on the interior   \
+     * cells, muT exactly in the boundary layer of cells; one call writes mu_e completely, in ONE pass with the same three reads and   \
+     * one write per cell.  G is ns3d_eddy_viscosity's gradient, gxx, gyy, gzz, uy, uz, vx, vz, wx, wy, verbatim, and h, two, muT, c   \
+     * are its constants; third = (T)(1.0/3.0).  All arithmetic in T, nothing contracted in STRICT.  `length` is the caller's ℓ in      \
+     * μ_t = ρ·ℓ²·op: C_s·Δ, C_w·Δ (C_w² ≈ 10.6·C_s²) or √c_v·Δ (c_v ≈ 2.5·C_s²).                                                      \
+     * NS3D_SGS_SMAGORINSKY (0): op = sqrt(s2) with ns3d_eddy_viscosity's s2 — the call returns that call's bits.                      \
+     * NS3D_SGS_WALE (1), Nicoud & Ducros 1999: g² = G·G with G = [[gxx,uy,uz],[vx,gyy,vz],[wx,wy,gzz]], its traceless symmetric part: \
+     *   q11 = (gxx*gxx + uy*vx) + uz*wx    q12 = (gxx*uy + uy*gyy) + uz*wy    q13 = (gxx*uz + uy*vz) + uz*gzz                          \
+     *   q21 = (vx*gxx + gyy*vx) + vz*wx    q22 = (vx*uy + gyy*gyy) + vz*wy    q23 = (vx*uz + gyy*vz) + vz*gzz                          \
+     *   q31 = (wx*gxx + wy*vx) + gzz*wx    q32 = (wx*uy + wy*gyy) + gzz*wy    q33 = (wx*uz + wy*vz) + gzz*gzz                          \
+     *   t = third*((q11 + q22) + q33);  d11 = q11 - t;  d22 = q22 - t;  d33 = q33 - t                                                 \
+     *   d12 = h*(q12 + q21);  d13 = h*(q13 + q31);  d23 = h*(q23 + q32)                                                               \
+     *   dd = ((d11*d11 + d22*d22) + d33*d33) + two*((d12*d12 + d13*d13) + d23*d23)                                                    \
+     *   ss = h*s2                                                                                                                     \
+     *   num = dd*sqrt(dd);   den = (ss*ss)*sqrt(ss) + dd*sqrt(sqrt(dd))                                                               \
+     *   op = (den == 0) ? 0 : num/den          the plain IEEE quotient; a NaN den is not == 0 and propagates                          \
+     * NS3D_SGS_VREMAN (2), Vreman 2004, with the isotropic filter width: β = G·Gᵀ,                                                     \
+     *   b11 = (gxx*gxx + uy*uy) + uz*uz    b22 = (vx*vx + gyy*gyy) + vz*vz    b33 = (wx*wx + wy*wy) + gzz*gzz                          \
+     *   b12 = (gxx*vx + uy*gyy) + uz*vz    b13 = (gxx*wx + uy*wy) + uz*gzz    b23 = (vx*wx + gyy*wy) + vz*gzz                          \
+     *   aa = (b11 + b22) + b33                                                                                                        \
+     *   B  = ((b11*b22 - b12*b12) + (b11*b33 - b13*b13)) + (b22*b33 - b23*b23)                                                        \
+     *   Bc = (B < 0) ? 0 : B                   a comparison: a NaN stays a NaN                                                        \
+     *   op = (aa == 0) ? 0 : sqrt(Bc/aa)                                                                                              \
+     * The fractional powers are products of the element type's correctly rounded square root; there is no pow.  Both operators are    \
+     * EXACTLY 0 in pure shear (u = γ·y: every q and B is a sum of exact zeros), where |S| = γ is largest; WALE also falls as y³ at a  \
+     * wall.  STRICT returns the bits of these statements (float64 and float32, whichever of the three division builds the spacings    \
+     * select; NS3D_IEEE_DIV is honoured); the quotient is the IEEE division in every build.  FAST multiplies the spacing divisions by \
+     * reciprocals and may contract; its quotient and roots are the same IEEE operations.  When an intermediate overflows or is        \
+     * subnormal (dd·√dd in float32 leaves the range near |G| ≈ 1e6 and 1e-8) NOTHING is promised beyond IEEE propagation through the   \
+     * tree: Inf/Inf gives NaN, a den that underflows to 0 gives 0.  Enqueued on the context's stream, no read-back.                    \
+     * NS3D_ERR_ARG, with nothing written: the cases of ns3d_eddy_viscosity, and an unknown op. */                                      \
+    int ns3d_sgs_viscosity_##S(ns3d_ctx *, int op, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length, \
+                               double dx, double dy, double dz, int nx, int ny, int nz);                     \
     /* update_τ! with the scalar μ replaced by the field mu_e ((nx,ny,nz), e.g. ns3d_eddy_viscosity's).  Normal stresses use the cell's \
      * own value, (two*mu_e)*(…): update_τ!'s expression tree with 2μ read per cell.  Shear stresses use the mean of the four cells    \
      * around the edge; with q = (T)0.25, m = mu_e, for the (nx-1,ny-1,nz-1) shear arrays:                                             \

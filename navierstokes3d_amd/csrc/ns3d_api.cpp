@@ -342,6 +342,15 @@ int ns3d_set_turbulence(ns3d_ctx *c, int model, double length, void *mu_e)
     return NS3D_OK;
 }
 int ns3d_turbulence(const ns3d_ctx *c) { return c ? c->turbulence : -1; }
+int ns3d_set_sgs_operator(ns3d_ctx *c, int op)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_sgs_operator: null context");
+    if (op != NS3D_SGS_SMAGORINSKY && op != NS3D_SGS_WALE && op != NS3D_SGS_VREMAN)
+        return fail(NS3D_ERR_ARG, "ns3d_set_sgs_operator: operator %d (NS3D_SGS_SMAGORINSKY | NS3D_SGS_WALE | NS3D_SGS_VREMAN)", op);
+    c->sgs_operator = op;
+    return NS3D_OK;
+}
+int ns3d_sgs_operator(const ns3d_ctx *c) { return c ? c->sgs_operator : -1; }
 
 int ns3d_set_pt2_variant(ns3d_ctx *c, int v)
 {

@@ -151,6 +151,23 @@ extern "C" int NS3D_FN(eddy_viscosity)(ns3d_ctx *c, T *mu_e, const T *Vx, const 
     return finish(c, DISPATCHG(c, dx, dy, dz, eddy_viscosity<T>(c->stream, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz)),
                   "eddy_viscosity");
 }
+extern "C" int NS3D_FN(sgs_viscosity)(ns3d_ctx *c, int op, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho,
+                                      double length, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(mu_e, Vx, Vy, Vz); CHECK_GRID(nx, ny, nz, 3);
+    if (op != NS3D_SGS_SMAGORINSKY && op != NS3D_SGS_WALE && op != NS3D_SGS_VREMAN)
+        return fail(NS3D_ERR_ARG, "%s: operator %d (NS3D_SGS_SMAGORINSKY | NS3D_SGS_WALE | NS3D_SGS_VREMAN)", __func__, op);
+    if (!(std::isfinite(dx) && std::isfinite(dy) && std::isfinite(dz) && dx > 0.0 && dy > 0.0 && dz > 0.0))
+        return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (need finite values > 0)", __func__, dx, dy, dz);
+    if (!(std::isfinite(mu) && std::isfinite(rho) && std::isfinite(length) && mu >= 0.0 && rho >= 0.0 && length >= 0.0))
+        return fail(NS3D_ERR_ARG, "%s: mu = %g, rho = %g, length = %g (need finite values >= 0)", __func__, mu, rho, length);
+    const size_t cells = (size_t)nx * ny * nz * sizeof(T);
+    if (overlaps(mu_e, cells, Vx, cells + (size_t)ny * nz * sizeof(T)) || overlaps(mu_e, cells, Vy, cells + (size_t)nx * nz * sizeof(T)) ||
+        overlaps(mu_e, cells, Vz, cells + (size_t)nx * ny * sizeof(T)))
+        return fail(NS3D_ERR_ARG, "%s: mu_e must not alias a velocity array", __func__);
+    return finish(c, DISPATCHG(c, dx, dy, dz, sgs_viscosity<T>(c->stream, op, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz)),
+                  "sgs_viscosity");
+}
 extern "C" int NS3D_FN(update_tau_var)(ns3d_ctx *c, T *txx, T *tyy, T *tzz, T *txy, T *txz, T *tyz, const T *Vx, const T *Vy, const T *Vz,
                                        const T *mu_e, double dx, double dy, double dz, int nx, int ny, int nz)
 {
@@ -512,7 +529,10 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
     do {
         if (c->turbulence != NS3D_TURB_NONE) {  // ns3d_set_turbulence: μ_e into the caller's array, then the same two statements under it
             T *mu_e = (T *)c->turb_mu_e;
-            if ((rc = NS3D_FN(eddy_viscosity)(c, mu_e, Vx, Vy, Vz, p->mu, p->rho, c->turb_length, p->dx, p->dy, p->dz, nx, ny, nz))) break;
+            if ((rc = c->sgs_operator == NS3D_SGS_SMAGORINSKY     // ns3d_set_sgs_operator: which operator forms it
+                          ? NS3D_FN(eddy_viscosity)(c, mu_e, Vx, Vy, Vz, p->mu, p->rho, c->turb_length, p->dx, p->dy, p->dz, nx, ny, nz)
+                          : NS3D_FN(sgs_viscosity)(c, c->sgs_operator, mu_e, Vx, Vy, Vz, p->mu, p->rho, c->turb_length, p->dx, p->dy, p->dz, nx,
+                                                   ny, nz))) break;
             if (p->write_stress && (rc = NS3D_FN(update_tau_var)(c, (T *)f->txx, (T *)f->tyy, (T *)f->tzz, (T *)f->txy, (T *)f->txz,
                                                                  (T *)f->tyz, Vx, Vy, Vz, mu_e, p->dx, p->dy, p->dz, nx, ny, nz))) break;
             if ((rc = NS3D_FN(predict_var)(c, Vxo, Vyo, Vzo, Vx, Vy, Vz, mu_e, p->rho, p->g, p->dt, p->dx, p->dy, p->dz, nx, ny, nz))) break;

@@ -80,6 +80,7 @@ struct ns3d_ctx {
     int turbulence = 0;                     // ns3d_set_turbulence: the subgrid model of ns3d_time_step's predictor (NS3D_TURB_*)
     double turb_length = 0.0;               //   its length ℓ = C_s·Δ
     void *turb_mu_e = nullptr;              //   the caller's nx·ny·nz array the step writes μ_e to
+    int sgs_operator = 0;                   // ns3d_set_sgs_operator: the operator the step forms μ_e with while a model is set (NS3D_SGS_*)
     void clear_graphs()
     {
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.exec);

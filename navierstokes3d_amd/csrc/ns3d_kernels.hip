@@ -4928,7 +4928,38 @@ hipError_t vortex(hipStream_t s, T *Wx, T *Wy, T *Wz, T *Q, const T *Vx, const T
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double sqrt_rn(double a) { return __builtin_sqrt(a); }
 __device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
-template <class T>
+// ns3d_sgs_viscosity: the same field with |S| replaced by the differential operator OP (NS3D_SGS_*; include/ns3d.h has the three
+// expression trees) — a COMPILE-TIME parameter of the one kernel, so the plane loop has no branch on the model; operator 0 keeps
+// its statement in the kernel's own text, as it always stood there (DESIGN §4.16 compares its ISA).  All nine gradient entries are in registers where |S| is formed: WALE (g² = G·G, its deviatoric
+// symmetric part) and Vreman (β = G·Gᵀ, the sum of its principal 2×2 minors) cost arithmetic only, not one byte of traffic.  The
+// fractional powers are products of correctly rounded square roots; the one quotient per cell is the element type's IEEE division
+// in every build — FAST differs by contraction alone (no fast-math flag reaches this unit, and no reciprocal is formed).
+template <int OP, class T>
+__device__ __forceinline__ T sgs_operator(T gxx, T gyy, T gzz, T uy, T uz, T vx, T vz, T wx, T wy, T s2)
+{
+    static_assert(OP == NS3D_SGS_WALE || OP == NS3D_SGS_VREMAN, "operator 0 is k_eddy_visc's own statement");
+    const T h = (T)0.5, two = (T)2;
+    if constexpr (OP == NS3D_SGS_VREMAN) {
+        const T b11 = (gxx * gxx + uy * uy) + uz * uz, b22 = (vx * vx + gyy * gyy) + vz * vz, b33 = (wx * wx + wy * wy) + gzz * gzz;
+        const T b12 = (gxx * vx + uy * gyy) + uz * vz, b13 = (gxx * wx + uy * wy) + uz * gzz, b23 = (vx * wx + gyy * wy) + vz * gzz;
+        const T aa = (b11 + b22) + b33;
+        const T B = ((b11 * b22 - b12 * b12) + (b11 * b33 - b13 * b13)) + (b22 * b33 - b23 * b23);
+        const T Bc = B < (T)0 ? (T)0 : B;       // a comparison: a NaN stays a NaN
+        return aa == (T)0 ? (T)0 : sqrt_rn(Bc / aa);
+    } else {
+        const T third = (T)(1.0 / 3.0);
+        const T q11 = (gxx * gxx + uy * vx) + uz * wx, q12 = (gxx * uy + uy * gyy) + uz * wy, q13 = (gxx * uz + uy * vz) + uz * gzz;
+        const T q21 = (vx * gxx + gyy * vx) + vz * wx, q22 = (vx * uy + gyy * gyy) + vz * wy, q23 = (vx * uz + gyy * vz) + vz * gzz;
+        const T q31 = (wx * gxx + wy * vx) + gzz * wx, q32 = (wx * uy + wy * gyy) + gzz * wy, q33 = (wx * uz + wy * vz) + gzz * gzz;
+        const T t = third * ((q11 + q22) + q33), d11 = q11 - t, d22 = q22 - t, d33 = q33 - t;
+        const T d12 = h * (q12 + q21), d13 = h * (q13 + q31), d23 = h * (q23 + q32);
+        const T dd = ((d11 * d11 + d22 * d22) + d33 * d33) + two * ((d12 * d12 + d13 * d13) + d23 * d23);
+        const T ss = h * s2;
+        const T num = dd * sqrt_rn(dd), den = (ss * ss) * sqrt_rn(ss) + dd * sqrt_rn(sqrt_rn(dd));
+        return den == (T)0 ? (T)0 : num / den;      // a NaN den is not == 0: it propagates
+    }
+}
+template <int OP, class T>
 __global__ __launch_bounds__(256) void k_eddy_visc(T *__restrict__ mu_e, const T *__restrict__ Vx, const T *__restrict__ Vy,
                                                    const T *__restrict__ Vz, T mu, T cl, Geo<T> g, int nx, int ny, int nz, int kz)
 {
@@ -5010,21 +5041,40 @@ __global__ __launch_bounds__(256) void k_eddy_visc(T *__restrict__ mu_e, const T
             const T gxx = DIV_X(dxc), gyy = DIV_Y(dyc), gzz = DIV_Z(zk1 - zk);
             const T a = uy + vx, b = uz + wx, cc = vz + wy;
             const T s2 = (two * ((gxx * gxx + gyy * gyy) + gzz * gzz)) + ((a * a + b * b) + cc * cc);
-            mu_e[oC + pC * k] = inner ? mu + cl * sqrt_rn(s2) : mu;
+            if constexpr (OP == NS3D_SGS_SMAGORINSKY)
+                mu_e[oC + pC * k] = inner ? mu + cl * sqrt_rn(s2) : mu;
+            else
+                mu_e[oC + pC * k] = inner ? mu + cl * sgs_operator<OP>(gxx, gyy, gzz, uy, uz, vx, vz, wx, wy, s2) : mu;
         }
         up = uc; uc = un; vp = vc; vc = vn; dxc = dxn; dyc = dyn; zk = zk1; zk1 = zk2;
     }
+}
+template <int OP, class T>
+static hipError_t sgs_launch(hipStream_t s, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length, double dx,
+                             double dy, double dz, int nx, int ny, int nz)
+{
+    const int kz = NS3D_VORTEX_KZ;
+    const dim3 blk(64, 4, 1);
+    const dim3 grd((unsigned)((nx + 63) / 64), (unsigned)((ny + 3) / 4), (unsigned)((nz + kz - 1) / kz));
+    hipLaunchKernelGGL((k_eddy_visc<OP, T>), grd, blk, 0, s, mu_e, Vx, Vy, Vz, (T)mu, (T)(rho * length * length), make_geo<T>(dx, dy, dz),
+                       nx, ny, nz, kz);
+    return hipGetLastError();
 }
 template <class T>
 hipError_t eddy_viscosity(hipStream_t s, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length, double dx,
                           double dy, double dz, int nx, int ny, int nz)
 {
-    const int kz = NS3D_VORTEX_KZ;
-    const dim3 blk(64, 4, 1);
-    const dim3 grd((unsigned)((nx + 63) / 64), (unsigned)((ny + 3) / 4), (unsigned)((nz + kz - 1) / kz));
-    hipLaunchKernelGGL(k_eddy_visc<T>, grd, blk, 0, s, mu_e, Vx, Vy, Vz, (T)mu, (T)(rho * length * length), make_geo<T>(dx, dy, dz), nx,
-                       ny, nz, kz);
-    return hipGetLastError();
+    return sgs_launch<NS3D_SGS_SMAGORINSKY>(s, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz);
+}
+template <class T>
+hipError_t sgs_viscosity(hipStream_t s, int op, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, double length,
+                         double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    switch (op) {       // the API has refused every other code
+    case NS3D_SGS_WALE: return sgs_launch<NS3D_SGS_WALE>(s, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz);
+    case NS3D_SGS_VREMAN: return sgs_launch<NS3D_SGS_VREMAN>(s, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz);
+    default: return eddy_viscosity<T>(s, mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, nx, ny, nz);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -5154,6 +5204,8 @@ hipError_t divtest(hipStream_t s, double d, long n, unsigned long long seed, uns
                                   int, int, int);                                                            \
     template hipError_t eddy_viscosity<T>(hipStream_t, T *, const T *, const T *, const T *, double, double, double, double, double, \
                                           double, int, int, int);                                            \
+    template hipError_t sgs_viscosity<T>(hipStream_t, int, T *, const T *, const T *, const T *, double, double, double, double, \
+                                         double, double, int, int, int);                                     \
     template hipError_t update_tau_var<T>(hipStream_t, T *, T *, T *, T *, T *, T *, const T *, const T *, const T *, const T *, \
                                           double, double, double, int, int, int);                            \
     template hipError_t predict_var<T>(hipStream_t, T *, T *, T *, const T *, const T *, const T *, const T *, double, double, \

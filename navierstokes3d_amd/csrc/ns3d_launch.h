@@ -217,6 +217,10 @@ hipError_t emit(hipStream_t, const T *A, const T *B, const ns3d_iso_geom &, doub
     template <class T>                                                                                       \
     hipError_t eddy_viscosity(hipStream_t, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, \
                               double length, double dx, double dy, double dz, int nx, int ny, int nz);       \
+    /* the same with |S| replaced by the operator `op` (NS3D_SGS_*, checked by the caller); op 0 IS eddy_viscosity */ \
+    template <class T>                                                                                       \
+    hipError_t sgs_viscosity(hipStream_t, int op, T *mu_e, const T *Vx, const T *Vy, const T *Vz, double mu, double rho, \
+                             double length, double dx, double dy, double dz, int nx, int ny, int nz);        \
     template <class T>                                                                                       \
     hipError_t update_tau_var(hipStream_t, T *, T *, T *, T *, T *, T *, const T *, const T *, const T *, const T *mu_e, \
                               double dx, double dy, double dz, int, int, int);                               \

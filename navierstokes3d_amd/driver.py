@@ -272,9 +272,12 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     "smagorinsky", or dict(model="smagorinsky", cs=0.17).  Each step forms the effective viscosity μ_e = μ + ρ·ℓ²·|S| with
     ℓ = cs·(dx·dy·dz)^(1/3) (ns3d_eddy_viscosity, into an array this driver allocates) and predicts under it (ns3d_predict_var; the
     stress arrays of the last step come from ns3d_update_tau_var) — with `one_call` inside ns3d_time_step (Context.set_turbulence),
-    otherwise as these calls; the same bits either way.  info.turbulence gets length and mu_e, the field of the last step, as a host
-    array.  With diagnostics=True every record gains mu_e_max, and a step whose dt·mu_e_max/ρ·(1/dx² + 1/dy² + 1/dz²) exceeds 1/2 —
-    the explicit diffusion limit — raises Ns3dError.  One rank: anything else raises Ns3dError before anything is allocated."""
+    otherwise as these calls; the same bits either way.  "wale" / dict(model="wale", cw=0.5535) and "vreman" /
+    dict(model="vreman", c=0.07225) replace |S| by the operator of Nicoud & Ducros or of Vreman (ns3d_sgs_viscosity in place of
+    ns3d_eddy_viscosity; ℓ = cw·Δ, √c·Δ): both vanish in pure shear, where |S| is largest; the defaults are the published equivalents
+    of cs = 0.17.  info.turbulence gets model, length and mu_e, the field of the last step, as a host array.  With diagnostics=True
+    every record gains mu_e_max, and a step whose dt·mu_e_max/ρ·(1/dx² + 1/dy² + 1/dz²) exceeds 1/2 — the explicit diffusion limit —
+    raises Ns3dError.  One rank: anything else raises Ns3dError before anything is allocated."""
     _check_advection(advection)
     _check_turbulence(turbulence)
     if pressure not in ("pt", "direct"):
@@ -491,7 +494,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     out = _gather_all(grid, fs)                                                               # :528-532
     obs.finish(info, fs)
     if les is not None:
-        info.turbulence = dict(length=les.length, mu_e=K.to_numpy(les.mu_e))
+        info.turbulence = dict(model=les.model, length=les.length, mu_e=K.to_numpy(les.mu_e))
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
@@ -582,32 +585,53 @@ def _check_turbulence(turbulence, P=1):
     if turbulence is None:
         return None
     opts = dict(model=turbulence) if isinstance(turbulence, str) else turbulence
-    if not isinstance(opts, dict) or opts.get("model") != "smagorinsky" or set(opts) - {"model", "cs"}:
-        raise L.Ns3dError("turbulence = %r (None | \"smagorinsky\" | dict(model=\"smagorinsky\", cs=0.17))" % (turbulence,))
-    cs = float(opts.get("cs", 0.17))
-    if not (math.isfinite(cs) and cs >= 0.0):
-        raise L.Ns3dError("turbulence: cs = %r (need a finite value >= 0)" % (opts.get("cs"),))
+    model = opts.get("model") if isinstance(opts, dict) else None
+    if not isinstance(model, str) or model not in SGS_MODELS or set(opts) - {"model", SGS_MODELS[model][0]}:
+        raise L.Ns3dError("turbulence = %r (None | %s)" % (turbulence, " | ".join(
+            "\"%s\" | dict(model=\"%s\", %s=%r)" % (m, m, k, v) for m, (k, v) in SGS_MODELS.items())))
+    key, default = SGS_MODELS[model]
+    coef = float(opts.get(key, default))
+    if not (math.isfinite(coef) and coef >= 0.0):
+        raise L.Ns3dError("turbulence: %s = %r (need a finite value >= 0)" % (key, opts.get(key)))
     if P != 1:
-        raise L.Ns3dError("turbulence=\"smagorinsky\" runs on one rank (this grid has %d): the boundary layer of cells where mu_e is the "
+        raise L.Ns3dError("turbulence=\"%s\" runs on one rank (this grid has %d): the boundary layer of cells where mu_e is the "
                           "molecular viscosity would sit at the seams, and mu_e's halo would have to be exchanged between the eddy-viscosity "
-                          "kernel and the predictor" % P)
-    return SimpleNamespace(cs=cs)
+                          "kernel and the predictor" % (model, P))
+    les = SimpleNamespace(model=model)
+    setattr(les, key, coef)
+    return les
+
+
+# the `turbulence` keyword's models: the coefficient's key and its default.  cw and c are the published equivalents of cs = 0.17:
+# C_w² = 10.6·C_s² (Nicoud & Ducros 1999), c_v = 2.5·C_s² (Vreman 2004)
+SGS_MODELS = {"smagorinsky": ("cs", 0.17), "wale": ("cw", 0.5535), "vreman": ("c", 0.07225)}
+
+
+def sgs_length(les, dx, dy, dz):
+    """ℓ of μ_t = ρ·ℓ²·op: cs·Δ, cw·Δ or √c·Δ with Δ = (dx·dy·dz)^(1/3)"""
+    delta = (dx * dy * dz) ** (1.0 / 3.0)
+    if les.model == "vreman":
+        return math.sqrt(les.c) * delta
+    return (les.cs if les.model == "smagorinsky" else les.cw) * delta
 
 
 def _les_start(les, p, f, ctx, in_step):
-    """ℓ = cs·Δ and the μ_e array of a run; in_step: ns3d_time_step issues the calls (the context's knob), otherwise _les_predict does"""
-    les.length = les.cs * (p.dx * p.dy * p.dz) ** (1.0 / 3.0)
+    """ℓ and the μ_e array of a run; in_step: ns3d_time_step issues the calls (the context's knobs), otherwise _les_predict does"""
+    les.length = sgs_length(les, p.dx, p.dy, p.dz)
     les.mu_e = K.zeros(tuple(f.Pr.shape), f.Pr.dtype, f.Pr.device)
     ctx.after_torch_fill()
     if in_step:
-        ctx.set_turbulence("smagorinsky", les.length, les.mu_e)
+        ctx.set_turbulence(les.model, les.length, les.mu_e)
 
 
 def _les_predict(f, p, ctx, les, fused, write_stress, watch, it):
-    """{update_τ!; predict_V!} under the Smagorinsky viscosity, call by call — what ns3d_time_step issues under the knob: μ_e, the
+    """{update_τ!; predict_V!} under the subgrid model's viscosity, call by call — what ns3d_time_step issues under the knob: μ_e, the
     stress arrays where the plain step writes them, the predictor (in one pass, names swapped, if fused).  watch: returns max μ_e
     (the monitor's mu_e_max) and raises where the step would leave the explicit diffusion limit."""
-    K.eddy_viscosity(les.mu_e, f.Vx, f.Vy, f.Vz, p.mu, p.rho, les.length, p.dx, p.dy, p.dz, ctx=ctx)
+    if les.model == "smagorinsky":
+        K.eddy_viscosity(les.mu_e, f.Vx, f.Vy, f.Vz, p.mu, p.rho, les.length, p.dx, p.dy, p.dz, ctx=ctx)
+    else:
+        K.sgs_viscosity(les.mu_e, f.Vx, f.Vy, f.Vz, les.model, p.mu, p.rho, les.length, p.dx, p.dy, p.dz, ctx=ctx)
     mu_e_max = None
     if watch:
         mu_e_max = K.max_abs(les.mu_e, ctx=ctx)
@@ -825,5 +849,5 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     info.ctx = ctx
     obs.finish(info, [f])
     if les is not None:
-        info.turbulence = dict(length=les.length, mu_e=K.to_numpy(les.mu_e))
+        info.turbulence = dict(model=les.model, length=les.length, mu_e=K.to_numpy(les.mu_e))
     return f, info

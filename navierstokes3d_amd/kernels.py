@@ -220,18 +220,30 @@ class Context:
 
     def set_turbulence(self, model, length=0.0, mu_e=None):
         """The subgrid model of ns3d_time_step's predictor: None / "none" (the default: the scalar μ, not one extra call) or
-        "smagorinsky" with length = C_s·Δ and mu_e, a column-major (nx,ny,nz) tensor of the step's dtype that the step writes the
-        effective viscosity to (kept alive here until the setting is replaced).  The single calls do not read it."""
-        codes = {None: L.NS3D_TURB_NONE, "none": L.NS3D_TURB_NONE, "smagorinsky": L.NS3D_TURB_SMAGORINSKY}
+        "smagorinsky" | "wale" | "vreman" with length = C·Δ (C_s, C_w, √c_v) and mu_e, a column-major (nx,ny,nz) tensor of the step's
+        dtype that the step writes the effective viscosity to (kept alive here until the setting is replaced).  The name sets the
+        differential operator (ns3d_set_sgs_operator), then the model; None also returns the operator to Smagorinsky's.  The single
+        calls do not read it."""
+        codes = {None: L.NS3D_TURB_NONE, "none": L.NS3D_TURB_NONE}
+        codes.update((name, L.NS3D_TURB_SMAGORINSKY) for name in L.SGS_OPERATORS)
         if model not in codes:
-            raise L.Ns3dError("turbulence model = %r (None | \"smagorinsky\")" % (model,))
+            raise L.Ns3dError("turbulence model = %r (None | \"smagorinsky\" | \"wale\" | \"vreman\")" % (model,))
         off = codes[model] == L.NS3D_TURB_NONE
         ptr = None if off or mu_e is None else _chk(mu_e, None, "mu_e")
-        L.check(self.lib.ns3d_set_turbulence(self.handle, codes[model], C.c_double(float(length)), ptr))
+        before = int(self.lib.ns3d_sgs_operator(self.handle))
+        L.check(self.lib.ns3d_set_sgs_operator(self.handle, L.SGS_OPERATORS.get(model, L.NS3D_SGS_SMAGORINSKY)))
+        rc = self.lib.ns3d_set_turbulence(self.handle, codes[model], C.c_double(float(length)), ptr)
+        if rc != L.NS3D_OK:         # a refused model leaves both settings
+            msg = L.last_error()
+            self.lib.ns3d_set_sgs_operator(self.handle, before)
+            raise L.Ns3dError("libns3d status %d: %s" % (rc, msg))
         self._mu_e = None if off else mu_e
 
     def turbulence(self):
-        return {L.NS3D_TURB_NONE: None, L.NS3D_TURB_SMAGORINSKY: "smagorinsky"}[int(self.lib.ns3d_turbulence(self.handle))]
+        """None, or the name of the operator the step forms mu_e with"""
+        if int(self.lib.ns3d_turbulence(self.handle)) == L.NS3D_TURB_NONE:
+            return None
+        return {code: name for name, code in L.SGS_OPERATORS.items()}[int(self.lib.ns3d_sgs_operator(self.handle))]
 
     def set_pt_depth(self, depth):
         """PT iterations per pass over memory in pt_iterate / pt_solve: 0 automatic, 1…4 forced (5: float32 fields only)."""
@@ -337,6 +349,22 @@ def eddy_viscosity(mu_e, Vx, Vy, Vz, mu, rho, length, dx, dy, dz, ctx=None):
         if t.dtype != Vx.dtype or t.device != Vx.device:
             raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
     _ctx(ctx, Vx).call("eddy_viscosity", Vx, out, *V, *_d(mu, rho, length, dx, dy, dz), nx, ny, nz)
+
+
+def sgs_viscosity(mu_e, Vx, Vy, Vz, op, mu, rho, length, dx, dy, dz, ctx=None):
+    """ns3d_sgs_viscosity: mu_e = μ + ρ·length²·op(∇V) with the differential operator `op` — "smagorinsky" (eddy_viscosity's bits),
+    "wale" or "vreman", or its NS3D_SGS_* code — from eddy_viscosity's velocity gradient, in one fused pass (include/ns3d.h has the
+    expressions).  WALE and Vreman vanish exactly in pure shear.  length = C_w·Δ / √c_v·Δ.  Enqueues; no read-back."""
+    code = L.SGS_OPERATORS.get(op, op) if isinstance(op, str) else op
+    if isinstance(code, bool) or not isinstance(code, int):
+        raise L.Ns3dError("sgs operator = %r (\"smagorinsky\" | \"wale\" | \"vreman\", or an NS3D_SGS_* code)" % (op,))
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    out = _chk_like(mu_e, (nx, ny, nz), "mu_e", Vx)
+    V = _chk_V(Vx, Vy, Vz, (nx, ny, nz))
+    for name, t in (("Vy", Vy), ("Vz", Vz)):
+        if t.dtype != Vx.dtype or t.device != Vx.device:
+            raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
+    _ctx(ctx, Vx).call("sgs_viscosity", Vx, code, out, *V, *_d(mu, rho, length, dx, dy, dz), nx, ny, nz)
 
 
 def update_tau_var(txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu_e, dx, dy, dz, ctx=None):

@@ -13,6 +13,8 @@ NS3D_STRICT, NS3D_FAST, NS3D_ASYNC, NS3D_IEEE_DIV = 0x0, 0x1, 0x2, 0x4
 NS3D_BC_MULTI, NS3D_BC_GPU = 0, 1
 NS3D_ADVECT_REFERENCE, NS3D_ADVECT_MACCORMACK = 0, 1
 NS3D_TURB_NONE, NS3D_TURB_SMAGORINSKY = 0, 1
+NS3D_SGS_SMAGORINSKY, NS3D_SGS_WALE, NS3D_SGS_VREMAN = 0, 1, 2
+SGS_OPERATORS = {"smagorinsky": NS3D_SGS_SMAGORINSKY, "wale": NS3D_SGS_WALE, "vreman": NS3D_SGS_VREMAN}
 
 
 class Ns3dError(RuntimeError):
@@ -120,6 +122,8 @@ DERIVED_SIGNATURES = {
     "eddy_viscosity": [_P] * 4 + [_D] * 6 + [_I] * 3,
     "update_tau_var": [_P] * 10 + [_D] * 3 + [_I] * 3,
     "predict_var": [_P] * 7 + [_D] * 6 + [_I] * 3,
+    # the same viscosity field under another differential operator (WALE, Vreman): the operator's code, then eddy_viscosity's list
+    "sgs_viscosity": [_I] + [_P] * 4 + [_D] * 6 + [_I] * 3,
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
@@ -127,7 +131,7 @@ CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destr
                    "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
                    "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test", "ns3d_set_advection", "ns3d_advection",
                    "ns3d_stats_reset", "ns3d_stats_finalize", "ns3d_voxelize", "ns3d_set_obstacle", "ns3d_obstacle",
-                   "ns3d_set_turbulence", "ns3d_turbulence"]
+                   "ns3d_set_turbulence", "ns3d_turbulence", "ns3d_set_sgs_operator", "ns3d_sgs_operator"]
 NS3D_STATS_SLOTS = 11
 
 
@@ -248,6 +252,10 @@ def load():
     lib.ns3d_set_turbulence.restype = _I
     lib.ns3d_turbulence.argtypes = [_P]
     lib.ns3d_turbulence.restype = _I
+    lib.ns3d_set_sgs_operator.argtypes = [_P, _I]
+    lib.ns3d_set_sgs_operator.restype = _I
+    lib.ns3d_sgs_operator.argtypes = [_P]
+    lib.ns3d_sgs_operator.restype = _I
     lib.ns3d_cached_graphs.argtypes = [_P]
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
