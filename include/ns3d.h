@@ -232,6 +232,20 @@ int ns3d_turbulence(const ns3d_ctx *ctx);
 enum { NS3D_SGS_SMAGORINSKY = 0, NS3D_SGS_WALE = 1, NS3D_SGS_VREMAN = 2 };
 int ns3d_set_sgs_operator(ns3d_ctx *ctx, int op);
 int ns3d_sgs_operator(const ns3d_ctx *ctx);
+/* The active scalar of ns3d_time_step (outside parity, like the knobs above): diffusion of C and Boussinesq buoyancy.  on = 0 (the
+ * default) clears the setting: C is the passive dye of the reference and the step makes not one extra call.  on != 0: the step calls
+ * ns3d_scalar_step (below) through the public entry point BEHIND the predictor's name swap and BEFORE the first set_cylinder! /
+ * ns3d_set_solid, in either script: from C into the C_o buffer of ns3d_step_fields — it must then be given —, with Vz the freshly
+ * predicted field, kappa, bg and c_ref of this call and dt, the spacings and μ of ns3d_step_params; C and C_o then swap names.  The
+ * masking call that follows re-imposes C = 1 in the body: the body is a Dirichlet wall of the scalar.  sct is the turbulent Schmidt
+ * number: while ns3d_set_turbulence has a model set and sct > 0 the step passes that model's mu_e (the field its predictor used) and
+ * sgs = 1/(ρ·sct); otherwise NULL and 0.  bg = g·β is formed by the caller.  The settings are plain numbers: no scratch, no accessor
+ * beyond ns3d_scalar, which returns 1 / 0 (-1 for a null context).  ns3d_set_turbulence does not touch them.  One rank: C's halo
+ * would have to be exchanged between the advection and this call.  Nothing but ns3d_time_step reads the knob.  The explicit limit
+ * dt·K·(1/dx² + 1/dy² + 1/dz²) ≤ 1/2 is the caller's to keep (the Python drivers check the molecular part before a run).
+ * NS3D_ERR_ARG, the setting unchanged: a null context; kappa < 0 or sct < 0; any value not finite. */
+int ns3d_set_scalar(ns3d_ctx *ctx, int on, double kappa, double sct, double bg, double c_ref);
+int ns3d_scalar(const ns3d_ctx *ctx);
 
 /* Parameters of the fused pseudo-transient path (ns3d_pt_iterate / ns3d_pt_solve). */
 typedef struct ns3d_pt_params {
@@ -636,6 +650,36 @@ int ns3d_voxelize(ns3d_ctx *, unsigned char *mask, const double *tri, long long 
      * context or pointer, a grid below 2×2×2, an output that is its own input. */                                                     \
     int ns3d_predict_var_##S(ns3d_ctx *, T *Vx_new, T *Vy_new, T *Vz_new, const T *Vx, const T *Vy, const T *Vz, const T *mu_e, \
                              double rho, double g, double dt, double dx, double dy, double dz, int nx, int ny, int nz); \
+    /* The active scalar (outside parity).  ns3d_scalar_diffuse: ONE explicit step of ∂C/∂t = ∇·(K ∇C) in flux form on the cell-centred \
+     * (nx,ny,nz) field C, out of place — every cell of C_out is written — with ZERO flux through all six domain faces.  mu_e, an    \
+     * (nx,ny,nz) field such as ns3d_eddy_viscosity's, may be NULL.  All arithmetic in T: the scalars arrive as double and are converted \
+     * once, h = (T)0.5.  As NumPy:                                                                                                  \
+     *   K  = kappa                         (mu_e NULL)      |      kappa + sgs*(mu_e - mu)       per cell                           \
+     *   Fx = (h*(K[:-1] + K[1:])) * ((C[1:] - C[:-1])/dx)           the nx-1 faces between cells in x; Fy, Fz likewise in y, z      \
+     *   Dx = (pad0(Fx)[1:] - pad0(Fx)[:-1]) / dx                    pad0: one face of +0.0 at each end, through the SAME subtraction \
+     *   C_out = C + dt*((Dx + Dy) + Dz)                                                                                             \
+     * sgs = 1/(ρ·Sc_t) is formed by the caller in double (0: no eddy diffusivity): no division by it runs on the device.  The divisions \
+     * by dx, dy, dz follow the context's arithmetic build exactly as in update_τ! (STRICT, NS3D_IEEE_DIV honoured: the bits of the  \
+     * statement in float64 and float32; FAST: reciprocals).  STRICT contracts nothing; FAST fuses exactly three sums, a·b + c in one\
+     * rounding: K = fma(sgs, mu_e - mu, kappa), C_out = fma(dt, (Dx + Dy) + Dz, C) and the one of ns3d_buoyancy below.  A face's flux is \
+     * the same bits for both cells that share it.  kappa == 0 with no eddy diffusivity is still a full pass (C_out = C by value).  A \
+     * uniform mu_e == mu returns the bits of mu_e NULL.  Stability (dt·K·Σ1/d² ≤ 1/2) is the caller's.  Enqueued on the context's   \
+     * stream, no read-back.  NS3D_ERR_ARG, with nothing written, for this call and the two below: a null context or array (mu_e     \
+     * excepted); a grid below 3×3×3; kappa, sgs, mu, bg, c_ref, dt or a spacing not finite; kappa < 0, sgs < 0, a spacing <= 0;     \
+     * C_out == C. */                                                                                                                \
+    int ns3d_scalar_diffuse_##S(ns3d_ctx *, T *C_out, const T *C, const T *mu_e, double kappa, double sgs, double mu, double dt,     \
+                                double dx, double dy, double dz, int nx, int ny, int nz);                                            \
+    /* The Boussinesq term of the vertical momentum, in place on @inn(Vz) — predict_V!'s range, 0-based 1 <= i <= nx-2, 1 <= j <= ny-2, \
+     * 1 <= k <= nz-1 of the (nx,ny,nz+1) array; every other entry is untouched:                                                     \
+     *   Vz[i,j,k] = Vz[i,j,k] + dt*(bg*(h*(C[i,j,k-1] + C[i,j,k]) - c_ref))                                                         \
+     * bg = g·β is formed by the caller; a positive bg lifts fluid whose C exceeds c_ref.  FAST: fma(dt, bg*(h*(…) - c_ref), Vz). */    \
+    int ns3d_buoyancy_##S(ns3d_ctx *, T *Vz, const T *C, double bg, double c_ref, double dt, int nx, int ny, int nz);                \
+    /* ns3d_scalar_diffuse and ns3d_buoyancy in ONE pass (the form ns3d_time_step uses under ns3d_set_scalar), both reading the input C: \
+     * C_out and Vz are left bit for bit what the two single calls leave, in every arithmetic mode and both element types — one kernel \
+     * template serves the three calls.  5 elements of traffic per cell (read C, mu_e; read and write Vz; write C_out) against 7 for the \
+     * two calls.  bg == 0 skips the Vz traffic (Vz may then be NULL). */                                                            \
+    int ns3d_scalar_step_##S(ns3d_ctx *, T *C_out, T *Vz, const T *C, const T *mu_e, double kappa, double sgs, double mu, double bg, \
+                             double c_ref, double dt, double dx, double dy, double dz, int nx, int ny, int nz);                      \
     /* set_cylinder!(C,Vx,Vy,Vz,a2,b2,ox,oy,sinβ,cosβ,xco_g,yco_g,zco_g,lx,ly,lz,dx,dy,dz) multi.jl:249-281 */\
     int ns3d_set_cylinder_##S(ns3d_ctx *, T *C, T *Vx, T *Vy, T *Vz, double a2, double b2, double ox,        \
                               double oy, double sinb, double cosb, double xco_g, double yco_g, double zco_g, \

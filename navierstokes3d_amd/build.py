@@ -25,6 +25,12 @@ UNITS = [
     ("ns3d_kernels.hip", "ns3d_kernels_strictx.o", ["-DNS3D_MODE_STRICT", "-DNS3D_EXACT_RECIP", "-ffp-contract=off"]),
     ("ns3d_kernels.hip", "ns3d_kernels_strictp.o", ["-DNS3D_MODE_STRICT", "-DNS3D_POW2_RECIP", "-ffp-contract=off"]),
     ("ns3d_kernels.hip", "ns3d_kernels_fast.o", ["-DNS3D_MODE_FAST", "-ffp-contract=fast"]),
+    # ns3d_scalar_diffuse / ns3d_buoyancy / ns3d_scalar_step: the four arithmetic builds, none of them contracting — where FAST
+    # fuses, the unit says fma, so that the fused call and the two single calls cannot differ
+    ("ns3d_scalar.hip", "ns3d_scalar_strict.o", ["-DNS3D_MODE_STRICT", "-ffp-contract=off"]),
+    ("ns3d_scalar.hip", "ns3d_scalar_strictx.o", ["-DNS3D_MODE_STRICT", "-DNS3D_EXACT_RECIP", "-ffp-contract=off"]),
+    ("ns3d_scalar.hip", "ns3d_scalar_strictp.o", ["-DNS3D_MODE_STRICT", "-DNS3D_POW2_RECIP", "-ffp-contract=off"]),
+    ("ns3d_scalar.hip", "ns3d_scalar_fast.o", ["-DNS3D_MODE_FAST", "-ffp-contract=off"]),
     ("ns3d_direct.hip", "ns3d_direct.o", []),
     # ns3d_sample / ns3d_tracers_advance: the same bits in every arithmetic mode, so one compilation and never an FMA
     ("ns3d_tracers.hip", "ns3d_tracers.o", ["-ffp-contract=off"]),

@@ -352,6 +352,22 @@ int ns3d_set_sgs_operator(ns3d_ctx *c, int op)
 }
 int ns3d_sgs_operator(const ns3d_ctx *c) { return c ? c->sgs_operator : -1; }
 
+int ns3d_set_scalar(ns3d_ctx *c, int on, double kappa, double sct, double bg, double c_ref)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_scalar: null context");
+    if (!(std::isfinite(kappa) && std::isfinite(sct) && std::isfinite(bg) && std::isfinite(c_ref)))
+        return fail(NS3D_ERR_ARG, "ns3d_set_scalar: kappa = %g, sct = %g, bg = %g, c_ref = %g (need finite values)", kappa, sct, bg, c_ref);
+    if (!(kappa >= 0.0 && sct >= 0.0))
+        return fail(NS3D_ERR_ARG, "ns3d_set_scalar: kappa = %g, sct = %g (need values >= 0)", kappa, sct);
+    if (!on) {
+        c->scalar_on = 0; c->scalar_kappa = c->scalar_sct = c->scalar_bg = c->scalar_c_ref = 0.0;
+        return NS3D_OK;
+    }
+    c->scalar_on = 1; c->scalar_kappa = kappa; c->scalar_sct = sct; c->scalar_bg = bg; c->scalar_c_ref = c_ref;
+    return NS3D_OK;
+}
+int ns3d_scalar(const ns3d_ctx *c) { return c ? c->scalar_on : -1; }
+
 int ns3d_set_pt2_variant(ns3d_ctx *c, int v)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_pt2_variant: null context");

@@ -184,6 +184,48 @@ extern "C" int NS3D_FN(predict_var)(ns3d_ctx *c, T *Vx_new, T *Vy_new, T *Vz_new
     return finish(c, DISPATCHG(c, dx, dy, dz, predict_var<T>(c->stream, Vx_new, Vy_new, Vz_new, Vx, Vy, Vz, mu_e, rho, g, dt, dx, dy, dz, nx, ny, nz)),
                   "predict_var");
 }
+// ns3d_scalar_diffuse / ns3d_buoyancy / ns3d_scalar_step (ns3d_scalar.hip): one kernel template, `what` selects its halves
+static int scalar_check(const char *fn, double kappa, double sgs, double mu, double bg, double c_ref, double dt, double dx, double dy,
+                        double dz)
+{
+    if (!(std::isfinite(dx) && std::isfinite(dy) && std::isfinite(dz) && dx > 0.0 && dy > 0.0 && dz > 0.0))
+        return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (need finite values > 0)", fn, dx, dy, dz);
+    if (!(std::isfinite(kappa) && std::isfinite(sgs) && kappa >= 0.0 && sgs >= 0.0))
+        return fail(NS3D_ERR_ARG, "%s: kappa = %g, sgs = %g (need finite values >= 0)", fn, kappa, sgs);
+    if (!(std::isfinite(mu) && std::isfinite(bg) && std::isfinite(c_ref) && std::isfinite(dt)))
+        return fail(NS3D_ERR_ARG, "%s: mu = %g, bg = %g, c_ref = %g, dt = %g (need finite values)", fn, mu, bg, c_ref, dt);
+    return NS3D_OK;
+}
+extern "C" int NS3D_FN(scalar_diffuse)(ns3d_ctx *c, T *C_out, const T *C, const T *mu_e, double kappa, double sgs, double mu, double dt,
+                                       double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(C_out, C); CHECK_GRID(nx, ny, nz, 3);
+    const int rc = scalar_check(__func__, kappa, sgs, mu, 0.0, 0.0, dt, dx, dy, dz);
+    if (rc) return rc;
+    if (C_out == C) return fail(NS3D_ERR_ARG, "%s: C_out needs a buffer of its own", __func__);
+    return finish(c, DISPATCHG(c, dx, dy, dz, scalar_step<T>(c->stream, 1, C_out, (T *)nullptr, C, mu_e, kappa, sgs, mu, 0.0, 0.0, dt, dx, dy, dz,
+                                                             nx, ny, nz)), "scalar_diffuse");
+}
+extern "C" int NS3D_FN(buoyancy)(ns3d_ctx *c, T *Vz, const T *C, double bg, double c_ref, double dt, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vz, C); CHECK_GRID(nx, ny, nz, 3);
+    const int rc = scalar_check(__func__, 0.0, 0.0, 0.0, bg, c_ref, dt, 1.0, 1.0, 1.0);
+    if (rc) return rc;
+    // no division in this half: the spacings only pick a build, and every build of it is the same statement
+    return finish(c, DISPATCH(c, scalar_step<T>(c->stream, 2, (T *)nullptr, Vz, C, (const T *)nullptr, 0.0, 0.0, 0.0, bg, c_ref, dt, 1.0, 1.0,
+                                                1.0, nx, ny, nz)), "buoyancy");
+}
+extern "C" int NS3D_FN(scalar_step)(ns3d_ctx *c, T *C_out, T *Vz, const T *C, const T *mu_e, double kappa, double sgs, double mu, double bg,
+                                    double c_ref, double dt, double dx, double dy, double dz, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(C_out, C); CHECK_GRID(nx, ny, nz, 3);
+    const int rc = scalar_check(__func__, kappa, sgs, mu, bg, c_ref, dt, dx, dy, dz);
+    if (rc) return rc;
+    if (bg != 0.0 && !Vz) return fail(NS3D_ERR_ARG, "%s: null field pointer (Vz, with bg != 0)", __func__);
+    if (C_out == C) return fail(NS3D_ERR_ARG, "%s: C_out needs a buffer of its own", __func__);
+    return finish(c, DISPATCHG(c, dx, dy, dz, scalar_step<T>(c->stream, bg != 0.0 ? 3 : 1, C_out, Vz, C, mu_e, kappa, sgs, mu, bg, c_ref, dt, dx,
+                                                             dy, dz, nx, ny, nz)), "scalar_step");
+}
 // ns3d_sample / ns3d_tracers_advance: one kernel build for every arithmetic mode (ns3d_tracers.hip), hence no DISPATCH
 static int tracers_count_check(long n, const char *fn)
 {
@@ -543,6 +585,13 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
             if ((rc = NS3D_FN(predict_fused)(c, Vxo, Vyo, Vzo, Vx, Vy, Vz, p->mu, p->rho, p->g, p->dt, p->dx, p->dy, p->dz, nx, ny, nz))) break;
         }
         std::swap(Vx, Vxo); std::swap(Vy, Vyo); std::swap(Vz, Vzo);
+        if (c->scalar_on) {     // ns3d_set_scalar: C diffuses and lifts the predicted Vz in one pass; the masking below is its Dirichlet wall
+            const bool eddy = c->turbulence != NS3D_TURB_NONE && c->scalar_sct > 0.0;
+            if ((rc = NS3D_FN(scalar_step)(c, Co, Vz, C, eddy ? (const T *)c->turb_mu_e : nullptr, c->scalar_kappa,
+                                           eddy ? 1.0 / (p->rho * c->scalar_sct) : 0.0, p->mu, c->scalar_bg, c->scalar_c_ref, p->dt, p->dx, p->dy,
+                                           p->dz, nx, ny, nz))) break;
+            std::swap(C, Co);
+        }
         if ((rc = cylinder())) break;                                                                               // :452 / :123
         if ((rc = NS3D_FN(update_divV)(c, divV, Vx, Vy, Vz, p->dx, p->dy, p->dz, nx, ny, nz))) break;               // :454 / :124
         ns3d_pt_params pt;

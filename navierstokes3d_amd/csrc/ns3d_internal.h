@@ -81,6 +81,8 @@ struct ns3d_ctx {
     double turb_length = 0.0;               //   its length ℓ = C_s·Δ
     void *turb_mu_e = nullptr;              //   the caller's nx·ny·nz array the step writes μ_e to
     int sgs_operator = 0;                   // ns3d_set_sgs_operator: the operator the step forms μ_e with while a model is set (NS3D_SGS_*)
+    int scalar_on = 0;                      // ns3d_set_scalar: ns3d_time_step diffuses C and lifts Vz (ns3d_scalar_step) behind its predictor
+    double scalar_kappa = 0.0, scalar_sct = 0.0, scalar_bg = 0.0, scalar_c_ref = 0.0;   //   κ, Sc_t (0: no eddy diffusivity), g·β, C_ref
     void clear_graphs()
     {
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.exec);

@@ -101,6 +101,10 @@ inline unsigned ns3d_diag_geometry(int nx, int ny, int nz, int *kz_out)
 // 8 / 16 / 32 planes at 512³ in fp64 and within 7 % of the best elsewhere (profiles/vortex_variants_ab.log).
 #define NS3D_VORTEX_KZ 16
 
+// ns3d_scalar_diffuse / ns3d_buoyancy / ns3d_scalar_step (ns3d_scalar.hip, k_scalar): the same 64×4 cell columns per workgroup over the
+// nx×ny columns, NS3D_SCALAR_KZ of the nz planes per workgroup (one further plane of C, and of mu_e, is read at each end of a chunk).
+#define NS3D_SCALAR_KZ 16
+
 // ns3d_isosurface (ns3d_isosurface.hip, compiled once: no arithmetic mode to select).  k_iso_count / k_iso_emit: one wave per row
 // segment of 64 cubes in x, NS3D_ISO_ROWS rows (j) per workgroup, NS3D_ISO_KZ cube planes marched in z per workgroup; the scan
 // works on NS3D_ISO_SCAN_BLOCK segments per workgroup and scans the workgroups' sums with one wave, 64 at a time.
@@ -227,6 +231,10 @@ hipError_t emit(hipStream_t, const T *A, const T *B, const ns3d_iso_geom &, doub
     template <class T>                                                                                       \
     hipError_t predict_var(hipStream_t, T *, T *, T *, const T *, const T *, const T *, const T *mu_e, double rho, \
                            double g, double dt, double dx, double dy, double dz, int, int, int);             \
+    /* ns3d_scalar.hip.  what: bit 0 the diffusion step C_out from C (mu_e may be null), bit 1 the buoyancy term into Vz */ \
+    template <class T>                                                                                       \
+    hipError_t scalar_step(hipStream_t, int what, T *C_out, T *Vz, const T *C, const T *mu_e, double kappa, double sgs, \
+                           double mu, double bg, double c_ref, double dt, double dx, double dy, double dz, int nx, int ny, int nz); \
     template <class T>                                                                                       \
     hipError_t divtest(hipStream_t, double d, long n, unsigned long long seed, unsigned long long *bad_dev); \
     template <class T>                                                                                       \

@@ -194,7 +194,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
                        statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None, advection="reference",
-                       obstacle=None, turbulence=None):
+                       obstacle=None, turbulence=None, scalar=None):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -277,9 +277,19 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     ns3d_eddy_viscosity; ℓ = cw·Δ, √c·Δ): both vanish in pure shear, where |S| is largest; the defaults are the published equivalents
     of cs = 0.17.  info.turbulence gets model, length and mu_e, the field of the last step, as a host array.  With diagnostics=True
     every record gains mu_e_max, and a step whose dt·mu_e_max/ρ·(1/dx² + 1/dy² + 1/dz²) exceeds 1/2 — the explicit diffusion limit —
-    raises Ns3dError.  One rank: anything else raises Ns3dError before anything is allocated."""
+    raises Ns3dError.  One rank: anything else raises Ns3dError before anything is allocated.
+    scalar=… (default None: C is the reference's passive dye, not one extra call; OUTSIDE the reference): dict(kappa=…, sct=0.7,
+    beta_g=0.0, c_ref=0.0) makes C an active, diffusing scalar.  Behind the predictor :449-451 and before the first set_cylinder!
+    :452 each step takes one explicit step of ∂C/∂t = ∇·(K ∇C), K = kappa (+ (μ_e − μ)/(ρ·sct) under a `turbulence` model with
+    sct > 0), with zero flux through the domain faces, and adds dt·beta_g·(C − c_ref) to the predicted Vz (ns3d_scalar_step, both
+    in one pass) — with `one_call` inside ns3d_time_step (Context.set_scalar), otherwise as this call; the same bits either way.
+    The body's C = 1 is re-imposed by the masking that follows: a Dirichlet wall.  info.scalar gets kappa, sct, bg and c_ref.  A
+    run whose dt·kappa·(1/dx² + 1/dy² + 1/dz²) exceeds 1/2 is refused; with diagnostics=True and a model, so is a step whose
+    dt·(kappa + (mu_e_max − μ)/(ρ·sct))·(1/dx² + 1/dy² + 1/dz²) does.  One rank: anything else raises Ns3dError before anything is
+    allocated."""
     _check_advection(advection)
     _check_turbulence(turbulence)
+    _check_scalar(scalar)
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -293,6 +303,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     P, dims, mg, root = grid.P, tuple(grid.dims), grid.mg, grid.is_root()
     maccormack = _check_advection(advection, faithful, P)
     les = _check_turbulence(turbulence, P)
+    sca = _check_scalar(scalar, P, multi_params(nx, dims=dims, coords=grid.local_coords[0], **shape))
     # the contexts of the ns3d_mgpu's ranks (their devices), or this rank's own
     ctxs = list(grid.contexts) if grid.contexts is not None else [K.Context(device, mode, async_=True)]
     ps = [multi_params(nx, dims=dims, coords=c3, **shape) for c3 in grid.local_coords]
@@ -381,6 +392,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         ctxs[0].set_obstacle(solid)                             # ns3d_time_step masks with it; back to the cylinder after the loop
     if les is not None:
         _les_start(les, p, fs[0], ctxs[0], step_params is not None)     # ns3d_time_step predicts under it; cleared after the loop
+    if sca is not None and step_params is not None:
+        ctxs[0].set_scalar(sca.kappa, sca.sct, sca.bg, sca.c_ref)       # ns3d_time_step diffuses and lifts with it; cleared after the loop
     hats = None
     if maccormack and step_params is not None:
         ctxs[0].set_advection("maccormack")                     # ns3d_time_step advects with it; back to the default after the loop
@@ -411,6 +424,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                 for f, c in zip(fs, ctxs):
                     K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
                                 ctx=c)                                                        # :451
+            if sca is not None:     # the active scalar (one rank): where ns3d_time_step issues it under the knob
+                _scalar_step(fs[0], p, ctxs[0], sca, les, mu_e_max if les is not None else None, it)
             if monitor:
                 mom_predict = removed()
             for f, c, cyl in zip(fs, ctxs, cyls):
@@ -487,6 +502,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         ctxs[0].set_obstacle(None)
     if les is not None:
         ctxs[0].set_turbulence(None)
+    if sca is not None and step_params is not None:
+        ctxs[0].set_scalar(None)
     if fused and faithful and nt > 0 and not (wide_advect_halo and P > 1):
         for f, c in zip(fs, ctxs):
             K.copy(f.Vz_o, f.Vz, ctx=c)     # the one copy of :475 the swaps skipped (Vz is never advected): same final state
@@ -495,6 +512,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     obs.finish(info, fs)
     if les is not None:
         info.turbulence = dict(model=les.model, length=les.length, mu_e=K.to_numpy(les.mu_e))
+    if sca is not None:
+        info.scalar = dict(kappa=sca.kappa, sct=sca.sct, bg=sca.bg, c_ref=sca.c_ref)
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
@@ -651,6 +670,51 @@ def _les_predict(f, p, ctx, les, fused, write_stress, watch, it):
     return mu_e_max
 
 
+SCALAR_KEYS = dict(kappa=None, sct=0.7, beta_g=0.0, c_ref=0.0)      # the `scalar` keyword's keys and defaults (kappa has none)
+
+
+def _check_scalar(scalar, P=1, p=None):
+    """the `scalar` keyword of both drivers → None, or a namespace with kappa, sct, bg (= beta_g) and c_ref; raises before anything
+    is allocated.  p: the run's parameters, for the explicit limit of the molecular part (None: not checked yet)"""
+    if scalar is None:
+        return None
+    usage = "scalar = %r (None | dict(kappa=…, sct=0.7, beta_g=0.0, c_ref=0.0))"
+    if not isinstance(scalar, dict) or set(scalar) - set(SCALAR_KEYS) or "kappa" not in scalar:
+        raise L.Ns3dError(usage % (scalar,))
+    vals = {}
+    for key, default in SCALAR_KEYS.items():
+        try:
+            vals[key] = float(scalar.get(key, default))
+        except (TypeError, ValueError):
+            raise L.Ns3dError(usage % (scalar,)) from None
+        if not math.isfinite(vals[key]) or (key in ("kappa", "sct") and vals[key] < 0.0):
+            raise L.Ns3dError("scalar: %s = %r (need a finite value%s)" % (key, scalar.get(key), " >= 0" if key in ("kappa", "sct") else ""))
+    if P != 1:
+        raise L.Ns3dError("scalar=… runs on one rank (this grid has %d): the diffusion step reads C across the seams, so C's halo would "
+                          "have to be exchanged between the advection and ns3d_scalar_step" % P)
+    if p is not None:
+        number = p.dt * vals["kappa"] * (1.0 / p.dx ** 2 + 1.0 / p.dy ** 2 + 1.0 / p.dz ** 2)
+        if not number <= 0.5:
+            raise L.Ns3dError("scalar: dt*kappa*(1/dx^2 + 1/dy^2 + 1/dz^2) = %r with kappa = %r is not within 1/2, the explicit diffusion "
+                              "limit; reduce kappa or dt" % (number, vals["kappa"]))
+    return SimpleNamespace(kappa=vals["kappa"], sct=vals["sct"], bg=vals["beta_g"], c_ref=vals["c_ref"])
+
+
+def _scalar_step(f, p, ctx, sca, les, mu_e_max, it):
+    """ns3d_scalar_step call by call — what ns3d_time_step issues under Context.set_scalar, behind the predictor: C diffuses into C_o
+    (under the subgrid model's eddy diffusivity while a model is set and sct > 0) and lifts the predicted Vz; the names swap.
+    mu_e_max (the monitor's, or None): raises where the step would leave the explicit diffusion limit."""
+    eddy = les is not None and sca.sct > 0.0
+    sgs = 1.0 / (p.rho * sca.sct) if eddy else 0.0
+    if eddy and mu_e_max is not None:
+        number = p.dt * (sca.kappa + sgs * (mu_e_max - p.mu)) * (1.0 / p.dx ** 2 + 1.0 / p.dy ** 2 + 1.0 / p.dz ** 2)
+        if not number <= 0.5:
+            raise L.Ns3dError("step %d: dt*(kappa + (mu_e_max - mu)/(rho*sct))*(1/dx^2 + 1/dy^2 + 1/dz^2) = %r with mu_e_max = %r is not "
+                              "within 1/2, the explicit diffusion limit of the scalar; reduce dt or raise sct" % (it, number, mu_e_max))
+    K.scalar_step(f.C_o, f.Vz, f.C, les.mu_e if eddy else None, sca.kappa, sgs, p.mu, sca.bg, sca.c_ref, p.dt, p.dx, p.dy, p.dz, ctx=ctx)
+    f.C, f.C_o = f.C_o, f.C
+
+
 def _alloc_hats(f, ctx):
     """buffers for stage 1 of the MacCormack advection (Vx, Vy, Vz, C) when the step runs call by call"""
     hats = tuple(K.zeros(tuple(a.shape), a.dtype, a.device) for a in (f.Vx, f.Vy, f.Vz, f.C))
@@ -697,7 +761,7 @@ def _save_mat(path, f, p, step0):
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
           diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None,
-          advection="reference", obstacle=None, turbulence=None):
+          advection="reference", obstacle=None, turbulence=None, scalar=None):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -716,9 +780,11 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     MAT file (numbered like the tracer dumps).
     advection: as in run_navierstokes3D, in place of :141-142; "maccormack" needs faithful=False.
     obstacle: as in run_navierstokes3D, in place of the set_cylinder! calls :123 and :139.
-    turbulence: as in run_navierstokes3D, in place of :121-122."""
+    turbulence: as in run_navierstokes3D, in place of :121-122.
+    scalar: as in run_navierstokes3D, between :122 and :123."""
     maccormack = _check_advection(advection, faithful)
     les = _check_turbulence(turbulence)
+    sca = _check_scalar(scalar, 1, gpu_params(nx))
     if device is None:
         device = torch.cuda.current_device()
     p = gpu_params(nx)
@@ -772,6 +838,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         ctx.set_obstacle(solid)                             # ns3d_time_step masks with it (the context is this run's own)
     if les is not None:
         _les_start(les, p, f, ctx, step_params is not None)     # ns3d_time_step predicts under it; cleared after the loop
+    if sca is not None and step_params is not None:
+        ctx.set_scalar(sca.kappa, sca.sct, sca.bg, sca.c_ref)   # ns3d_time_step diffuses and lifts with it; cleared after the loop
     hats = None
     if maccormack and step_params is not None:
         ctx.set_advection("maccormack")                     # ns3d_time_step advects with it (the context is this run's own)
@@ -792,6 +860,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
                 K.update_tau(f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, f.Vx, f.Vy, f.Vz, p.mu, p.dx, p.dy, p.dz, ctx=ctx)  # :121
                 K.predict_V(f.Vx, f.Vy, f.Vz, f.txx, f.tyy, f.tzz, f.txy, f.txz, f.tyz, p.rho, p.g, p.dt, p.dx, p.dy, p.dz,
                             ctx=ctx)                                                          # :122
+            if sca is not None:         # the active scalar: where ns3d_time_step issues it under the knob
+                _scalar_step(f, p, ctx, sca, les, mu_e_max if les is not None else None, it)
             if monitor:
                 mom_predict = removed()
             body(f, cyl, ctx)                                                                 # :123
@@ -843,6 +913,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         ctx.set_obstacle(None)
     if les is not None:
         ctx.set_turbulence(None)
+    if sca is not None and step_params is not None:
+        ctx.set_scalar(None)
     if fused and faithful and nt > 0:
         K.copy(f.Vz_o, f.Vz, ctx=ctx)       # the one copy of :141 the swaps skipped (Vz is never advected): same final state
     ctx.sync()
@@ -850,4 +922,6 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     obs.finish(info, [f])
     if les is not None:
         info.turbulence = dict(model=les.model, length=les.length, mu_e=K.to_numpy(les.mu_e))
+    if sca is not None:
+        info.scalar = dict(kappa=sca.kappa, sct=sca.sct, bg=sca.bg, c_ref=sca.c_ref)
     return f, info

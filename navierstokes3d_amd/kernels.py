@@ -245,6 +245,20 @@ class Context:
             return None
         return {code: name for name, code in L.SGS_OPERATORS.items()}[int(self.lib.ns3d_sgs_operator(self.handle))]
 
+    def set_scalar(self, kappa=None, sct=0.0, bg=0.0, c_ref=0.0):
+        """The active scalar of ns3d_time_step: kappa=None (the default: C is the reference's passive dye, not one extra call) clears
+        the setting; a number makes every step diffuse C with diffusivity kappa (plus the subgrid model's eddy diffusivity
+        (mu_e − μ)/(ρ·sct) while set_turbulence has a model and sct > 0) and lift the predicted Vz by dt·bg·(C − c_ref), bg = g·β, in
+        one ns3d_scalar_step call behind the predictor.  The single calls do not read it."""
+        if kappa is None:
+            L.check(self.lib.ns3d_set_scalar(self.handle, 0, 0.0, 0.0, 0.0, 0.0))
+        else:
+            L.check(self.lib.ns3d_set_scalar(self.handle, 1, float(kappa), float(sct), float(bg), float(c_ref)))
+
+    def scalar(self):
+        """whether ns3d_time_step runs the active scalar"""
+        return bool(self.lib.ns3d_scalar(self.handle))
+
     def set_pt_depth(self, depth):
         """PT iterations per pass over memory in pt_iterate / pt_solve: 0 automatic, 1…4 forced (5: float32 fields only)."""
         L.check(self.lib.ns3d_set_pt_depth(self.handle, int(depth)))
@@ -365,6 +379,31 @@ def sgs_viscosity(mu_e, Vx, Vy, Vz, op, mu, rho, length, dx, dy, dz, ctx=None):
         if t.dtype != Vx.dtype or t.device != Vx.device:
             raise L.Ns3dError("%s is %s on %s, Vx is %s on %s" % (name, t.dtype, t.device, Vx.dtype, Vx.device))
     _ctx(ctx, Vx).call("sgs_viscosity", Vx, code, out, *V, *_d(mu, rho, length, dx, dy, dz), nx, ny, nz)
+
+
+def scalar_diffuse(C_out, Cf, mu_e, kappa, sgs, mu, dt, dx, dy, dz, ctx=None):
+    """ns3d_scalar_diffuse: one explicit step of ∂C/∂t = ∇·(K ∇C) in flux form, out of place into C_out, zero flux through the domain
+    faces; K = kappa, or kappa + sgs·(mu_e − mu) per cell with the (nx,ny,nz) field mu_e (None: none).  include/ns3d.h has the
+    statement.  Enqueues; no read-back."""
+    nx, ny, nz = Cf.shape
+    _ctx(ctx, Cf).call("scalar_diffuse", Cf, _chk_like(C_out, (nx, ny, nz), "C_out", Cf), _chk(Cf, None, "C"),
+                       None if mu_e is None else _chk_like(mu_e, (nx, ny, nz), "mu_e", Cf), *_d(kappa, sgs, mu, dt, dx, dy, dz), nx, ny, nz)
+
+
+def buoyancy(Vz, Cf, bg, c_ref, dt, ctx=None):
+    """ns3d_buoyancy: Vz += dt·bg·(½(C[k−1] + C[k]) − c_ref) in place on predict_V!'s range of the (nx,ny,nz+1) array; bg = g·β."""
+    nx, ny, nz = Cf.shape
+    _ctx(ctx, Cf).call("buoyancy", Cf, _chk_like(Vz, (nx, ny, nz + 1), "Vz", Cf), _chk(Cf, None, "C"), *_d(bg, c_ref, dt), nx, ny, nz)
+
+
+def scalar_step(C_out, Vz, Cf, mu_e, kappa, sgs, mu, bg, c_ref, dt, dx, dy, dz, ctx=None):
+    """ns3d_scalar_step: scalar_diffuse and buoyancy in one pass, both reading Cf — the bits of the two calls.  Vz may be None when
+    bg == 0."""
+    nx, ny, nz = Cf.shape
+    _ctx(ctx, Cf).call("scalar_step", Cf, _chk_like(C_out, (nx, ny, nz), "C_out", Cf),
+                       None if Vz is None else _chk_like(Vz, (nx, ny, nz + 1), "Vz", Cf), _chk(Cf, None, "C"),
+                       None if mu_e is None else _chk_like(mu_e, (nx, ny, nz), "mu_e", Cf),
+                       *_d(kappa, sgs, mu, bg, c_ref, dt, dx, dy, dz), nx, ny, nz)
 
 
 def update_tau_var(txx, tyy, tzz, txy, txz, tyz, Vx, Vy, Vz, mu_e, dx, dy, dz, ctx=None):

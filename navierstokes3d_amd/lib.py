@@ -124,6 +124,10 @@ DERIVED_SIGNATURES = {
     "predict_var": [_P] * 7 + [_D] * 6 + [_I] * 3,
     # the same viscosity field under another differential operator (WALE, Vreman): the operator's code, then eddy_viscosity's list
     "sgs_viscosity": [_I] + [_P] * 4 + [_D] * 6 + [_I] * 3,
+    # the active scalar: diffusion of C, the buoyancy term of Vz, and both in one pass
+    "scalar_diffuse": [_P] * 3 + [_D] * 7 + [_I] * 3,
+    "buoyancy": [_P] * 2 + [_D] * 3 + [_I] * 3,
+    "scalar_step": [_P] * 4 + [_D] * 9 + [_I] * 3,
 }
 CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destroy", "ns3d_flags",
                    "ns3d_set_stream", "ns3d_use_own_stream", "ns3d_get_stream", "ns3d_sync", "ns3d_reserve_cus", "ns3d_reserved_cus", "ns3d_set_pt_variant",
@@ -131,7 +135,8 @@ CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destr
                    "ns3d_arith_build", "ns3d_cached_graphs", "ns3d_set_persist_mode", "ns3d_persist_faults",
                    "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test", "ns3d_set_advection", "ns3d_advection",
                    "ns3d_stats_reset", "ns3d_stats_finalize", "ns3d_voxelize", "ns3d_set_obstacle", "ns3d_obstacle",
-                   "ns3d_set_turbulence", "ns3d_turbulence", "ns3d_set_sgs_operator", "ns3d_sgs_operator"]
+                   "ns3d_set_turbulence", "ns3d_turbulence", "ns3d_set_sgs_operator", "ns3d_sgs_operator",
+                   "ns3d_set_scalar", "ns3d_scalar"]
 NS3D_STATS_SLOTS = 11
 
 
@@ -256,6 +261,10 @@ def load():
     lib.ns3d_set_sgs_operator.restype = _I
     lib.ns3d_sgs_operator.argtypes = [_P]
     lib.ns3d_sgs_operator.restype = _I
+    lib.ns3d_set_scalar.argtypes = [_P, _I, _D, _D, _D, _D]
+    lib.ns3d_set_scalar.restype = _I
+    lib.ns3d_scalar.argtypes = [_P]
+    lib.ns3d_scalar.restype = _I
     lib.ns3d_cached_graphs.argtypes = [_P]
     lib.ns3d_cached_graphs.restype = _I
     lib.ns3d_arith_build.argtypes = [_P, _D, _D, _D]
