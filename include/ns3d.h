@@ -31,7 +31,8 @@
  *        ns3d_max_abs, ns3d_residual_max        the value it returns               (none)
  *        ns3d_diagnostics                       the record it returns              (none)
  *        ns3d_selftest_exact_div                the count it returns               (none)
- *        ns3d_solid_momentum                    the sums and counts it returns     (none)
+ *        ns3d_solid_momentum,                   the sums and counts it returns     (none)
+ *        ns3d_solid_momentum_moving
  *        ns3d_isosurface                        the triangle count                 no: tri / val are enqueued behind the count
  *        ns3d_tracers_migrate_mgpu              the counts of leavers and empty    no: pack, exchange and insert are enqueued behind them
  *                                               slots of every rank
@@ -207,6 +208,18 @@ int ns3d_advection(const ns3d_ctx *ctx);
  * the setting (NULL for a null context).  Nothing else reads the knob: the single calls are what their names say. */
 int ns3d_set_obstacle(ns3d_ctx *ctx, const unsigned char *mask);
 const unsigned char *ns3d_obstacle(const ns3d_ctx *ctx);
+/* The rigid motion of the obstacle ns3d_time_step masks with (outside parity, like the knobs around it).  NULL motion9 (the default)
+ * clears the setting: the step issues exactly the calls described above.  motion9 = U[3], omega[3], centre[3] as ns3d_set_solid_moving
+ * takes them, origin (may be NULL: zeros) likewise: the context COPIES the twelve numbers and keeps no pointer.  While the setting is
+ * on, the step calls ns3d_set_solid_moving through the public entry point at BOTH masking places, in either script, with the mask of
+ * ns3d_set_obstacle, these numbers and the spacings of ns3d_step_params; with no mask set the step returns NS3D_ERR_ARG before anything
+ * is enqueued, the fields untouched.  Between steps the caller may rewrite the BYTES of the mask it registered (ns3d_voxelize into the
+ * same buffer, on the context's stream: a body that moves through the grid) and call this again with the pose's numbers; the address
+ * stays registered.  ns3d_set_obstacle does not touch the setting, and nothing but ns3d_time_step reads it.  ns3d_obstacle_motion
+ * returns 1 (and the nine numbers in out9, which may be NULL) or 0, -1 for a null context.
+ * NS3D_ERR_ARG, the setting unchanged: a null context, a number that is not finite, a negative origin entry. */
+int ns3d_set_obstacle_motion(ns3d_ctx *ctx, const double *motion9, const int *origin);
+int ns3d_obstacle_motion(const ns3d_ctx *ctx, double *out9);
 /* The subgrid-scale model of ns3d_time_step's predictor (outside parity with the reference, like the two knobs above).
  * NS3D_TURB_NONE (the default): the step's first two statements are update_τ! (if write_stress) and ns3d_predict_fused with the scalar
  * μ of ns3d_step_params — not one extra call.  NS3D_TURB_SMAGORINSKY: they are replaced, through the public entry points, by
@@ -399,6 +412,20 @@ int ns3d_stats_finalize(ns3d_ctx *, const double *S, double wsum, double *mean, 
  * NS3D_ERR_ARG, with nothing written: a null context, a null mask, a null tri with n_tri > 0, n_tri < 0, a grid below 3x3x3, a negative
  * origin entry. */
 int ns3d_voxelize(ns3d_ctx *, unsigned char *mask, const double *tri, long long n_tri, int nx, int ny, int nz, const int *origin);
+/* A rigid motion in PHYSICAL space applied to a mesh stored in INDEX space (ns3d_voxelize's tri layout; a rotation is not rigid in
+ * index space when the spacings differ).  R is a 3x3 matrix, row-major; pivot and shift are in index units; spacing = dx, dy, dz.  Per
+ * vertex p and output component a, with q_b = (p_b - pivot_b)*d_b, all fp64, nothing contracted, the quotient the plain IEEE one:
+ *   out_a = (pivot_a + shift_a) + ((R[a][0]*q_x + R[a][1]*q_y) + R[a][2]*q_z) / d_a
+ * As NumPy, for P of shape (n, 3): q = (P - pivot)*d;  out = (pivot + shift) + ((R[:,0]*q[:,:1] + R[:,1]*q[:,1:2]) + R[:,2]*q[:,2:])/d.
+ * STRICT, NS3D_IEEE_DIV and FAST contexts return the same bits.  Coordinates that are not finite propagate (ns3d_voxelize ignores such
+ * triangles).  out == tri is allowed (a vertex is read whole before it is stored); any other overlap of the two ranges of 72*n_tri
+ * bytes is refused.  n_tri == 0 is a no-op that returns NS3D_OK (out and tri may then be NULL).  Device memory only; enqueued on the
+ * context's stream, no scratch, no read-back.  A pose is applied to the ORIGINAL mesh with the accumulated rotation and shift, never
+ * to the previous pose's output: a mask at step s then does not depend on how many steps preceded it.
+ * NS3D_ERR_ARG, with nothing written: a null context; n_tri < 0; a null R, pivot, shift or spacing; one of their numbers not finite; a
+ * spacing not > 0; a null out or tri with n_tri > 0; buffers that overlap without being equal. */
+int ns3d_mesh_transform(ns3d_ctx *, double *out, const double *tri, long long n_tri, const double *R, const double *pivot,
+                        const double *shift, const double *spacing);
 
 #define NS3D_DECL(T, S)                                                                                     \
     /* One sample: per cell and slot S = S + weight·term, term = u, v, w, p, u·u, v·v, w·w, u·v, u·w, v·w, p·p evaluated in   \
@@ -702,6 +729,30 @@ int ns3d_voxelize(ns3d_ctx *, unsigned char *mask, const double *tri, long long 
      * the call blocks for this read-back like ns3d_max_abs.  NS3D_ERR_ARG: a null context or pointer, a grid below 3x3x3. */            \
     int ns3d_solid_momentum_##S(ns3d_ctx *, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny, int nz,    \
                                 const int *seam_lo, const int *seam_hi, double *mom_host, long long *n_host);                           \
+    /* ns3d_set_solid for a body in rigid motion: the bits, the valid ranges and the treatment of bits at invalid points are its own,   \
+     * C = 1 where bit 0 is set (C may be NULL), and where a velocity bit is set the store is the body's velocity at that node.         \
+     * motion = U[3], omega[3], centre[3] (centre in index space); origin (may be NULL: zeros) as ns3d_voxelize.  A node's position is  \
+     * X = (i+origin_x)+s_x, ... with the stagger s of ns3d_voxelize (exact).  All in fp64, nothing contracted, converted ONCE to T:    \
+     *   rx = (X - cx)*dx;  ry = (Y - cy)*dy;  rz = (Z - cz)*dz                                                                         \
+     *   vbx = Ux + (wy*rz - wz*ry);  vby = Uy + (wz*rx - wx*rz);  vbz = Uz + (wx*ry - wy*rx)                                           \
+     *   Vx[node] = (T)vbx (bit 1)    Vy[node] = (T)vby (bit 2)    Vz[node] = (T)vbz (bit 3)                                            \
+     * As NumPy, for Vx with I, J, K = ogrid of its shape: rz = ((K+oz)+.5 - cz)*dz; ry = ((J+oy)+.5 - cy)*dy;                          \
+     *   Vx[bit1] = (Ux + (wy*rz - wz*ry)).astype(T)[bit1]  (tests/moving_ref.py is this statement).                                   \
+     * STRICT, NS3D_IEEE_DIV and FAST contexts return the same bits.  Two consequences: with U = omega = +0.0 every store is +0.0      \
+     * (0 + (±0 − ±0) is +0 in round-to-nearest), so the call returns ns3d_set_solid's bits; and vbx does not depend on X, vby not on  \
+     * Y, vbz not on Z, so the two faces of a cell in each direction hold identical bits and ns3d_update_divV is exactly +0.0 in every \
+     * cell whose six faces are masked, in both element types.  Enqueued on the context's stream, no read-back.                        \
+     * NS3D_ERR_ARG, with nothing written: the cases of ns3d_set_solid; a null motion; one of the nine numbers or a spacing not finite; \
+     * a spacing not > 0; a negative origin entry; a grid below 3x3x3. */                                                              \
+    int ns3d_set_solid_moving_##S(ns3d_ctx *, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, const double *motion, double dx,    \
+                                  double dy, double dz, const int *origin, int nx, int ny, int nz);                                     \
+    /* ns3d_solid_momentum for a body in rigid motion: per direction the sum of (double)V[node] - (double)(T)vb over the owned masked   \
+     * nodes — exactly what the next ns3d_set_solid_moving with the same motion removes — and the same counts.  The same fixed order,  \
+     * the same scratch and the same read-back: two calls return the same bits, and zero motion returns ns3d_solid_momentum's bits.     \
+     * NS3D_ERR_ARG: the cases of ns3d_solid_momentum and the motion, spacing and origin cases of ns3d_set_solid_moving. */             \
+    int ns3d_solid_momentum_moving_##S(ns3d_ctx *, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny,    \
+                                       int nz, const int *seam_lo, const int *seam_hi, double *mom_host, long long *n_host,             \
+                                       const double *motion, double dx, double dy, double dz, const int *origin);                       \
     /* update_∇V!(∇V,Vx,Vy,Vz,dx,dy,dz)                             multi.jl:61-64   gpu.jl:194-197 */        \
     int ns3d_update_divV_##S(ns3d_ctx *, T *divV, const T *Vx, const T *Vy, const T *Vz, double dx,          \
                              double dy, double dz, int nx, int ny, int nz);                                  \

@@ -326,6 +326,32 @@ int ns3d_set_obstacle(ns3d_ctx *c, const unsigned char *mask)
 }
 const unsigned char *ns3d_obstacle(const ns3d_ctx *c) { return c ? c->obstacle : nullptr; }
 
+int ns3d_set_obstacle_motion(ns3d_ctx *c, const double *motion9, const int *origin)
+{
+    if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_obstacle_motion: null context");
+    if (!motion9) {
+        c->motion_on = 0;
+        for (int q = 0; q < 9; ++q) c->motion[q] = 0.0;
+        for (int q = 0; q < 3; ++q) c->motion_origin[q] = 0;
+        return NS3D_OK;
+    }
+    for (int q = 0; q < 9; ++q)
+        if (!std::isfinite(motion9[q])) return fail(NS3D_ERR_ARG, "ns3d_set_obstacle_motion: motion[%d] = %g is not finite", q, motion9[q]);
+    if (origin && (origin[0] < 0 || origin[1] < 0 || origin[2] < 0))
+        return fail(NS3D_ERR_ARG, "ns3d_set_obstacle_motion: origin %d, %d, %d (each >= 0)", origin[0], origin[1], origin[2]);
+    c->motion_on = 1;
+    for (int q = 0; q < 9; ++q) c->motion[q] = motion9[q];
+    for (int q = 0; q < 3; ++q) c->motion_origin[q] = origin ? origin[q] : 0;
+    return NS3D_OK;
+}
+int ns3d_obstacle_motion(const ns3d_ctx *c, double *out9)
+{
+    if (!c) return -1;
+    if (c->motion_on && out9)
+        for (int q = 0; q < 9; ++q) out9[q] = c->motion[q];
+    return c->motion_on;
+}
+
 int ns3d_set_turbulence(ns3d_ctx *c, int model, double length, void *mu_e)
 {
     if (!c) return fail(NS3D_ERR_ARG, "ns3d_set_turbulence: null context");
@@ -1190,6 +1216,45 @@ extern "C" int ns3d_voxelize(ns3d_ctx *c, unsigned char *mask, const double *tri
     const int rc = c->solid_dev.reserve(ns3d_solid::voxelize_scratch_bytes(nx, ny, nz), ns3d_drain_stream(c));
     if (rc) return rc;
     return finish(c, ns3d_solid::voxelize(c->stream, mask, tri, n_tri, nx, ny, nz, o, c->solid_dev.ptr), "voxelize");
+}
+// the checks ns3d_set_solid_moving and ns3d_solid_momentum_moving share, and the kernels' form of what they take
+static int make_motion(const char *fn, const double *motion, double dx, double dy, double dz, const int *origin, ns3d_solid::Motion *mo)
+{
+    if (!motion) return fail(NS3D_ERR_ARG, "%s: null motion", fn);
+    for (int q = 0; q < 9; ++q)
+        if (!std::isfinite(motion[q])) return fail(NS3D_ERR_ARG, "%s: motion[%d] = %g is not finite", fn, q, motion[q]);
+    if (!(std::isfinite(dx) && std::isfinite(dy) && std::isfinite(dz) && dx > 0.0 && dy > 0.0 && dz > 0.0))
+        return fail(NS3D_ERR_ARG, "%s: spacings %g, %g, %g (each finite and > 0)", fn, dx, dy, dz);
+    const int zero[3] = {0, 0, 0};
+    const int *o = origin ? origin : zero;
+    if (o[0] < 0 || o[1] < 0 || o[2] < 0) return fail(NS3D_ERR_ARG, "%s: origin %d, %d, %d (each >= 0)", fn, o[0], o[1], o[2]);
+    for (int q = 0; q < 3; ++q) { mo->U[q] = motion[q]; mo->w[q] = motion[3 + q]; mo->c[q] = motion[6 + q]; mo->o[q] = o[q]; }
+    mo->d[0] = dx; mo->d[1] = dy; mo->d[2] = dz;
+    return NS3D_OK;
+}
+extern "C" int ns3d_mesh_transform(ns3d_ctx *c, double *out, const double *tri, long long n_tri, const double *R, const double *pivot,
+                                   const double *shift, const double *spacing)
+{
+    CHECK_CTX(c);
+    if (n_tri < 0) return fail(NS3D_ERR_ARG, "%s: n_tri = %lld is negative", __func__, n_tri);
+    if (n_tri > 4ll * 0x7fffffffll) return fail(NS3D_ERR_ARG, "%s: n_tri = %lld exceeds one launch (4 x 2^31 triangles)", __func__, n_tri);
+    if (!R || !pivot || !shift || !spacing) return fail(NS3D_ERR_ARG, "%s: null R, pivot, shift or spacing", __func__);
+    for (int q = 0; q < 9; ++q)
+        if (!std::isfinite(R[q])) return fail(NS3D_ERR_ARG, "%s: R[%d] = %g is not finite", __func__, q, R[q]);
+    for (int q = 0; q < 3; ++q) {
+        if (!(std::isfinite(pivot[q]) && std::isfinite(shift[q])))
+            return fail(NS3D_ERR_ARG, "%s: pivot[%d] = %g, shift[%d] = %g (need finite values)", __func__, q, pivot[q], q, shift[q]);
+        if (!(std::isfinite(spacing[q]) && spacing[q] > 0.0))
+            return fail(NS3D_ERR_ARG, "%s: spacing[%d] = %g (finite and > 0)", __func__, q, spacing[q]);
+    }
+    if (n_tri == 0) return NS3D_OK;
+    if (!out || !tri) return fail(NS3D_ERR_ARG, "%s: null %s with n_tri = %lld", __func__, out ? "tri" : "out", n_tri);
+    if (out != tri) {
+        const uintptr_t a = (uintptr_t)out, b = (uintptr_t)tri, len = (uintptr_t)n_tri * 9 * sizeof(double);
+        if (a < b + len && b < a + len)
+            return fail(NS3D_ERR_ARG, "%s: out and tri overlap (in place, out == tri, or apart)", __func__);
+    }
+    return finish(c, ns3d_solid::mesh_transform(c->stream, out, tri, n_tri, R, pivot, shift, spacing), "mesh_transform");
 }
 extern "C" int ns3d_poisson_direct_f64(ns3d_ctx *, double *, double *, const double *, const ns3d_pt_params *);      // ns3d_direct.hip
 extern "C" int ns3d_poisson_direct_f32(ns3d_ctx *, float *, float *, const float *, const ns3d_pt_params *);

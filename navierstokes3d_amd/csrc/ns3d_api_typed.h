@@ -67,6 +67,36 @@ extern "C" int NS3D_FN(solid_momentum)(ns3d_ctx *c, const T *Vx, const T *Vy, co
     }
     return NS3D_OK;
 }
+// moving bodies: the same two with a rigid motion (make_motion checks it: nothing is enqueued on a refusal)
+extern "C" int NS3D_FN(set_solid_moving)(ns3d_ctx *c, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, const double *motion, double dx,
+                                         double dy, double dz, const int *origin, int nx, int ny, int nz)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, mask); CHECK_GRID(nx, ny, nz, 3);
+    ns3d_solid::Motion mo;
+    if (const int rc = make_motion(__func__, motion, dx, dy, dz, origin, &mo)) return rc;
+    return finish(c, ns3d_solid::set_solid_moving<T>(c->stream, C, Vx, Vy, Vz, mask, mo, nx, ny, nz), "set_solid_moving");
+}
+extern "C" int NS3D_FN(solid_momentum_moving)(ns3d_ctx *c, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny,
+                                              int nz, const int *seam_lo, const int *seam_hi, double *mom_host, long long *n_host,
+                                              const double *motion, double dx, double dy, double dz, const int *origin)
+{
+    CHECK_CTX(c); CHECK_PTRS(Vx, Vy, Vz, mask, mom_host, n_host); CHECK_GRID(nx, ny, nz, 3);
+    ns3d_solid::Motion mo;
+    if (const int rc0 = make_motion(__func__, motion, dx, dy, dz, origin, &mo)) return rc0;
+    const int zero[3] = {0, 0, 0};
+    const int rc = c->solid_dev.reserve(ns3d_solid::momentum_scratch_bytes(nx, ny, nz), ns3d_drain_stream(c));
+    if (rc) return rc;
+    hipError_t e = ns3d_solid::momentum_moving<T>(c->stream, Vx, Vy, Vz, mask, mo, nx, ny, nz, seam_lo ? seam_lo : zero,
+                                                  seam_hi ? seam_hi : zero, c->solid_dev.ptr, c->key_dev);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(NS3D_ERR_HIP, "solid_momentum_moving launch: %s", hipGetErrorString(e)); }
+    HIPCHK(c, hipMemcpyAsync(c->key_host, c->key_dev, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int q = 0; q < 3; ++q) {
+        std::memcpy(&mom_host[q], &c->key_host[q], sizeof(double));
+        n_host[q] = (long long)c->key_host[3 + q];
+    }
+    return NS3D_OK;
+}
 extern "C" int NS3D_FN(update_divV)(ns3d_ctx *c, T *divV, const T *Vx, const T *Vy, const T *Vz, double dx, double dy, double dz, int nx,
                                     int ny, int nz)
 {
@@ -554,6 +584,8 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
     const bool maccormack = c->advection == NS3D_ADVECT_MACCORMACK;
     if (maccormack && p->faithful)
         return fail(NS3D_ERR_ARG, "ns3d_time_step: NS3D_ADVECT_MACCORMACK advects Vz: it needs faithful == 0");
+    if (c->motion_on && !c->obstacle)
+        return fail(NS3D_ERR_ARG, "ns3d_time_step: ns3d_set_obstacle_motion is set without a mask (ns3d_set_obstacle)");
     const int was = c->flags;
     c->flags |= NS3D_ASYNC;
     int rc = NS3D_OK;
@@ -561,6 +593,8 @@ extern "C" int NS3D_FN(time_step)(ns3d_ctx *c, ns3d_step_fields *f, const ns3d_s
     T *Vx = (T *)f->Vx, *Vy = (T *)f->Vy, *Vz = (T *)f->Vz, *Vxo = (T *)f->Vx_o, *Vyo = (T *)f->Vy_o, *Vzo = (T *)f->Vz_o;
     T *C = (T *)f->C, *Co = (T *)f->C_o, *Pr = (T *)f->Pr, *D = (T *)f->dPrdtau, *divV = (T *)f->divV;
     auto cylinder = [&]() -> int {          // multi.jl:249-281 (global coordinates) / gpu.jl:336-368 (local); ns3d_set_obstacle: the mask
+        if (c->motion_on)                   // ns3d_set_obstacle_motion: the body's own velocity where the mask is set
+            return NS3D_FN(set_solid_moving)(c, C, Vx, Vy, Vz, c->obstacle, c->motion, p->dx, p->dy, p->dz, c->motion_origin, nx, ny, nz);
         if (c->obstacle) return NS3D_FN(set_solid)(c, C, Vx, Vy, Vz, c->obstacle, nx, ny, nz);
         return p->script == NS3D_BC_MULTI
                    ? NS3D_FN(set_cylinder)(c, C, Vx, Vy, Vz, p->a2, p->b2, p->ox, p->oy, p->sinb, p->cosb, p->xco_g, p->yco_g, p->zco_g, p->lx,

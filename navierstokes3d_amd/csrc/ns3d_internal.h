@@ -77,6 +77,9 @@ struct ns3d_ctx {
     ns3d_scratch mc_hat;                    // ns3d_time_step under NS3D_ADVECT_MACCORMACK: stage 1's four complete fields
     ns3d_scratch solid_dev;                 // ns3d_voxelize's bit planes / ns3d_solid_momentum's partials (one stream orders both)
     const unsigned char *obstacle = nullptr; // ns3d_set_obstacle: the caller's mask ns3d_time_step masks with; null: the cylinder
+    int motion_on = 0;                      // ns3d_set_obstacle_motion: ns3d_time_step masks with ns3d_set_solid_moving and these copies
+    double motion[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   //   U, ω, the centre (index space)
+    int motion_origin[3] = {0, 0, 0};       //   the rank's origin
     int turbulence = 0;                     // ns3d_set_turbulence: the subgrid model of ns3d_time_step's predictor (NS3D_TURB_*)
     double turb_length = 0.0;               //   its length ℓ = C_s·Δ
     void *turb_mu_e = nullptr;              //   the caller's nx·ny·nz array the step writes μ_e to
@@ -282,4 +285,17 @@ size_t momentum_scratch_bytes(int nx, int ny, int nz);
 template <class T>
 hipError_t momentum(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, int nx, int ny, int nz,
                     const int *seam_lo, const int *seam_hi, void *scratch, unsigned long long *result);
+// moving bodies: a rigid motion as the kernels take it — U, ω, the centre (index space), the spacings and the rank's origin — checked by
+// the entry points; set_solid_moving / momentum_moving are set_solid / momentum with it; mesh_transform: out == tri or disjoint
+struct Motion {
+    double U[3], w[3], c[3], d[3];
+    int o[3];
+};
+template <class T>
+hipError_t set_solid_moving(hipStream_t s, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, const Motion &mo, int nx, int ny, int nz);
+template <class T>
+hipError_t momentum_moving(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, const Motion &mo, int nx, int ny,
+                           int nz, const int *seam_lo, const int *seam_hi, void *scratch, unsigned long long *result);
+hipError_t mesh_transform(hipStream_t s, double *out, const double *tri, long long n_tri, const double *R, const double *pivot,
+                          const double *shift, const double *spacing);
 }

@@ -1,6 +1,7 @@
 // ns3d_solid.hip — obstacles from triangle meshes (include/ns3d.h has the definitions): ns3d_voxelize turns a closed triangle surface
 // into the four staggered masks of set_cylinder!'s thread range, ns3d_set_solid stores what k_set_cylinder stores with the flags read
-// from such a mask, ns3d_solid_momentum sums what the next ns3d_set_solid removes.
+// from such a mask, ns3d_solid_momentum sums what the next ns3d_set_solid removes.  Moving bodies: ns3d_set_solid_moving stores a rigid
+// body's velocity where ns3d_set_solid stores zero, ns3d_solid_momentum_moving sums what it removes, ns3d_mesh_transform poses a mesh.
 //
 // Compiled ONCE, with -ffp-contract=off (build.py), like ns3d_tracers.hip: every decision of the voxelizer is a stated fp64
 // comparison, so STRICT, NS3D_IEEE_DIV and FAST contexts return the same bytes and there is no arithmetic mode to select.
@@ -358,10 +359,181 @@ hipError_t momentum(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, const 
     return hipGetLastError();
 }
 
+// ---- moving bodies: ns3d_set_solid_moving / ns3d_solid_momentum_moving / ns3d_mesh_transform.  The rigid-body velocity of a node is
+// the header's statement, operation for operation, in fp64 and never contracted; q picks the component and with it the node's stagger.
+__device__ __forceinline__ double body_velocity(int q, const Motion &m, int i, int j, int k)
+{
+    const double X = (double)((idx_t)i + m.o[0]) + (q == 0 ? 0.0 : 0.5);
+    const double Y = (double)((idx_t)j + m.o[1]) + (q == 1 ? 0.0 : 0.5);
+    const double Z = (double)((idx_t)k + m.o[2]) + (q == 2 ? 0.0 : 0.5);
+    const double rx = (X - m.c[0]) * m.d[0], ry = (Y - m.c[1]) * m.d[1], rz = (Z - m.c[2]) * m.d[2];
+    if (q == 0) return m.U[0] + (m.w[1] * rz - m.w[2] * ry);
+    if (q == 1) return m.U[1] + (m.w[2] * rx - m.w[0] * rz);
+    return m.U[2] + (m.w[0] * ry - m.w[1] * rx);
+}
+
+// k_set_solid's shape — 16 mask bytes per thread, one 16-byte load where the chunk is whole and aligned, out at once on an all-zero
+// chunk — with the body's velocity formed for the set bits only: the cost stays the read of the mask
+template <class T>
+__global__ __launch_bounds__(256) void k_set_solid_moving(T *__restrict__ C, T *__restrict__ Vx, T *__restrict__ Vy, T *__restrict__ Vz,
+                                                          const unsigned char *__restrict__ mask, const Motion mo, int nx, int ny, int nz,
+                                                          idx_t N, int lead)
+{
+    const idx_t c = (idx_t)blockIdx.x * 256 + threadIdx.x;
+    const idx_t b0 = 16 * c - lead;
+    if (b0 >= N) return;
+    unsigned long long lo = 0ull, hi = 0ull;
+    if (b0 >= 0 && b0 + 16 <= N) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(mask + b0);
+        lo = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+        hi = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+    } else {
+        for (int q = 0; q < 8; ++q) {
+            const idx_t b = b0 + q;
+            if (b >= 0 && b < N) lo |= (unsigned long long)mask[b] << (8 * q);
+            if (b + 8 >= 0 && b + 8 < N) hi |= (unsigned long long)mask[b + 8] << (8 * q);
+        }
+    }
+    if ((lo | hi) == 0ull) return;
+    const idx_t row = nx + 1, plane = row * (ny + 1);
+#pragma unroll 1
+    for (int q = 0; q < 16; ++q) {
+        const unsigned m = (unsigned)((q < 8 ? lo >> (8 * q) : hi >> (8 * (q - 8))) & 0xFFull);
+        if (!m) continue;
+        const idx_t b = b0 + q;
+        const int k = (int)(b / plane);
+        const idx_t rem = b - (idx_t)k * plane;
+        const int j = (int)(rem / row), i = (int)(rem - (idx_t)j * row);
+        const bool ci = i < nx, cj = j < ny, ck = k < nz;
+        if ((m & 1u) && C && ci && cj && ck) C[(idx_t)i + (idx_t)nx * ((idx_t)j + (idx_t)ny * k)] = (T)1.0;
+        if ((m & 2u) && cj && ck) Vx[(idx_t)i + (idx_t)(nx + 1) * ((idx_t)j + (idx_t)ny * k)] = (T)body_velocity(0, mo, i, j, k);
+        if ((m & 4u) && ci && ck) Vy[(idx_t)i + (idx_t)nx * ((idx_t)j + (idx_t)(ny + 1) * k)] = (T)body_velocity(1, mo, i, j, k);
+        if ((m & 8u) && ci && cj) Vz[(idx_t)i + (idx_t)nx * ((idx_t)j + (idx_t)ny * k)] = (T)body_velocity(2, mo, i, j, k);
+    }
+}
+
+template <class T>
+hipError_t set_solid_moving(hipStream_t s, T *C, T *Vx, T *Vy, T *Vz, const unsigned char *mask, const Motion &mo, int nx, int ny, int nz)
+{
+    const idx_t N = (idx_t)(nx + 1) * (ny + 1) * (nz + 1);
+    const int lead = (int)((size_t)mask & 15);
+    const idx_t chunks = (N + lead + 15) / 16;
+    hipLaunchKernelGGL(k_set_solid_moving<T>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, C, Vx, Vy, Vz, mask, mo, nx, ny, nz, N,
+                       lead);
+    return hipGetLastError();
+}
+
+// k_mom with the subtraction: each term is (double)V − (double)(T)vb, what the next ns3d_set_solid_moving removes from that node; the
+// ranges, the counts, the order of the sums and the partials' layout are k_mom's, and k_mom_final finishes both
+template <class T>
+__global__ __launch_bounds__(256) void k_mom_moving(const T *__restrict__ Vx, const T *__restrict__ Vy, const T *__restrict__ Vz,
+                                                    const unsigned char *__restrict__ mask, const MomGeom a, const Motion mo,
+                                                    unsigned long long *__restrict__ part)
+{
+    typedef unsigned long long u64;
+    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y;
+    const int kb = blockIdx.z * a.kz, ke = min(kb + a.kz, nz + 1);
+    double s[3] = {0.0, 0.0, 0.0};
+    u64 n[3] = {0, 0, 0};
+    if (i <= nx && j <= ny) {
+        const bool cx = i < nx, cy = j < ny;
+        const bool ox0 = i >= a.own[0][0][0] && i < a.own[0][0][1], ox1 = i >= a.own[0][1][0] && i < a.own[0][1][1];
+        const bool oy0 = j >= a.own[1][0][0] && j < a.own[1][0][1], oy1 = j >= a.own[1][1][0] && j < a.own[1][1][1];
+        const idx_t pM = (idx_t)(nx + 1) * (ny + 1), oM = (idx_t)i + (idx_t)(nx + 1) * j;
+        const idx_t pVx = (idx_t)(nx + 1) * ny, pVy = (idx_t)nx * (ny + 1), pC = (idx_t)nx * ny;
+        const idx_t oVx = (idx_t)i + (idx_t)(nx + 1) * j, oVy = (idx_t)i + (idx_t)nx * j;
+        for (int k = kb; k < ke; ++k) {
+            const unsigned m = mask[oM + pM * k];
+            if (!m) continue;
+            const bool oz0 = k >= a.own[2][0][0] && k < a.own[2][0][1], oz1 = k >= a.own[2][1][0] && k < a.own[2][1][1];
+            if ((m & 2u) && cy && k < nz && ox1 && oy0 && oz0) {
+                s[0] += (double)Vx[oVx + pVx * k] - (double)(T)body_velocity(0, mo, i, j, k); ++n[0];
+            }
+            if ((m & 4u) && cx && k < nz && ox0 && oy1 && oz0) {
+                s[1] += (double)Vy[oVy + pVy * k] - (double)(T)body_velocity(1, mo, i, j, k); ++n[1];
+            }
+            if ((m & 8u) && cx && cy && ox0 && oy0 && oz1) {
+                s[2] += (double)Vz[oVy + pC * k] - (double)(T)body_velocity(2, mo, i, j, k); ++n[2];
+            }
+        }
+    }
+    __shared__ u64 wpart[NS3D_MOM_SLOTS][4];
+    const int tid = threadIdx.x + 64 * threadIdx.y, w = tid >> 6;
+    u64 v[NS3D_MOM_SLOTS];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        v[q] = (u64)__double_as_longlong(wave_sum_f64(s[q]));
+        v[3 + q] = wave_sum_u64(n[q]);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NS3D_MOM_SLOTS; ++q) wpart[q][w] = v[q];
+    }
+    __syncthreads();
+    if (tid < NS3D_MOM_SLOTS) {
+        u64 r = wpart[tid][0];
+        for (int q = 1; q < 4; ++q) r = mom_combine(tid, r, wpart[tid][q]);
+        const unsigned bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+        part[(size_t)tid * a.nblocks + bid] = r;
+    }
+}
+
+template <class T>
+hipError_t momentum_moving(hipStream_t s, const T *Vx, const T *Vy, const T *Vz, const unsigned char *mask, const Motion &mo, int nx, int ny,
+                           int nz, const int *seam_lo, const int *seam_hi, void *scratch, unsigned long long *result)
+{
+    MomGeom a;
+    a.nx = nx; a.ny = ny; a.nz = nz;
+    const int n[3] = {nx, ny, nz};
+    for (int d = 0; d < 3; ++d)
+        for (int st = 0; st < 2; ++st) {
+            a.own[d][st][0] = seam_lo[d] ? 1 + st : 0;
+            a.own[d][st][1] = seam_hi[d] ? n[d] + st - 1 : n[d] + st;
+        }
+    a.nblocks = ns3d_diag_geometry(nx, ny, nz, &a.kz);
+    const dim3 blk(64, 4, 1);
+    const dim3 grd((unsigned)((nx + 1 + 63) / 64), (unsigned)((ny + 1 + 3) / 4), (unsigned)((nz + 1 + a.kz - 1) / a.kz));
+    hipLaunchKernelGGL(k_mom_moving<T>, grd, blk, 0, s, Vx, Vy, Vz, mask, a, mo, (unsigned long long *)scratch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mom_final, dim3(NS3D_MOM_SLOTS), dim3(256), 0, s, (const unsigned long long *)scratch, a.nblocks, result);
+    return hipGetLastError();
+}
+
+// one thread per vertex: its three coordinates are read before any is stored, so out == tri is in order
+struct Pose {
+    double R[9], pivot[3], shift[3], d[3];
+};
+__global__ __launch_bounds__(256) void k_mesh_transform(double *out, const double *tri, idx_t n_vert, const Pose p)
+{
+    const idx_t v = (idx_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n_vert) return;
+    const double qx = (tri[3 * v] - p.pivot[0]) * p.d[0], qy = (tri[3 * v + 1] - p.pivot[1]) * p.d[1],
+                 qz = (tri[3 * v + 2] - p.pivot[2]) * p.d[2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        out[3 * v + a] = (p.pivot[a] + p.shift[a]) + ((p.R[3 * a] * qx + p.R[3 * a + 1] * qy) + p.R[3 * a + 2] * qz) / p.d[a];
+}
+
+hipError_t mesh_transform(hipStream_t s, double *out, const double *tri, long long n_tri, const double *R, const double *pivot,
+                          const double *shift, const double *spacing)
+{
+    Pose p;
+    for (int q = 0; q < 9; ++q) p.R[q] = R[q];
+    for (int q = 0; q < 3; ++q) { p.pivot[q] = pivot[q]; p.shift[q] = shift[q]; p.d[q] = spacing[q]; }
+    const idx_t n_vert = 3 * (idx_t)n_tri;
+    hipLaunchKernelGGL(k_mesh_transform, dim3((unsigned)((n_vert + 255) / 256)), dim3(256), 0, s, out, tri, n_vert, p);
+    return hipGetLastError();
+}
+
 #define INST(T)                                                                                                              \
     template hipError_t set_solid<T>(hipStream_t, T *, T *, T *, T *, const unsigned char *, int, int, int);                 \
     template hipError_t momentum<T>(hipStream_t, const T *, const T *, const T *, const unsigned char *, int, int, int,      \
-                                    const int *, const int *, void *, unsigned long long *);
+                                    const int *, const int *, void *, unsigned long long *);                                 \
+    template hipError_t set_solid_moving<T>(hipStream_t, T *, T *, T *, T *, const unsigned char *, const Motion &, int, int, int); \
+    template hipError_t momentum_moving<T>(hipStream_t, const T *, const T *, const T *, const unsigned char *, const Motion &, int, int, \
+                                           int, const int *, const int *, void *, unsigned long long *);
 INST(double)
 INST(float)
 #undef INST

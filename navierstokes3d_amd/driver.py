@@ -194,7 +194,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
                        temporal=True, dtype=torch.float64, faithful=True, grid=None, device=None, niter_cap=None,
                        return_info=False, shape=None, pressure="pt", wide_advect_halo=False, one_call=True, diagnostics=False,
                        statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None, advection="reference",
-                       obstacle=None, turbulence=None, scalar=None):
+                       obstacle=None, turbulence=None, scalar=None, motion=None):
     """run_navierstokes3D (multi.jl:287-536).  nx is the LOCAL streamwise size (ny = nz = ceil(0.6 nx) local).
     `grid` decides the decomposition: None = one rank; a halo.ZSlabGrid = this process is one z-slab rank of an
     initialised torch.distributed group; a mgpu.MgpuGrid = the C-ABI grid (this process drives every local rank of an
@@ -286,10 +286,23 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     The body's C = 1 is re-imposed by the masking that follows: a Dirichlet wall.  info.scalar gets kappa, sct, bg and c_ref.  A
     run whose dt·kappa·(1/dx² + 1/dy² + 1/dz²) exceeds 1/2 is refused; with diagnostics=True and a model, so is a step whose
     dt·(kappa + (mu_e_max − μ)/(ρ·sct))·(1/dx² + 1/dy² + 1/dz²) does.  One rank: anything else raises Ns3dError before anything is
-    allocated."""
+    allocated.
+    motion=… (default None: the body stands still, not one extra call; OUTSIDE the reference): the rigid motion of the body —
+    dict(velocity=(0,0,0), omega=(0,0,0), centre=…) for a steady one (solid.rigid_motion: physical velocity and angular velocity,
+    the centre of rotation at t = 0 in index space), or any callable pose(t) → (R, shift, U, omega, centre) of that shape.  The pose
+    is evaluated at t = s·dt for the steps s = 1, 2, … (and at t = 0 for :372), and every masking stores the body's own velocity
+    U + omega × r where it stored zero (ns3d_set_solid_moving) — with `one_call` inside ns3d_time_step (Context.set_obstacle_motion,
+    set per step), otherwise as that call at the same two places; the same bits either way.  With `obstacle` given as triangles the
+    original mesh stays on the device and, whenever the pose differs from the previous step's, the mask is rebuilt into the SAME
+    buffer (ns3d_mesh_transform of the original mesh, ns3d_voxelize).  With `obstacle` None (the cylinder, through
+    solid.mask_of_cylinder) or a uint8 mask, the mask is fixed and only the velocity is imposed — a body of revolution spinning about
+    its axis — and a pose with a non-zero shift raises.  With diagnostics=True the two removed-momentum terms of force come from
+    ns3d_solid_momentum_moving.  info.motion gets one dict per step: t, R, shift, U, omega, centre, rebuilt.  One rank: anything
+    else, an unknown key or a number that is not finite raises Ns3dError before anything is allocated."""
     _check_advection(advection)
     _check_turbulence(turbulence)
     _check_scalar(scalar)
+    _check_motion(motion)
     if pressure not in ("pt", "direct"):
         raise L.Ns3dError("pressure = %r (\"pt\" | \"direct\")" % (pressure,))
     if device is None:
@@ -304,6 +317,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     maccormack = _check_advection(advection, faithful, P)
     les = _check_turbulence(turbulence, P)
     sca = _check_scalar(scalar, P, multi_params(nx, dims=dims, coords=grid.local_coords[0], **shape))
+    _check_motion(motion, P)
     # the contexts of the ns3d_mgpu's ranks (their devices), or this rank's own
     ctxs = list(grid.contexts) if grid.contexts is not None else [K.Context(device, mode, async_=True)]
     ps = [multi_params(nx, dims=dims, coords=c3, **shape) for c3 in grid.local_coords]
@@ -329,8 +343,13 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     grid.update_halo(col("Pr"))                                                               # :371
     cyls = [(q.a2, q.b2, q.ox, q.oy, q.sinb, q.cosb, q.xco_g, q.yco_g, q.zco_g, q.lx, q.ly, q.lz, q.dx, q.dy, q.dz)
             for q in ps]
-    solid = _obstacle_mask(obstacle, P, ctxs[0], (nx, ny, nz))
-    body = _body(solid)
+    solid, mesh = _obstacle_mask(obstacle, P, ctxs[0], (nx, ny, nz))
+    mov = None
+    if motion is not None:
+        mov = _motion_start(motion, mesh, solid, ctxs[0], p, cyls[0], dtype, nt)
+        solid = mov.mask
+        _motion_pose(mov, 0, record=False)
+    body = _body(solid, mov)
     for f, c, cyl in zip(fs, ctxs, cyls):
         body(f, cyl, c)                                                                       # :372
     grid.update_halo(col("C"), col("Vx"), col("Vy"), col("Vz"))                               # :373
@@ -375,7 +394,7 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
             raise L.Ns3dError("diagnostics on %d ranks needs the C-ABI grid (mgpu.MgpuGrid)" % P)
         info.diag = []
         monitor = _monitor(grid, ctxs, fs, cyls if solid is None else [None], p)
-    removed = _removed(monitor, solid, fs, ctxs)
+    removed = _removed(monitor, solid, fs, ctxs, mov)
     obs.start()
     nsave = nvis = 10                                                                         # :330,332
     # :450's halo update of the normal stresses may only go with the stress arrays where the interior planes two ranks both compute
@@ -400,6 +419,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
     elif maccormack:
         hats = _alloc_hats(fs[0], ctxs[0])
     for it in range(1, nt + 1):                                                               # :446
+        if mov is not None:
+            _motion_pose(mov, it, step_params is not None)
         if step_params is not None:                             # :449-477 (ns3d_time_step swaps the names in fs[0] like the swaps below)
             step_params.write_stress = 1 if it == nt else 0     # the stress arrays as the reference leaves them after its last step
             done, errs = K.time_step(fs[0], step_params, ctx=ctxs[0])
@@ -498,6 +519,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         frame(do_save and it % nsave == 0, do_vis and it % nvis == 0)
     if maccormack and step_params is not None:
         ctxs[0].set_advection("reference")
+    if mov is not None and step_params is not None:
+        ctxs[0].set_obstacle_motion(None)
     if solid is not None and step_params is not None:
         ctxs[0].set_obstacle(None)
     if les is not None:
@@ -514,6 +537,8 @@ def run_navierstokes3D(do_vis=False, do_save=False, do_print=False, nx=255, nt=1
         info.turbulence = dict(model=les.model, length=les.length, mu_e=K.to_numpy(les.mu_e))
     if sca is not None:
         info.scalar = dict(kappa=sca.kappa, sct=sca.sct, bg=sca.bg, c_ref=sca.c_ref)
+    if mov is not None:
+        info.motion = mov.log
     info.fields = fs[0]
     info.local_fields = fs
     info.ctx = ctxs[0]
@@ -545,10 +570,10 @@ def _copy_advect_swap(f, p, faithful, ctx):
 
 
 def _obstacle_mask(obstacle, P, ctx, n):
-    """the `obstacle` keyword of both drivers → None (the cylinder) or the uint8 device mask of the cell grid n; raises before anything
-    is advanced"""
+    """the `obstacle` keyword of both drivers → (mask, tri): mask None (the cylinder) or the uint8 device mask of the cell grid n;
+    tri the (n,3,3) host array the mask was voxelized from, None for a ready mask; raises before anything is advanced"""
     if obstacle is None:
-        return None
+        return None, None
     if P != 1:
         raise L.Ns3dError("obstacle= runs on one rank (this grid has %d): the ranks of a decomposed grid voxelize with their own origin "
                           "through solid.voxelize" % P)
@@ -562,27 +587,105 @@ def _obstacle_mask(obstacle, P, ctx, n):
         tri = np.asarray(obstacle, dtype=np.float64)
         if tri.ndim != 3 or tri.shape[1:] != (3, 3):
             raise L.Ns3dError("obstacle: an (n,3,3) array of triangles in index space, or a uint8 mask; got shape %r" % (tri.shape,))
-        return S.voxelize(ctx, tri, *n)
+        return S.voxelize(ctx, tri, *n), tri
     if mask.numel() != nbytes:
         raise L.Ns3dError("obstacle: the mask has %d bytes, a %dx%dx%d grid needs %d" % ((mask.numel(),) + tuple(n) + (nbytes,)))
     ctx.after_torch_fill()
-    return mask
+    return mask, None
 
 
-def _body(solid):
-    """what stands where the reference calls set_cylinder!: the cylinder's analytic test, or ns3d_set_solid with the obstacle's mask"""
+def _body(solid, mov=None):
+    """what stands where the reference calls set_cylinder!: the cylinder's analytic test, ns3d_set_solid with the obstacle's mask, or
+    — under `motion` — ns3d_set_solid_moving with the mask and the current pose's numbers"""
+    if mov is not None:
+        return lambda f, cyl, c: K.set_solid_moving(f.C, f.Vx, f.Vy, f.Vz, mov.mask, mov.motion9, *mov.spacing, ctx=c)
     if solid is None:
         return lambda f, cyl, c: K.set_cylinder(f.C, f.Vx, f.Vy, f.Vz, *cyl, ctx=c)
     return lambda f, cyl, c: K.set_solid(f.C, f.Vx, f.Vy, f.Vz, solid, ctx=c)
 
 
-def _removed(monitor, solid, fs, ctxs):
-    """diagnostics=True: the momentum the next masking call removes — the monitor's masked sums, or ns3d_solid_momentum for an obstacle"""
+def _removed(monitor, solid, fs, ctxs, mov=None):
+    """diagnostics=True: the momentum the next masking call removes — the monitor's masked sums, ns3d_solid_momentum for an obstacle,
+    ns3d_solid_momentum_moving for one in motion"""
     if monitor is None:
         return None
+    if mov is not None:
+        return lambda: K.solid_momentum_moving(fs[0].Vx, fs[0].Vy, fs[0].Vz, mov.mask, mov.motion9, *mov.spacing, ctx=ctxs[0])[0]
     if solid is None:
         return lambda: monitor(False).mom
     return lambda: K.solid_momentum(fs[0].Vx, fs[0].Vy, fs[0].Vz, solid, ctx=ctxs[0])[0]
+
+
+MOTION_KEYS = ("velocity", "omega", "centre")
+
+
+def _check_motion(motion, P=1):
+    """the `motion` keyword of both drivers: None, a dict of MOTION_KEYS (centre is required) or a callable; raises before anything is
+    allocated"""
+    if motion is None:
+        return
+    if isinstance(motion, dict):
+        if set(motion) - set(MOTION_KEYS) or "centre" not in motion:
+            raise L.Ns3dError("motion = %r (None | dict(velocity=…, omega=…, centre=…) with centre given | a callable pose(t))" % (motion,))
+        for k, v in motion.items():
+            a = np.asarray(v, dtype=np.float64).reshape(-1)
+            if a.size != 3 or not np.isfinite(a).all():
+                raise L.Ns3dError("motion: %s = %r (need 3 finite numbers)" % (k, v))
+    elif not callable(motion):
+        raise L.Ns3dError("motion = %r (None | dict(velocity=…, omega=…, centre=…) | a callable pose(t))" % (motion,))
+    if P != 1:
+        raise L.Ns3dError("motion= runs on one rank (this grid has %d): the ranks of a decomposed grid call ns3d_set_solid_moving with "
+                          "their own origin" % P)
+
+
+def _motion_start(motion, mesh, solid, ctx, p, cyl, dtype, nt):
+    """What a run under `motion` keeps: the poses of t = s·dt, s = 0 … nt, evaluated and checked HERE — before a knob of the context
+    is set, so that a pose that is refused leaves the context as it was —, the spacings, the mask buffer every pose is voxelized into
+    (`solid`, or the cylinder's own mask when there is no obstacle) and, for an obstacle given as triangles (`mesh`), the original
+    mesh and a work buffer on the device."""
+    from . import solid as S
+    spacing = (p.dx, p.dy, p.dz)
+    pose = S.rigid_motion(spacing=spacing, **motion) if isinstance(motion, dict) else motion
+    poses = []
+    for s in range(nt + 1):
+        t = s * p.dt
+        R, shift, U, omega, centre = (np.array(v, dtype=np.float64) for v in pose(t))
+        if R.shape != (3, 3) or any(v.shape != (3,) for v in (shift, U, omega, centre)) or \
+                not all(np.isfinite(v).all() for v in (R, shift, U, omega, centre)):
+            raise L.Ns3dError("motion: pose(%r) must return finite R (3x3), shift, U, omega, centre (3 each)" % (t,))
+        if mesh is None and np.any(shift != 0.0):
+            raise L.Ns3dError("motion: a shift of %r at t = %r needs the obstacle as triangles; a mask (or the cylinder) stays where it is "
+                              "and only takes the body's velocity" % (tuple(shift), t))
+        poses.append(dict(t=t, R=R, shift=shift, U=U, omega=omega, centre=centre))
+    mov = SimpleNamespace(poses=poses, spacing=spacing, n=(p.nx, p.ny, p.nz), ctx=ctx, tri0=None, posed=None, motion9=None, log=[],
+                          last=(np.eye(3), np.zeros(3)))         # the pose the mask holds: the mesh as given
+    if solid is None:
+        solid = S.mask_of_cylinder(ctx, mov.n, *cyl, dtype=dtype)
+    if mesh is not None:
+        mov.tri0 = torch.from_numpy(S.tri_array(mesh).reshape(-1)).to(solid.device)
+        mov.posed = torch.empty_like(mov.tri0)
+        ctx.after_torch_fill()
+    mov.mask = solid
+    return mov
+
+
+def _motion_pose(mov, s, knob=False, record=True):
+    """The pose of step s (0: before the loop): logged, its nine numbers (U, omega, centre) made current for the masking calls — and,
+    with knob, for ns3d_time_step; the mask is rebuilt in place (the ORIGINAL mesh transformed, then voxelized) when the pose differs
+    from the one the mask holds."""
+    from . import solid as S
+    q = mov.poses[s]
+    R, shift = q["R"], q["shift"]
+    rebuilt = False
+    if mov.tri0 is not None and not (np.array_equal(R, mov.last[0]) and np.array_equal(shift, mov.last[1])):
+        S.transform(mov.ctx, mov.tri0, R, q["centre"] - shift, shift, mov.spacing, out=mov.posed)     # about the centre the mesh came with
+        K.voxelize(mov.mask, mov.posed, mov.n, ctx=mov.ctx)
+        mov.last, rebuilt = (R, shift), True
+    mov.motion9 = tuple(q["U"]) + tuple(q["omega"]) + tuple(q["centre"])
+    if record:
+        mov.log.append(dict(q, rebuilt=rebuilt))
+    if knob:
+        mov.ctx.set_obstacle_motion(mov.motion9)
 
 
 def _check_advection(advection, faithful=False, P=1):
@@ -761,7 +864,7 @@ def _save_mat(path, f, p, step0):
 def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused=True, dtype=torch.float64,
           faithful=True, device=None, niter_cap=None, do_print=False, initial=None, pressure="pt", one_call=True,
           diagnostics=False, statistics=None, stats_every=1, vortex=False, tracers=None, probes=None, isosurface=None,
-          advection="reference", obstacle=None, turbulence=None, scalar=None):
+          advection="reference", obstacle=None, turbulence=None, scalar=None, motion=None):
     """runme (gpu.jl:12-173): single device, gravity, hydrostatic x-planes.  Returns (fields, info).
     nx/nt are literals in the reference (gpu.jl:44,51: 255, 10000) and keyword options here.  do_save writes the MAT files
     of gpu.jl:89,168-170 (step 0 and every nsave = 10 steps); do_vis the heat maps of gpu.jl:90-117,143-167 (frame 0 and
@@ -781,10 +884,12 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     advection: as in run_navierstokes3D, in place of :141-142; "maccormack" needs faithful=False.
     obstacle: as in run_navierstokes3D, in place of the set_cylinder! calls :123 and :139.
     turbulence: as in run_navierstokes3D, in place of :121-122.
-    scalar: as in run_navierstokes3D, between :122 and :123."""
+    scalar: as in run_navierstokes3D, between :122 and :123.
+    motion: as in run_navierstokes3D, at the set_cylinder! calls :123 and :139 (gpu.jl masks nothing before its loop)."""
     maccormack = _check_advection(advection, faithful)
     les = _check_turbulence(turbulence)
     sca = _check_scalar(scalar, 1, gpu_params(nx))
+    _check_motion(motion)
     if device is None:
         device = torch.cuda.current_device()
     p = gpu_params(nx)
@@ -802,8 +907,12 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     cyl = (p.a2, p.b2, p.ox, p.oy, p.sinb, p.cosb, p.lx, p.ly, p.lz, p.dx, p.dy, p.dz)
     pt = K.pt_params(f.Pr, p.rho, p.dt, p.dtau, p.damp, p.dx, p.dy, p.dz, L.NS3D_BC_GPU, False, 0.0, p.g)
     info = SimpleNamespace(iters=[], errs=[], params=p)
-    solid = _obstacle_mask(obstacle, 1, ctx, (nx, ny, nz))
-    body = _body(solid)
+    solid, mesh = _obstacle_mask(obstacle, 1, ctx, (nx, ny, nz))
+    mov = None
+    if motion is not None:
+        mov = _motion_start(motion, mesh, solid, ctx, p, cyl, dtype, nt)
+        solid = mov.mask
+    body = _body(solid, mov)
     nsave = nvis = 10                                                                         # :50,52
     obs = Observers(grid, [ctx], p, nt, dtype, gathered=False, **watch)
     iframe = 0
@@ -829,7 +938,7 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     if diagnostics:
         info.diag = []
         monitor = _monitor(grid, [ctx], [f], [cyl if solid is None else None], p)
-    removed = _removed(monitor, solid, [f], [ctx])
+    removed = _removed(monitor, solid, [f], [ctx], mov)
     obs.start()
     step_params = None
     if fused and one_call and not diagnostics:
@@ -846,6 +955,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
     elif maccormack:
         hats = _alloc_hats(f, ctx)
     for it in range(1, nt + 1):                                                               # :119
+        if mov is not None:
+            _motion_pose(mov, it, step_params is not None)
         if step_params is not None:                         # :121-142 (ns3d_time_step swaps the names in f like the swaps below)
             step_params.write_stress = 1 if it == nt else 0
             done, errs = K.time_step(f, step_params, ctx=ctx)
@@ -909,6 +1020,8 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
             drawn()
         if do_save and it % nsave == 0:                                                       # :168-170
             saved(it)
+    if mov is not None and step_params is not None:
+        ctx.set_obstacle_motion(None)
     if solid is not None and step_params is not None:
         ctx.set_obstacle(None)
     if les is not None:
@@ -924,4 +1037,6 @@ def runme(do_vis=False, do_save=False, *, nx=255, nt=10000, mode="strict", fused
         info.turbulence = dict(model=les.model, length=les.length, mu_e=K.to_numpy(les.mu_e))
     if sca is not None:
         info.scalar = dict(kappa=sca.kappa, sct=sca.sct, bg=sca.bg, c_ref=sca.c_ref)
+    if mov is not None:
+        info.motion = mov.log
     return f, info

@@ -218,6 +218,20 @@ class Context:
         """the device address ns3d_time_step masks with; None: the cylinder"""
         return self.lib.ns3d_obstacle(self.handle)
 
+    def set_obstacle_motion(self, motion, origin=None):
+        """The rigid motion of the obstacle ns3d_time_step masks with: 9 numbers (U, omega, centre; the centre in index space) — the
+        step then stores the body's velocity where the mask is set (set_solid_moving at both masking places) — or None: the static
+        obstacle.  The context copies the numbers.  Needs set_obstacle; the single calls do not read it."""
+        if motion is None:
+            L.check(self.lib.ns3d_set_obstacle_motion(self.handle, None, None))
+        else:
+            L.check(self.lib.ns3d_set_obstacle_motion(self.handle, _motion9(motion), _int3(origin)))
+
+    def obstacle_motion(self):
+        """the nine numbers of set_obstacle_motion as a tuple; None: no motion set"""
+        out = (C.c_double * 9)()
+        return tuple(out) if int(self.lib.ns3d_obstacle_motion(self.handle, out)) == 1 else None
+
     def set_turbulence(self, model, length=0.0, mu_e=None):
         """The subgrid model of ns3d_time_step's predictor: None / "none" (the default: the scalar μ, not one extra call) or
         "smagorinsky" | "wale" | "vreman" with length = C·Δ (C_s, C_w, √c_v) and mu_e, a column-major (nx,ny,nz) tensor of the step's
@@ -485,6 +499,51 @@ def solid_momentum(Vx, Vy, Vz, mask, seam_lo=None, seam_hi=None, ctx=None):
     _ctx(ctx, Vx).call("solid_momentum", Vx, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), _chk_mask(mask, (nx, ny, nz), Vx), nx, ny, nz,
                        _int3(seam_lo), _int3(seam_hi), mom, cnt)
     return tuple(mom), tuple(int(q) for q in cnt)
+
+
+def _motion9(motion):
+    """U, omega, centre (9 numbers, any nesting) as the C array the moving calls take"""
+    m = np.asarray(motion, dtype=np.float64).reshape(-1)
+    if m.size != 9:
+        raise L.Ns3dError("motion holds 9 numbers (U, omega, centre), got %d" % m.size)
+    return (C.c_double * 9)(*m)
+
+
+def set_solid_moving(Cf, Vx, Vy, Vz, mask, motion, dx, dy, dz, origin=None, ctx=None):
+    """ns3d_set_solid_moving: set_solid for a body in rigid motion — where a velocity bit is set the store is the body's velocity at
+    that node, U + omega × r with r = (node − centre)·spacing (include/ns3d.h has the statement; motion = U, omega, centre, the centre
+    in index space).  Zero motion gives set_solid's bits.  Cf may be None.  Enqueues; no read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    _ctx(ctx, Vx).call("set_solid_moving", Vx, None if Cf is None else _chk(Cf, (nx, ny, nz), "C"), *_chk_V(Vx, Vy, Vz, (nx, ny, nz)),
+                       _chk_mask(mask, (nx, ny, nz), Vx), _motion9(motion), *_d(dx, dy, dz), _int3(origin), nx, ny, nz)
+
+
+def solid_momentum_moving(Vx, Vy, Vz, mask, motion, dx, dy, dz, origin=None, seam_lo=None, seam_hi=None, ctx=None):
+    """ns3d_solid_momentum_moving: (mom, n) as solid_momentum, each term less the body's own velocity at the node: what the next
+    set_solid_moving with this motion removes.  Blocks for the read-back."""
+    nx, ny, nz = Vx.shape[0] - 1, Vx.shape[1], Vx.shape[2]
+    mom, cnt = (C.c_double * 3)(), (C.c_longlong * 3)()
+    _ctx(ctx, Vx).call("solid_momentum_moving", Vx, *_chk_V(Vx, Vy, Vz, (nx, ny, nz)), _chk_mask(mask, (nx, ny, nz), Vx), nx, ny, nz,
+                       _int3(seam_lo), _int3(seam_hi), mom, cnt, _motion9(motion), *_d(dx, dy, dz), _int3(origin))
+    return tuple(mom), tuple(int(q) for q in cnt)
+
+
+def mesh_transform(out, tri, R, pivot, shift, spacing, ctx=None):
+    """ns3d_mesh_transform: the rigid motion x → pivot + shift + R·(x − pivot), taken in PHYSICAL space, of a mesh stored in index
+    space (`tri`: a contiguous float64 device array of 9 doubles per triangle) into `out` (the same size; `out is tri` works in place).
+    R: 3×3, pivot and shift in index units, spacing = (dx, dy, dz).  Enqueues; no read-back."""
+    for name, t in (("out", out), ("tri", tri)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() % 9:
+            raise L.Ns3dError("%s must be a contiguous float64 CUDA/HIP tensor of 9 values per triangle" % name)
+    if out.device != tri.device or out.numel() != tri.numel():
+        raise L.Ns3dError("out holds %d values on %s, tri %d on %s" % (out.numel(), out.device, tri.numel(), tri.device))
+    r = np.asarray(R, dtype=np.float64)
+    vec = [np.asarray(v, dtype=np.float64).reshape(-1) for v in (pivot, shift, spacing)]
+    if r.shape != (3, 3) or any(v.size != 3 for v in vec):
+        raise L.Ns3dError("mesh_transform: R is 3x3, pivot, shift and spacing hold 3 numbers each")
+    n_tri = tri.numel() // 9
+    _untyped(ctx, tri, "ns3d_mesh_transform", C.c_void_p(out.data_ptr()) if n_tri else None, C.c_void_p(tri.data_ptr()) if n_tri else None,
+             C.c_longlong(n_tri), (C.c_double * 9)(*r.reshape(-1)), *((C.c_double * 3)(*v) for v in vec))
 
 
 def update_divV(divV, Vx, Vy, Vz, dx, dy, dz, ctx=None):

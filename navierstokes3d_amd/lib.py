@@ -118,6 +118,10 @@ DERIVED_SIGNATURES = {
     # obstacles from a mask (ns3d_voxelize writes one), beside set_cylinder / set_cylinder_local above
     "set_solid": [_P] * 5 + [_I] * 3,
     "solid_momentum": [_P] * 4 + [_I] * 3 + [C.POINTER(_I)] * 2 + [C.POINTER(_D), C.POINTER(C.c_longlong)],
+    # the same two for a body in rigid motion: motion (9 doubles), the spacings and the origin
+    "set_solid_moving": [_P] * 5 + [C.POINTER(_D)] + [_D] * 3 + [C.POINTER(_I)] + [_I] * 3,
+    "solid_momentum_moving": [_P] * 4 + [_I] * 3 + [C.POINTER(_I)] * 2 + [C.POINTER(_D), C.POINTER(C.c_longlong)] +
+                             [C.POINTER(_D)] + [_D] * 3 + [C.POINTER(_I)],
     # the Smagorinsky model: the viscosity field, and update_tau / predict_fused under it
     "eddy_viscosity": [_P] * 4 + [_D] * 6 + [_I] * 3,
     "update_tau_var": [_P] * 10 + [_D] * 3 + [_I] * 3,
@@ -136,7 +140,7 @@ CONTEXT_SYMBOLS = ["ns3d_version", "ns3d_last_error", "ns3d_create", "ns3d_destr
                    "ns3d_set_pt_pace", "ns3d_last_pt_pace", "ns3d_set_pt_pace_test", "ns3d_set_advection", "ns3d_advection",
                    "ns3d_stats_reset", "ns3d_stats_finalize", "ns3d_voxelize", "ns3d_set_obstacle", "ns3d_obstacle",
                    "ns3d_set_turbulence", "ns3d_turbulence", "ns3d_set_sgs_operator", "ns3d_sgs_operator",
-                   "ns3d_set_scalar", "ns3d_scalar"]
+                   "ns3d_set_scalar", "ns3d_scalar", "ns3d_mesh_transform", "ns3d_set_obstacle_motion", "ns3d_obstacle_motion"]
 NS3D_STATS_SLOTS = 11
 
 
@@ -253,6 +257,12 @@ def load():
     lib.ns3d_set_obstacle.restype = _I
     lib.ns3d_obstacle.argtypes = [_P]
     lib.ns3d_obstacle.restype = _P
+    lib.ns3d_mesh_transform.argtypes = [_P, _P, _P, C.c_longlong] + [C.POINTER(_D)] * 4
+    lib.ns3d_mesh_transform.restype = _I
+    lib.ns3d_set_obstacle_motion.argtypes = [_P, C.POINTER(_D), C.POINTER(_I)]
+    lib.ns3d_set_obstacle_motion.restype = _I
+    lib.ns3d_obstacle_motion.argtypes = [_P, C.POINTER(_D)]
+    lib.ns3d_obstacle_motion.restype = _I
     lib.ns3d_set_turbulence.argtypes = [_P, _I, _D, _P]
     lib.ns3d_set_turbulence.restype = _I
     lib.ns3d_turbulence.argtypes = [_P]

@@ -1,8 +1,9 @@
 """Host side of ns3d_voxelize / ns3d_set_solid / ns3d_solid_momentum (include/ns3d.h): obstacles from closed triangle surfaces.  The
 mask — one byte per point of set_cylinder!'s thread range, bit 0 C, 1 Vx, 2 Vy, 3 Vz at their stagger locations — is made on the device
 by libns3d from triangles in the INDEX space of the cell grid ([0,nx]×[0,ny]×[0,nz], cell centres at half-integers); this module
-brings meshes into that space (from an isosurface.Isosurface, a PLY file it wrote, or physical coordinates) and uploads them.  PyTorch
-does no arithmetic here."""
+brings meshes into that space (from an isosurface.Isosurface, a PLY file it wrote, or physical coordinates) and uploads them.  For a
+body in motion (ns3d_mesh_transform / ns3d_set_solid_moving): `transform` poses a mesh on the device, `rigid_motion` makes the pose(t)
+callable the drivers' `motion` keyword takes.  PyTorch does no arithmetic here."""
 import numpy as np
 import torch
 
@@ -40,6 +41,48 @@ def box_mesh(lo, hi):
     c = np.array([[(hi if (n >> q) & 1 else lo)[q] for q in range(3)] for n in range(8)])       # corner n = di + 2 dj + 4 dk
     quads = ((0, 4, 6, 2), (1, 3, 7, 5), (0, 1, 5, 4), (2, 6, 7, 3), (0, 2, 3, 1), (4, 5, 7, 6))  # outward normals −x +x −y +y −z +z
     return np.array([[c[q[0]], c[q[a]], c[q[a + 1]]] for q in quads for a in (1, 2)])
+
+
+def transform(ctx, tri_dev, R, pivot, shift, spacing, out=None):
+    """The mesh `tri_dev` (a contiguous float64 device tensor of 9 values per triangle, index space) in the pose x → pivot + shift +
+    R·(x − pivot), the rotation taken in PHYSICAL space (ns3d_mesh_transform; pivot and shift in index units, spacing = (dx, dy, dz)),
+    into `out` — a new tensor when None, `tri_dev` itself for in place.  Apply a pose to the ORIGINAL mesh, never to the last pose's
+    output.  Enqueues on the context's stream."""
+    if out is None:
+        out = torch.empty_like(tri_dev)
+        ctx.after_torch_fill()
+    K.mesh_transform(out, tri_dev, R, pivot, shift, spacing, ctx=ctx)
+    return out
+
+
+def rotation(omega, t):
+    """Rodrigues' formula: the 3×3 rotation by the angle |omega|·t about omega's direction, NumPy fp64; the identity for omega = 0"""
+    w = np.asarray(omega, dtype=np.float64).reshape(3)
+    rate = float(np.sqrt(np.sum(w * w)))
+    if rate == 0.0:
+        return np.eye(3)
+    kx, ky, kz = w / rate
+    Kx = np.array([[0.0, -kz, ky], [kz, 0.0, -kx], [-ky, kx, 0.0]])
+    a = rate * float(t)
+    return np.eye(3) + np.sin(a) * Kx + (1.0 - np.cos(a)) * (Kx @ Kx)
+
+
+def rigid_motion(velocity=(0.0, 0.0, 0.0), omega=(0.0, 0.0, 0.0), centre=None, spacing=None):
+    """A body in steady rigid motion as the drivers' `motion` keyword takes it: a callable pose(t) → (R, shift, U, omega, centre).
+    velocity U and angular velocity omega are physical (length/time, rad/time); centre is the centre of rotation at t = 0 in index
+    space; spacing = (dx, dy, dz).  R is the rotation by |omega|·t (rotation()), shift = U·t/spacing in index units, centre the
+    centre at time t: centre(0) + shift.  Any callable with this return shape describes a motion — y(t) = A·sin(2πft) with U its
+    derivative, say."""
+    if centre is None or spacing is None:
+        raise L.Ns3dError("rigid_motion needs centre (index space) and spacing (dx, dy, dz)")
+    U, w, c0, d = (np.array(v, dtype=np.float64).reshape(-1) for v in (velocity, omega, centre, spacing))
+    if any(v.size != 3 for v in (U, w, c0, d)) or not all(np.isfinite(v).all() for v in (U, w, c0, d)) or not (d > 0).all():
+        raise L.Ns3dError("rigid_motion: velocity, omega, centre and spacing hold 3 finite numbers each, the spacings > 0")
+
+    def pose(t):
+        shift = U * float(t) / d
+        return rotation(w, t), shift, U.copy(), w.copy(), c0 + shift
+    return pose
 
 
 def to_index(points, spacings, low_corner=(0.0, 0.0, 0.0)):
